@@ -16,7 +16,10 @@ Workloads (synthetic inputs per SURVEY.md 8d: SplitMix64 scalars uniform in [0, 
                       library context per job type), one small all-gather each.  Prints its own JSON line.
 
 K steps are timed between barrier + synchronize pairs; the reported time is the max over ranks; `value` = scalar-muls of
-all ranks / that time.  The JSON line also carries
+all ranks / that time, `ms_per_step` = that time / K.  A plain run does nothing else: set up, warm up, time the K steps, print
+the line.  --dump-outputs DIR also writes the result of the last timed step to DIR/<name>.npy (float64 entries holding the bytes
+of its canonical encoding; the inputs are seeded, so two runs with the same arguments compute the same outputs).
+With --full the JSON line also carries
   roofline        the dominant kernel (bucket accumulation) against the integer-VALU roofline: canonical MAC32 per launch /
                   HIP-event launch time inside the timed region; peak = v_mad_u64_u32 rate measured live
   single_call_ms / end_to_end_h2d_ms   latency of ONE non-pipelined MSM (scalars in HBM -> result in HBM) and of one MSM
@@ -27,6 +30,8 @@ all ranks / that time.  The JSON line also carries
                   reference's criterion points (benches/groups.rs)
   extras          BASELINE configs[2] (2^20 G2 MSM, 2^16 pairings), the 2^18-term multi_miller_loop, each with its
                   canonical roofline fraction (SURVEY.md 8d work units)
+  result_matches_identity / group_path   N > 1: the folded point checked against [sum s_i k_i] G, and the same MSM driven
+                  from one process (bench.py --group N); --workload mixed: jobs_alone_ms and ranks_agree
 """
 import argparse
 import json
@@ -257,6 +262,33 @@ def emit(line):
     sys.stdout.flush()
 
 
+def g1_encoding(bls, ctx, xyz):
+    """a projective G1 result (18 Montgomery limbs) in canonical form: the 96-byte uncompressed encoding of its affine point (the
+    projective limbs are one representative of many; the encoding is unique)"""
+    xy, inf = ctx.batch_normalize(1, np.asarray(xyz).view(np.uint64).reshape(1, 18))
+    return np.frombuffer(bls.G1Affine(xy[0], bool(inf[0])).to_uncompressed(), dtype=np.uint8)
+
+
+def g2_encoding(bls, ctx, xyz):
+    """the same for a projective G2 result (36 limbs): 192 bytes"""
+    xy, inf = ctx.batch_normalize(2, np.asarray(xyz).view(np.uint64).reshape(1, 36))
+    return np.frombuffer(bls.G2Affine(xy[0], bool(inf[0])).to_uncompressed(), dtype=np.uint8)
+
+
+def fp12_encoding(bls, f):
+    """an Fp12 element (72 Montgomery limbs, struct order) as its twelve base-field coefficients, 48 big-endian bytes each: 576 bytes"""
+    f = np.asarray(f).view(np.uint64).reshape(12, 6)
+    return np.frombuffer(b"".join(bls.api.limbs_to_fp(c).to_bytes(48, "big") for c in f), dtype=np.uint8)
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: every named byte array -> d/<name>.npy in float64 (bytes are exact there, and a byte that differs differs by at
+    least 1 -- far outside any floating-point tolerance a comparison may apply)"""
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -277,7 +309,17 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (batched pairings, G2 MSM, latency probes)")
     ap.add_argument("--mixed-log", type=int, nargs=3, default=[22, 22, 18], metavar=("G1", "G2", "MML"),
                     help="--workload mixed: log2 sizes of the three jobs per node (default 22 22 18 = BASELINE configs[4])")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run everything the headline does not need: roofline probes, one-call "
+                    "latencies, CPU baselines, the secondary legs (extras), the result checks of the multi-rank, group and mixed paths, the mixed "
+                    "workload's jobs alone and the device-group run of a multi-rank job (--no-cpu-baseline / --no-extras trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64: the "
+                    "canonical byte encodings of the result points / field elements, one byte per entry)")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def self_launch(args):
@@ -601,9 +643,13 @@ def run_msm(args, e):
     dt = time.perf_counter() - t0
     live_acc_ms, live_acc_n = ctx.msm_accumulate_stats(False)
     dt = max_over_ranks(e, dt)
+    if args.dump_outputs and rank == 0:
+        # the result of the last timed step: the folded sum with several ranks, else the output slot of MSM steps - 1
+        res = (d_fold if multi else d_out[(steps - 1) & 7]).cpu().numpy()
+        dump_outputs(args.dump_outputs, {"g1_msm_result": g1_encoding(bls, ctx, res)})
     aff_rccl = None
     identity_ok = None
-    if multi:
+    if multi and args.full:
         last = d_fold.cpu().numpy().view(np.uint64)
         aff = ctx.batch_normalize(1, last[None, :])[0][0]
         if not ranks_agree(e, aff):
@@ -626,8 +672,8 @@ def run_msm(args, e):
     log_n = int(round(np.log2(n))) if n & (n - 1) == 0 else None
 
     # ---- roofline of the dominant kernel, measured live with HIP events on the library's stream ----------
-    roof = phases = latency = None
-    if rank == 0:
+    roof = phases = latency = peak = None
+    if rank == 0 and args.full:
         # v_mad_u64_u32 lane-ops/s = MAC32/s; the best of three probes (a probe right after a long chip-filling run can read
         # 10 % low, which would flatter every fraction below)
         peak = max(ctx.mad_throughput(2000) for _ in range(3))
@@ -657,7 +703,7 @@ def run_msm(args, e):
                     "16 windows (SURVEY.md 8d); peak = v_mad_u64_u32 issue rate measured in this run",
         }
     # ---- latency of ONE call (SURVEY.md 8d timing protocol) ------------------------------------------------
-    if rank == 0 and not multi and not args.no_extras:
+    if rank == 0 and not multi and args.full and not args.no_extras:
         sync = torch.cuda.synchronize
         single = median_ms(lambda: ctx.msm_device(bases, d_scalars.data_ptr(), n, d_out0.data_ptr()), sync)
         # the same call 40 more times, one after the other (a synchronisation between them): the shader clock climbs for ~35 ms after an idle moment
@@ -721,19 +767,19 @@ def run_msm(args, e):
 
     # ---- CPU baseline: the reference's own definition on the host cores (bounded sample) ------------------
     cpu = None
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if rank == 0 and not multi and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_g1(ctx, bases, sb, n)
 
     # ---- secondary measurements of the same path (BASELINE configs[2]); never part of `value` ---------------
     extras = None
-    if rank == 0 and not multi and not args.no_extras:
+    if rank == 0 and not multi and args.full and not args.no_extras:
         extras = run_extras(args, e, ctx, bases, d_scalars, sb, n, peak, d_out0)
 
     # ---- the same sharded MSM from ONE process (the C library's device group: what a Rust host uses), timed by rank 0 while the other
     # ranks wait at a CPU-side barrier (gloo: an RCCL barrier would spin on their GPUs) ------------------------------------------------
     group_path = None
     # (BENCH_FORCE_GROUP_PATH: run this block with ONE rank too -- how the one-GPU box exercises it)
-    if multi and args.backend == "nccl" and not args.same_device and ((world > 1 and not args.no_extras) or os.environ.get("BENCH_FORCE_GROUP_PATH")):
+    if multi and args.full and args.backend == "nccl" and not args.same_device and ((world > 1 and not args.no_extras) or os.environ.get("BENCH_FORCE_GROUP_PATH")):
         # The group run is a CHILD process of rank 0 with a time limit (`bench.py --group N`, the mode tools/run_scale.sh also uses): its cross-device
         # paths have never run on real multi-GPU hardware (the build box has one GPU), and a fault or a hang there must not cost the line above.
         try:
@@ -1405,9 +1451,14 @@ def run_mixed(args, e):
     for _ in range(warmup):
         step()
     dt = timed((0, 1, 2), steps)
-    alone = [timed((k,), max(1, steps // 2)) for k in range(3)]
-    ok = True
-    if multi:
+    if args.dump_outputs and rank == 0:
+        # the last timed step's three results: the folded sums with several ranks, else this rank's own; gt is the final exponentiation either way
+        r1, r2 = (f1, f2) if multi else (jobs.o1, jobs.o2)
+        dump_outputs(args.dump_outputs, {"g1_msm_result": g1_encoding(bls, fold_ctx, r1.cpu().numpy()), "g2_msm_result": g2_encoding(bls, fold_ctx, r2.cpu().numpy()),
+                                         "multi_miller_loop_final_exp_result": fp12_encoding(bls, gt.cpu().numpy())})
+    alone = [timed((k,), max(1, steps // 2)) for k in range(3)] if args.full else None
+    ok = True if args.full else None
+    if multi and args.full:
         ok = ranks_agree(e, gt.cpu().numpy().view(np.uint64)) and ranks_agree(e, f1.cpu().numpy().view(np.uint64))
     if rank == 0:
         s = [1 << x for x in args.mixed_log]
@@ -1418,8 +1469,8 @@ def run_mixed(args, e):
             "config": {"workload": "2^%d-point G1 MSM + 2^%d-point G2 MSM + 2^%d-term multi_miller_loop with its final exponentiation, sharded over %d MI355X, "
                                    "the three jobs overlapped on separate stream sets, one all-gather (144 / 288 / 576 B per rank) + fold each"
                                    % (args.mixed_log[0], args.mixed_log[1], args.mixed_log[2], world), "parallelism": "shard%d" % world},
-            "jobs_alone_ms": {"g1_msm": 1e3 * alone[0], "g2_msm": 1e3 * alone[1], "multi_miller_loop+final_exp": 1e3 * alone[2]},
-            "sum_of_jobs_alone_ms": 1e3 * sum(alone), "overlap_gain": sum(alone) / dt,
+            "jobs_alone_ms": {"g1_msm": 1e3 * alone[0], "g2_msm": 1e3 * alone[1], "multi_miller_loop+final_exp": 1e3 * alone[2]} if alone else None,
+            "sum_of_jobs_alone_ms": 1e3 * sum(alone) if alone else None, "overlap_gain": sum(alone) / dt if alone else None,
             "rates_overlapped": {"g1_scalar_muls_per_s": s[0] / dt, "g2_scalar_muls_per_s": s[1] / dt, "miller_terms_per_s": s[2] / dt},
             "ranks_agree": ok,
         }
@@ -1432,9 +1483,10 @@ def run_mixed(args, e):
 # =====================================================================================================================
 # the same workload from ONE process: a device group of the C library (what a Rust host without torch.distributed uses)
 # =====================================================================================================================
-def group_measure(bls, torch, devices, total, steps, warmup, weak_n=None, check=True, expect_affine=None):
+def group_measure(bls, torch, devices, total, steps, warmup, weak_n=None, check=True, expect_affine=None, outputs=None):
     """K pipelined sharded MSMs through blsgpu_g1_msm_sharded_device + blsgpu_g1_partials_fold ("enqueue MSM i, fold MSM i - 3"); returns the
-    record of the run.  total = points of the ONE MSM split over the members (strong), or weak_n points per member."""
+    record of the run.  total = points of the ONE MSM split over the members (strong), or weak_n points per member.  A dict passed as
+    `outputs` receives the folded result of the last timed step ("g1_msm_result", canonical encoding)."""
     import ctypes
     from bls12_381_amd import synthetic
     N = len(devices)
@@ -1494,6 +1546,10 @@ def group_measure(bls, torch, devices, total, steps, warmup, weak_n=None, check=
     bls._lib.check(lib.blsgpu_msm_accumulate_stats(g.member_ctx(0), 0, ctypes.byref(avg), ctypes.byref(cnt)), "msm_accumulate_stats")
     rec = {"members": N, "devices": list(devices), "fold": "device (queued on the members' streams)" if device_fold else "host (pinned staging, lag 3)", "distinct_gpus": len(set(devices)), "total_points": n_all, "points_per_member": sizes[0], "steps": steps, "warmup": warmup,
            "ms_per_step": 1e3 * dt / steps, "value": float(n_all) * steps / dt, "member0_accumulate_launch_ms": avg.value, "member0_launches_timed": int(cnt.value)}
+    if outputs is not None:
+        c0 = bls.Context(devices[0])
+        outputs["g1_msm_result"] = g1_encoding(bls, c0, state["last"])
+        c0.close()
     if expect_affine is not None:
         # the same shards, seeds and sizes as the one-process-per-GPU run that precedes this measurement: the two folded sums must agree
         c0 = bls.Context(devices[0])
@@ -1517,7 +1573,7 @@ def group_measure(bls, torch, devices, total, steps, warmup, weak_n=None, check=
 def group_child(args, world, strong, expect_affine, limit_s=420):
     """`bench.py --group <world>` as a child process with a time limit; returns its group_path record (or an error record)"""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--group", str(world), "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-extras", "--log-total", str(args.log_total)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--group", str(world), "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-extras", "--log-total", str(args.log_total)]
     if not strong:
         cmd += ["--weak"] + (["--log-n", str(args.log_n)] if args.log_n is not None else [])
     elif world == 1:                                        # --dist-single: the ONE "shard" is the whole MSM (a group of one is never "strong")
@@ -1554,16 +1610,22 @@ def run_group(args):
     total = (1 << args.log_total) if strong else (1 << log_n) * N
     expect = os.environ.get("BENCH_EXPECT_AFFINE")          # set by group_child(): the folded result of the RCCL run on the same shards
     expect = np.frombuffer(bytes.fromhex(expect), dtype=np.uint64).copy() if expect else None
-    rec = group_measure(bls, torch, devices, total, steps, warmup, weak_n=None if strong else (1 << log_n), expect_affine=expect)
+    outputs = {} if args.dump_outputs else None
+    rec = group_measure(bls, torch, devices, total, steps, warmup, weak_n=None if strong else (1 << log_n), check=args.full,
+                        expect_affine=expect if args.full else None, outputs=outputs)
+    if outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if not rec.get("result_matches", True):
         raise SystemExit("bench --group: the folded MSM result is wrong")
-    ctx = bls.Context(devices[0])
-    peak = max(ctx.mad_throughput(2000) for _ in range(3))
-    windows = (256 + WINDOW_BITS - 1) // WINDOW_BITS
-    mac = float(rec["points_per_member"]) * windows * MAC32_G1_ADD
-    dur = rec["member0_accumulate_launch_ms"] * 1e-3
-    roof = {"bound": "int-valu", "kernel": "k_msm_accumulate<G1> (member 0)", "achieved": mac / dur / 1e12 if dur else None, "peak": peak / 1e12, "unit": "TMAC32/s",
-            "frac": mac / dur / peak if dur else None, "traffic": None, "launch_ms": rec["member0_accumulate_launch_ms"]}
+    roof = None
+    if args.full:
+        ctx = bls.Context(devices[0])
+        peak = max(ctx.mad_throughput(2000) for _ in range(3))
+        windows = (256 + WINDOW_BITS - 1) // WINDOW_BITS
+        mac = float(rec["points_per_member"]) * windows * MAC32_G1_ADD
+        dur = rec["member0_accumulate_launch_ms"] * 1e-3
+        roof = {"bound": "int-valu", "kernel": "k_msm_accumulate<G1> (member 0)", "achieved": mac / dur / 1e12 if dur else None, "peak": peak / 1e12, "unit": "TMAC32/s",
+                "frac": mac / dur / peak if dur else None, "traffic": None, "launch_ms": rec["member0_accumulate_launch_ms"]}
     workload = ("ONE 2^%d-point G1 MSM sharded over %d members of a blsgpu_group in ONE process (%d distinct GPUs; %d points per member), bases and scalars resident in HBM; "
                 "one folded result per step" % (args.log_total, N, rec["distinct_gpus"], rec["points_per_member"])) if strong else (
                 "2^%d-point G1 MSM per member of a blsgpu_group of %d in ONE process (%d distinct GPUs), bases and scalars resident in HBM; one folded result per step"

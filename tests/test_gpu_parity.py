@@ -1551,7 +1551,7 @@ def test_device_variants_of_miller_final_exp_product(ctx):
 
 
 @pytest.mark.parametrize("workload", ["msm", "mixed"])
-def test_bench_distributed_branch_over_rccl_with_one_rank(workload):
+def test_bench_distributed_branch_over_rccl_with_one_rank(workload, tmp_path):
     """bench.py's N > 1 code path -- process group on backend "nccl" (= RCCL) bound to the device, the (world, words) int64
     all-gather of the partial sums on the GPU, the device-side fold, the max / min all-reduces of the timing and agreement
     checks -- executed for real with a single rank (`--dist-single`): a one-GPU box cannot run two RCCL ranks, but every
@@ -1561,7 +1561,7 @@ def test_bench_distributed_branch_over_rccl_with_one_rank(workload):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dist-single", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(tmp_path)]
     if workload == "msm":
         cmd += ["--log-total", "18"]
     else:
@@ -1578,8 +1578,15 @@ def test_bench_distributed_branch_over_rccl_with_one_rank(workload):
         # the one-process device-group measurement a multi-rank run appends (rank 0 drives every GPU while the others wait at a CPU-side barrier)
         gp = line["group_path"]
         assert "error" not in gp and gp["result_matches"] is True and gp["total_points"] == 1 << 18 and gp["value"] > 0
+        sizes = {"g1_msm_result": 96}
     else:
         assert line["ranks_agree"] is True
+        sizes = {"g1_msm_result": 96, "g2_msm_result": 192, "multi_miller_loop_final_exp_result": 576}
+    # --dump-outputs: the folded results of the last step, as float64 bytes
+    assert sorted(os.listdir(str(tmp_path))) == sorted(k + ".npy" for k in sizes)
+    for k, sz in sizes.items():
+        a = np.load(str(tmp_path / (k + ".npy")))
+        assert a.dtype == np.float64 and a.shape == (sz,) and np.array_equal(a, np.round(a)) and 0 <= a.min() and a.max() <= 255 and a.any()
 
 
 def test_msm_g2_psi_decomposition_boundaries(ctx, monkeypatch):
@@ -2913,7 +2920,7 @@ def test_bench_two_ranks_on_one_gpu_runs_the_exchange_with_real_kernels():
     sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()          # a free port, not a fixed one
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--log-total", "18", "--steps", "4", "--warmup", "2",
-           "--no-cpu-baseline", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-extras"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -2921,6 +2928,34 @@ def test_bench_two_ranks_on_one_gpu_runs_the_exchange_with_real_kernels():
     assert line["result_matches_identity"] is True
     assert line["ranks"]["world"] == 2 and line["ranks"]["world_from_process_group"] == 2 and line["ranks"]["backend"] == "gloo" and line["ranks"]["same_device"] is True
     assert line["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_step_reproducibly(tmp_path):
+    """A plain `bench.py` run (no --full) prints the contract's keys and nothing it does not time; --dump-outputs writes the last step's MSM
+    result, which is [sum s_i k_i] G by the oracle, and two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    import sys
+    from bls12_381_amd import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for k in (0, 1):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--log-n", "14", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / str(k))]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line.get(key) is not None, key
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx((1 << 14) / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert "roofline" not in line and "cpu_baseline" not in line and "extras" not in line and "single_call_ms" not in line
+    got = [np.load(str(tmp_path / str(k) / "g1_msm_result.npy")) for k in (0, 1)]
+    assert got[0].dtype == np.float64 and got[0].shape == (96,) and np.array_equal(got[0], got[1])
+    n = 1 << 14
+    t = synthetic.dot_mod_r(synthetic.scalars(n, synthetic.SEED), synthetic.scalars(n, synthetic.SEED + 1))
+    want = o.g1_to_uncompressed(o.g1_to_affine(o.g1_affine_mul(o.G1_GEN, t)))
+    assert bytes(got[0].astype(np.uint8)) == want
 
 
 def test_round6_entry_points_edge_cases_and_argument_errors(ctx):

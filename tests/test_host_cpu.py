@@ -268,6 +268,37 @@ def test_bench_launch_contract():
     assert [shard_range(1 << 24, r, 8)[1] - shard_range(1 << 24, r, 8)[0] for r in range(8)] == [1 << 21] * 8
 
 
+def test_bench_plain_and_full_options_and_output_dumps(kats, tmp_path):
+    """a plain `bench.py` run times the steps only (`--full` adds the rest), `--steps` below 1 is refused, and `--dump-outputs` writes
+    float64 .npy files whose entries are the bytes of the canonical encodings, exactly"""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    import bls12_381_amd as b
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", str(tmp_path)]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == str(tmp_path)
+        for bad in (["--steps", "0"], ["--warmup", "-1"]):
+            sys.argv = ["bench.py"] + bad
+            with pytest.raises(SystemExit):
+                bench.parse()
+    finally:
+        sys.argv = old
+    # Gt = e(G1, G2) from the golden constants: its encoding is the twelve coefficients, 48 big-endian bytes each
+    gt = np.array(kats["consts"]["pairings.GT_GENERATOR"], dtype=np.uint64).reshape(72)
+    enc = bench.fp12_encoding(b, gt)
+    assert enc.dtype == np.uint8 and enc.shape == (576,)
+    assert [int.from_bytes(enc[48 * i:48 * i + 48].tobytes(), "big") for i in range(12)] == [o.fp_from_mont_limbs([int(x) for x in gt[6 * i:6 * i + 6]]) for i in range(12)]
+    bench.dump_outputs(str(tmp_path / "d"), {"gt": enc})
+    back = np.load(str(tmp_path / "d" / "gt.npy"))
+    assert back.dtype == np.float64 and np.array_equal(back.astype(np.uint8), enc) and np.array_equal(back, enc.astype(np.float64))
+
+
 # ---- the Rust side of the boundary (rust/bls12_381-hip): no toolchain here, so it is checked by structure -------------------
 _RUST_TYPES = {"c_int": "int", "usize": "size_t", "c_uint": "unsigned", "*mut BlsgpuCtx": "blsgpu_ctx*", "*mut *mut BlsgpuCtx": "blsgpu_ctx**",
                "*mut BlsgpuBases": "blsgpu_bases*", "*const BlsgpuBases": "const blsgpu_bases*", "*mut *mut BlsgpuBases": "blsgpu_bases**",

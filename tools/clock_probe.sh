@@ -1,7 +1,7 @@
 #!/bin/bash
 # Samples GPU clock / power / utilisation while the headline bench runs (is the VALU-bound kernel clock- or power-limited?).
 #   bash tools/clock_probe.sh > gpurun_out/clock_probe.log
-python bench.py --steps 4000 --warmup 5 --no-cpu-baseline --no-extras > /tmp/clock_probe_bench.log 2>&1 &
+python bench.py --steps 4000 --warmup 5 --full --no-cpu-baseline --no-extras > /tmp/clock_probe_bench.log 2>&1 &
 BPID=$!
 n=0
 while kill -0 $BPID 2>/dev/null && [ $n -lt 400 ]; do

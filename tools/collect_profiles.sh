@@ -6,11 +6,12 @@
 #   gpurun_out/prof_wide       ... and for 2^8 pairings per call (the wide small-batch kernel)
 # tools/summarise_profiles.py <round> turns them into profiles/<round>_*.md / .json.
 R="${GRAFT_REPO_ROOT:-$PWD}"; cd "$R"
-tools/pmc.sh prof_msm python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras
+tools/pmc.sh prof_msm python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras
 # the stats pass of prof_msm is replaced by one over the DEFAULT command, whose bench line is kept next to it
 cd /tmp && export TMPDIR=/tmp && cd "$R"
-rm -rf gpurun_out/prof_msm/stats
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_msm/stats -- python bench.py --no-cpu-baseline --no-extras > gpurun_out/prof_msm/bench_under_rocprof.json 2> /dev/null
+MSM="$(ls -d */prof_msm | head -1)"           # the directory tools/pmc.sh wrote for prof_msm above
+rm -rf "$MSM/stats"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$MSM/stats" -- python bench.py --full --no-cpu-baseline --no-extras > "$MSM/bench_under_rocprof.json" 2> /dev/null
 tools/pmc.sh prof_pair python tools/run_pairing.py pairing 16 3
 BLSGPU_PAIRING_LAYOUT=pair tools/pmc.sh prof_pair_lp python tools/run_pairing.py pairing 16 3
 tools/pmc.sh prof_mml python tools/run_pairing.py mml 18 3

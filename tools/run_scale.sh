@@ -10,9 +10,9 @@ for N in 1 2 4 8; do
   if [ "$N" -le "$NG" ]; then
     # (the line carries "ranks": the process group's own world size, the backend, lazy / eager RCCL communicator, devices visible -- and
     # "result_matches_identity": the folded point checked against [sum s_i k_i] G)
-    python bench.py --gpus $N --no-cpu-baseline --no-extras "$@" | tail -1
+    python bench.py --gpus $N --full --no-cpu-baseline --no-extras "$@" | tail -1
     # the same sharded MSM from ONE process (the C library's device group; round 5)
-    python bench.py --group $N --no-cpu-baseline --no-extras "$@" | tail -1
+    python bench.py --group $N --full --no-cpu-baseline --no-extras "$@" | tail -1
   else
     echo "{\"n_gpus\": $N, \"skipped\": \"only $NG GPU(s) visible\"}"
   fi
