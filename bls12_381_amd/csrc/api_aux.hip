@@ -21,15 +21,20 @@ static int expand_launch(blsgpu_ctx* c, int expander, const uint8_t* msgs, const
   LAUNCHCHK();
   return BLSGPU_OK;
 }
+// uniform bytes -> from_okm -> map_to_curve -> (sum) -> clear_h
+static int uniform_launch(blsgpu_ctx* c, int group, const uint8_t* uniform, size_t n, int encode_only, u32* out) {
+  if (group == 1) KLAUNCH(k_hash_to_curve_uniform<FpPolicy>, dim3(nblk(n, 64)), dim3(64), 0, c->stream, uniform, n, encode_only ? 1 : 0, out);
+  else KLAUNCH(k_hash_to_curve_uniform<Fp2PairPolicy>, dim3(nblk(n * 2, 256)), dim3(256), 0, c->stream, uniform, n, encode_only ? 1 : 0, out);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
 static int h2c_launch(blsgpu_ctx* c, int group, int expander, const uint8_t* msgs, const unsigned long long* offs, size_t n, const uint8_t* dst, u32 dlen, int encode_only, u32* out) {
   if (expander != EXPAND_XMD_SHA256) {
     // the reference's other expanders (expand_msg.rs:167-328 over SHA-512 / SHAKE128 / SHAKE256): expand, then map from the uniform bytes
     const u32 len = (u32)((encode_only ? 1 : 2) * (group == 1 ? 1 : 2) * 64);
     if (c->h2c_uniform.reserve(n * (size_t)len)) { g_err = "hipMalloc(uniform bytes) failed"; return BLSGPU_ERR_HIP; }
     if (int rc = expand_launch(c, expander, msgs, offs, n, dst, dlen, len, c->h2c_uniform.as<uint8_t>())) return rc;
-    if (group == 1) KLAUNCH(k_hash_to_curve_uniform<FpPolicy>, dim3(nblk(n, 64)), dim3(64), 0, c->stream, c->h2c_uniform.as<uint8_t>(), n, encode_only ? 1 : 0, out);
-    else KLAUNCH(k_hash_to_curve_uniform<Fp2PairPolicy>, dim3(nblk(n * 2, 256)), dim3(256), 0, c->stream, c->h2c_uniform.as<uint8_t>(), n, encode_only ? 1 : 0, out);
-    return BLSGPU_OK;
+    return uniform_launch(c, group, c->h2c_uniform.as<uint8_t>(), n, encode_only, out);
   }
   const int forced = c->h2c_split;
   const bool split = !encode_only && (forced >= 0 ? forced == 1 : n <= (group == 1 ? (size_t)1 << 15 : (size_t)1 << 14));
@@ -40,52 +45,57 @@ static int h2c_launch(blsgpu_ctx* c, int group, int expander, const uint8_t* msg
     if (split) KLAUNCH(k_hash_to_curve_split<Fp2PairPolicy>, dim3(nblk(n * 4, 256)), dim3(256), 0, c->stream, msgs, offs, n, dst, dlen, out);
     else KLAUNCH(k_hash_to_curve<Fp2PairPolicy>, dim3(nblk(n * 2, 256)), dim3(256), 0, c->stream, msgs, offs, n, dst, dlen, encode_only ? 1 : 0, out);
   }
-  return BLSGPU_OK;
-}
-template <class F>
-static int h2c_host(blsgpu_ctx* c, int expander, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, int encode_only,
-                    uint64_t* out) {
-  if (expander < EXPAND_XMD_SHA256 || expander > EXPAND_XOF_SHAKE256) return bad("hash_to_curve: unknown expander");
-  if (!c || (n && (!offsets || !out)) || (dst_len && !dst)) return bad("hash_to_curve: NULL argument");
-  if (!n) return BLSGPU_OK;
-  const size_t total = (size_t)offsets[n];
-  for (size_t i = 0; i < n; i++) if (offsets[i] > offsets[i + 1]) return bad("hash_to_curve: offsets must be non-decreasing");
-  if (total && !msgs) return bad("hash_to_curve: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  // a DST longer than 255 bytes is replaced by H("H2C-OVERSIZE-DST-" || DST)  (expand_msg.rs:47-95)
-  uint8_t d[255];
-  const u32 dlen = h2c_reduce_dst(expander, dst, dst_len, d);
-  constexpr int WW = Wire<F>::WORDS;
-  if (c->io_a.reserve(total + 16) || c->io_b.reserve((n + 1) * 8) || c->io_c.reserve(256) || c->io_out.reserve(n * 3 * WW * 4)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (total) HIPCHK(hipMemcpyAsync(c->io_a.p, msgs, total, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->io_b.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (dlen) HIPCHK(hipMemcpyAsync(c->io_c.p, d, dlen, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));                 // `d` lives on this stack frame
-  { int rl = h2c_launch(c, GroupTag<F>::id, expander, c->io_a.as<uint8_t>(), (const unsigned long long*)c->io_b.p, n, c->io_c.as<uint8_t>(), dlen, encode_only, c->io_out.as<u32>()); if (rl) return rl; }
   LAUNCHCHK();
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * 3 * WW * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
   return BLSGPU_OK;
 }
-extern "C" int blsgpu_g1_hash_to_curve_batch(blsgpu_ctx* c, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len,
-                                             int encode_only, uint64_t* out_xyz) { CTX_CLAIM(c);
-  return h2c_host<FpPolicy>(c, EXPAND_XMD_SHA256, msgs, offsets, n, dst, dst_len, encode_only, out_xyz);
+// Messages (offsets[0..n] into msgs), offsets and DST of the host forms: the offsets are scanned, then the three are staged into io_a / io_b /
+// io_f (a DST longer than 255 bytes reduced to H("H2C-OVERSIZE-DST-" || DST) first, expand_msg.rs:47-95).  The device pointers come back
+// through d_msgs / d_offs / d_dst, the length of the staged DST through *dlen.
+static int stage_messages(HostCall& h, const char* offsets_msg, const char* msgs_msg, int expander, const uint8_t* msgs, const uint64_t* offsets, size_t n,
+                          const uint8_t* dst, size_t dst_len, void** d_msgs, void** d_offs, void** d_dst, u32* dlen) {
+  if (!scan_offsets(offsets, n)) return bad(offsets_msg);
+  const size_t total = (size_t)offsets[n];
+  if (total && !msgs) return bad(msgs_msg);
+  blsgpu_ctx* c = h.c;
+  *dlen = h2c_reduce_dst(expander, dst, dst_len, h.keep);
+  *d_msgs = h.in(c->io_a, msgs, total);
+  *d_offs = h.in(c->io_b, offsets, (n + 1) * 8);
+  *d_dst = h.in(c->io_f, h.keep, *dlen);
+  return h.rc;
 }
-extern "C" int blsgpu_g2_hash_to_curve_batch(blsgpu_ctx* c, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len,
-                                             int encode_only, uint64_t* out_xyz) { CTX_CLAIM(c);
-  return h2c_host<Fp2Policy>(c, EXPAND_XMD_SHA256, msgs, offsets, n, dst, dst_len, encode_only, out_xyz);
+// the arguments of every hash-to-curve form (dst_max: 255 for the device forms, which take a reduced DST; no bound on the host)
+static int h2c_check(blsgpu_ctx* c, int group, int expander, const void* offsets, size_t n, const void* dst, size_t dst_len, size_t dst_max, const void* out) {
+  if (!c || (n && (!offsets || !out)) || (dst_len && !dst)) return bad("hash_to_curve: NULL argument");
+  if (dst_len > dst_max) return bad("hash_to_curve_device: reduce a DST longer than 255 bytes on the host first");
+  if (group != 1 && group != 2) return bad("hash_to_curve: group must be 1 or 2");
+  if (expander < EXPAND_XMD_SHA256 || expander > EXPAND_XOF_SHAKE256) return bad("hash_to_curve: unknown expander");
+  return BLSGPU_OK;
 }
 // device-resident variant: messages, offsets (n + 1 u64) and the DST (<= 255 bytes) already in device memory
 static int h2c_device(blsgpu_ctx* c, int group, int expander, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst, size_t dst_len, int encode_only, void* d_out_xyz) {
-  if (!c || (n && (!d_offsets || !d_out_xyz)) || (dst_len && !d_dst)) return bad("hash_to_curve: NULL argument");
-  if (dst_len > 255) return bad("hash_to_curve_device: reduce a DST longer than 255 bytes on the host first");
-  if (group != 1 && group != 2) return bad("hash_to_curve: group must be 1 or 2");
-  if (expander < EXPAND_XMD_SHA256 || expander > EXPAND_XOF_SHAKE256) return bad("hash_to_curve: unknown expander");
+  if (int rc = h2c_check(c, group, expander, d_offsets, n, d_dst, dst_len, 255, d_out_xyz)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  if (int rc = h2c_launch(c, group, expander, (const uint8_t*)d_msgs, (const unsigned long long*)d_offsets, n, (const uint8_t*)d_dst, (u32)dst_len, encode_only, (u32*)d_out_xyz)) return rc;
-  LAUNCHCHK();
-  return BLSGPU_OK;
+  return h2c_launch(c, group, expander, (const uint8_t*)d_msgs, (const unsigned long long*)d_offsets, n, (const uint8_t*)d_dst, (u32)dst_len, encode_only, (u32*)d_out_xyz);
+}
+static int h2c_host(blsgpu_ctx* c, int group, int expander, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, int encode_only,
+                    uint64_t* out) {
+  if (int rc = h2c_check(c, group, expander, offsets, n, dst, dst_len, (size_t)-1, out)) return rc;
+  if (!n) return BLSGPU_OK;
+  HostCall h(c);
+  void *m, *o, *d; u32 dlen;
+  if (int rc = stage_messages(h, "hash_to_curve: offsets must be non-decreasing", "hash_to_curve: NULL argument", expander, msgs, offsets, n, dst, dst_len, &m, &o, &d, &dlen)) return rc;
+  void* x = h.out(c->io_out, out, n * 3 * (group == 1 ? 12 : 24) * 4);
+  if (h.rc) return h.rc;
+  return h.finish(h2c_device(c, group, expander, m, o, n, d, dlen, encode_only, x));
+}
+extern "C" int blsgpu_g1_hash_to_curve_batch(blsgpu_ctx* c, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len,
+                                             int encode_only, uint64_t* out_xyz) { CTX_CLAIM(c);
+  return h2c_host(c, 1, EXPAND_XMD_SHA256, msgs, offsets, n, dst, dst_len, encode_only, out_xyz);
+}
+extern "C" int blsgpu_g2_hash_to_curve_batch(blsgpu_ctx* c, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len,
+                                             int encode_only, uint64_t* out_xyz) { CTX_CLAIM(c);
+  return h2c_host(c, 2, EXPAND_XMD_SHA256, msgs, offsets, n, dst, dst_len, encode_only, out_xyz);
 }
 extern "C" int blsgpu_hash_to_curve_device(blsgpu_ctx* c, int group, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst, size_t dst_len,
                                            int encode_only, void* d_out_xyz) { CTX_CLAIM(c);
@@ -96,111 +106,105 @@ extern "C" int blsgpu_hash_to_curve_device(blsgpu_ctx* c, int group, const void*
 // ExpandMsgXof<Shake128 | Shake256> (expand_msg.rs:167-328)
 extern "C" int blsgpu_hash_to_curve_expander_batch(blsgpu_ctx* c, int group, int expander, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len,
                                                    int encode_only, uint64_t* out_xyz) { CTX_CLAIM(c);
-  if (group != 1 && group != 2) return bad("hash_to_curve: group must be 1 or 2");
-  return group == 1 ? h2c_host<FpPolicy>(c, expander, msgs, offsets, n, dst, dst_len, encode_only, out_xyz) : h2c_host<Fp2Policy>(c, expander, msgs, offsets, n, dst, dst_len, encode_only, out_xyz);
+  return h2c_host(c, group, expander, msgs, offsets, n, dst, dst_len, encode_only, out_xyz);
 }
 extern "C" int blsgpu_hash_to_curve_expander_device(blsgpu_ctx* c, int group, int expander, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst, size_t dst_len,
                                                     int encode_only, void* d_out_xyz) { CTX_CLAIM(c);
   return h2c_device(c, group, expander, d_msgs, d_offsets, n, d_dst, dst_len, encode_only, d_out_xyz);
 }
 // the part behind the expander: caller-supplied uniform bytes -> from_okm -> map_to_curve -> (sum) -> clear_h
-extern "C" int blsgpu_hash_to_curve_from_uniform_device(blsgpu_ctx* c, int group, const void* d_uniform, size_t n, int encode_only, void* d_out_xyz) { CTX_CLAIM(c);
-  if (!c || (n && (!d_uniform || !d_out_xyz))) return bad("hash_to_curve_from_uniform: NULL argument");
+static int from_uniform_check(blsgpu_ctx* c, int group, const void* uniform, size_t n, const void* out) {
+  if (!c || (n && (!uniform || !out))) return bad("hash_to_curve_from_uniform: NULL argument");
   if (group != 1 && group != 2) return bad("hash_to_curve: group must be 1 or 2");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_hash_to_curve_from_uniform_device(blsgpu_ctx* c, int group, const void* d_uniform, size_t n, int encode_only, void* d_out_xyz) { CTX_CLAIM(c);
+  if (int rc = from_uniform_check(c, group, d_uniform, n, d_out_xyz)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  if (group == 1) KLAUNCH(k_hash_to_curve_uniform<FpPolicy>, dim3(nblk(n, 64)), dim3(64), 0, c->stream, (const uint8_t*)d_uniform, n, encode_only ? 1 : 0, (u32*)d_out_xyz);
-  else KLAUNCH(k_hash_to_curve_uniform<Fp2PairPolicy>, dim3(nblk(n * 2, 256)), dim3(256), 0, c->stream, (const uint8_t*)d_uniform, n, encode_only ? 1 : 0, (u32*)d_out_xyz);
-  LAUNCHCHK();
-  return BLSGPU_OK;
+  return uniform_launch(c, group, (const uint8_t*)d_uniform, n, encode_only, (u32*)d_out_xyz);
 }
 extern "C" int blsgpu_hash_to_curve_from_uniform_batch(blsgpu_ctx* c, int group, const uint8_t* uniform, size_t n, int encode_only, uint64_t* out_xyz) { CTX_CLAIM(c);
-  if (!c || (n && (!uniform || !out_xyz))) return bad("hash_to_curve_from_uniform: NULL argument");
-  if (group != 1 && group != 2) return bad("hash_to_curve: group must be 1 or 2");
+  if (int rc = from_uniform_check(c, group, uniform, n, out_xyz)) return rc;
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  const size_t per = (size_t)(encode_only ? 1 : 2) * (group == 1 ? 1 : 2) * 64, ob = n * 3 * (group == 1 ? 12 : 24) * 4;
-  if (c->io_a.reserve(n * per) || c->io_out.reserve(ob)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, uniform, n * per, hipMemcpyHostToDevice, c->stream));
-  if (int rc = blsgpu_hash_to_curve_from_uniform_device(c, group, c->io_a.p, n, encode_only, c->io_out.p)) return rc;
-  HIPCHK(hipMemcpyAsync(out_xyz, c->io_out.p, ob, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  const size_t per = (size_t)(encode_only ? 1 : 2) * (group == 1 ? 1 : 2) * 64;
+  void* u = h.in(c->io_a, uniform, n * per);
+  void* o = h.out(c->io_out, out_xyz, n * 3 * (group == 1 ? 12 : 24) * 4);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_hash_to_curve_from_uniform_device(c, group, u, n, encode_only, o));
 }
-// `ExpandMessage::init_expand` + reading all `len_in_bytes` bytes, per message (out: n x len_in_bytes)
-extern "C" int blsgpu_expand_message_device(blsgpu_ctx* c, int expander, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst, size_t dst_len, size_t len_in_bytes,
-                                            void* d_out) { CTX_CLAIM(c);
-  if (!c || (n && (!d_offsets || !d_out)) || (dst_len && !d_dst)) return bad("expand_message: NULL argument");
+// `ExpandMessage::init_expand` + reading all `len_in_bytes` bytes, per message (out: n x len_in_bytes); dst_max as for h2c_check
+static int expand_check(blsgpu_ctx* c, int expander, const void* offsets, size_t n, const void* dst, size_t dst_len, size_t dst_max, size_t len_in_bytes, const void* out) {
+  if (!c || (n && (!offsets || !out)) || (dst_len && !dst)) return bad("expand_message: NULL argument");
   if (expander < EXPAND_XMD_SHA256 || expander > EXPAND_XOF_SHAKE256) return bad("expand_message: unknown expander");
-  if (dst_len > 255) return bad("expand_message_device: reduce a DST longer than 255 bytes on the host first");
+  if (dst_len > dst_max) return bad("expand_message_device: reduce a DST longer than 255 bytes on the host first");
   // expand_msg.rs:181-183, :263-268: the reference panics beyond these
   if (len_in_bytes > 65535) return bad("expand_message: len_in_bytes must not exceed 65535");
   if (expander <= EXPAND_XMD_SHA512 && (len_in_bytes + (expander == EXPAND_XMD_SHA256 ? 31 : 63)) / (expander == EXPAND_XMD_SHA256 ? 32 : 64) > 255) return bad("expand_message: more than 255 digest blocks");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_expand_message_device(blsgpu_ctx* c, int expander, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst, size_t dst_len, size_t len_in_bytes,
+                                            void* d_out) { CTX_CLAIM(c);
+  if (int rc = expand_check(c, expander, d_offsets, n, d_dst, dst_len, 255, len_in_bytes, d_out)) return rc;
   if (!n || !len_in_bytes) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   return expand_launch(c, expander, (const uint8_t*)d_msgs, (const unsigned long long*)d_offsets, n, (const uint8_t*)d_dst, (u32)dst_len, (u32)len_in_bytes, (uint8_t*)d_out);
 }
-// messages / offsets / DST from the host into io_a / io_b / io_c (the DST reduced if it is longer than 255 bytes); returns the DST length through *dlen
-static int h2c_stage(blsgpu_ctx* c, int expander, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, u32* dlen) {
-  if (expander < EXPAND_XMD_SHA256 || expander > EXPAND_XOF_SHAKE256) return bad("unknown expander");
-  const size_t total = (size_t)offsets[n];
-  for (size_t i = 0; i < n; i++) if (offsets[i] > offsets[i + 1]) return bad("offsets must be non-decreasing");
-  if (total && !msgs) return bad("NULL messages");
-  HIPCHK(hipSetDevice(c->device));
-  uint8_t d[255];
-  *dlen = h2c_reduce_dst(expander, dst, dst_len, d);
-  if (c->io_a.reserve(total + 16) || c->io_b.reserve((n + 1) * 8) || c->io_c.reserve(256)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (total) HIPCHK(hipMemcpyAsync(c->io_a.p, msgs, total, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->io_b.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (*dlen) HIPCHK(hipMemcpyAsync(c->io_c.p, d, *dlen, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));                 // `d` lives on this stack frame
-  return BLSGPU_OK;
-}
 extern "C" int blsgpu_expand_message_batch(blsgpu_ctx* c, int expander, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, size_t len_in_bytes,
                                            uint8_t* out) { CTX_CLAIM(c);
-  if (!c || (n && (!offsets || !out)) || (dst_len && !dst)) return bad("expand_message: NULL argument");
+  if (int rc = expand_check(c, expander, offsets, n, dst, dst_len, (size_t)-1, len_in_bytes, out)) return rc;
   if (!n || !len_in_bytes) return BLSGPU_OK;
-  u32 dlen = 0;
-  if (int rc = h2c_stage(c, expander, msgs, offsets, n, dst, dst_len, &dlen)) return rc;
-  if (c->io_out.reserve(n * len_in_bytes)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (int rc = blsgpu_expand_message_device(c, expander, c->io_a.p, c->io_b.p, n, c->io_c.p, dlen, len_in_bytes, c->io_out.p)) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * len_in_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  void *m, *o, *d; u32 dlen;
+  if (int rc = stage_messages(h, "offsets must be non-decreasing", "NULL messages", expander, msgs, offsets, n, dst, dst_len, &m, &o, &d, &dlen)) return rc;
+  void* x = h.out(c->io_out, out, n * len_in_bytes);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_expand_message_device(c, expander, m, o, n, d, dlen, len_in_bytes, x));
 }
 // `hash_to_field::<X, Scalar>` (mod.rs:32-49 with map_scalar.rs:10-25): `count` scalars per message as Montgomery limbs (out: n x count x 4 u64)
+static int hash_to_scalar_check(blsgpu_ctx* c, const void* offsets, size_t n, const void* dst, size_t dst_len, size_t count, const void* out) {
+  if (!c || (n && count && (!offsets || !out)) || (dst_len && !dst)) return bad("hash_to_scalar: NULL argument");
+  if (count > 65535 / 48) return bad("hash_to_scalar: count * 48 must not exceed 65535 (expand_msg.rs:181-183)");
+  return BLSGPU_OK;
+}
 extern "C" int blsgpu_hash_to_scalar_device(blsgpu_ctx* c, int expander, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst, size_t dst_len, size_t count,
                                             void* d_out) { CTX_CLAIM(c);
-  if (!c || (n && count && (!d_offsets || !d_out)) || (dst_len && !d_dst)) return bad("hash_to_scalar: NULL argument");
-  if (count > 65535 / 48) return bad("hash_to_scalar: count * 48 must not exceed 65535 (expand_msg.rs:181-183)");
+  if (int rc = hash_to_scalar_check(c, d_offsets, n, d_dst, dst_len, count, d_out)) return rc;
   if (!n || !count) return BLSGPU_OK;
+  if (int rc = expand_check(c, expander, d_offsets, n, d_dst, dst_len, 255, count * 48, d_out)) return rc;
   HIPCHK(hipSetDevice(c->device));
   if (c->h2c_uniform.reserve(n * count * 48)) { g_err = "hipMalloc(uniform bytes) failed"; return BLSGPU_ERR_HIP; }
-  if (int rc = blsgpu_expand_message_device(c, expander, d_msgs, d_offsets, n, d_dst, dst_len, count * 48, c->h2c_uniform.p)) return rc;
+  if (int rc = expand_launch(c, expander, (const uint8_t*)d_msgs, (const unsigned long long*)d_offsets, n, (const uint8_t*)d_dst, (u32)dst_len, (u32)(count * 48),
+                             c->h2c_uniform.as<uint8_t>())) return rc;
   KLAUNCH(k_hash_to_scalar, dim3(nblk(n * count, 256)), dim3(256), 0, c->stream, c->h2c_uniform.as<uint8_t>(), n * count, (u32*)d_out);
   LAUNCHCHK();
   return BLSGPU_OK;
 }
 extern "C" int blsgpu_hash_to_scalar_batch(blsgpu_ctx* c, int expander, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, size_t count,
                                            uint64_t* out) { CTX_CLAIM(c);
-  if (!c || (n && count && (!offsets || !out)) || (dst_len && !dst)) return bad("hash_to_scalar: NULL argument");
+  if (int rc = hash_to_scalar_check(c, offsets, n, dst, dst_len, count, out)) return rc;
   if (!n || !count) return BLSGPU_OK;
-  u32 dlen = 0;
-  if (int rc = h2c_stage(c, expander, msgs, offsets, n, dst, dst_len, &dlen)) return rc;
-  if (c->io_out.reserve(n * count * 32)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (int rc = blsgpu_hash_to_scalar_device(c, expander, c->io_a.p, c->io_b.p, n, c->io_c.p, dlen, count, c->io_out.p)) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * count * 32, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  if (int rc = expand_check(c, expander, offsets, n, dst, dst_len, (size_t)-1, count * 48, out)) return rc;
+  HostCall h(c);
+  void *m, *o, *d; u32 dlen;
+  if (int rc = stage_messages(h, "offsets must be non-decreasing", "NULL messages", expander, msgs, offsets, n, dst, dst_len, &m, &o, &d, &dlen)) return rc;
+  void* x = h.out(c->io_out, out, n * count * 32);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_hash_to_scalar_device(c, expander, m, o, n, d, dlen, count, x));
 }
 
 // ---------------------------------------------------------------------------------------------------
 // scalar field Fr: element-wise vector operations and the radix-2 transform (fr.hip.h)
 // ---------------------------------------------------------------------------------------------------
-extern "C" int blsgpu_fr_op_device(blsgpu_ctx* c, int op, const void* a, const void* b, size_t n, void* out, void* nonzero_flags) { CTX_CLAIM(c);
+static int fr_op_check(blsgpu_ctx* c, int op, const void* a, const void* b, size_t n, const void* out) {
   if (!c || (n && (!a || !out))) return bad("fr_op: NULL argument");
   if (op < 0 || op > 6) return bad("fr_op: unknown op");
   if (op <= 2 && n && !b) return bad("fr_op: binary op needs b");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_op_device(blsgpu_ctx* c, int op, const void* a, const void* b, size_t n, void* out, void* nonzero_flags) { CTX_CLAIM(c);
+  if (int rc = fr_op_check(c, op, a, b, n, out)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   KLAUNCH(k_fr_op, dim3(nblk(n, 256)), dim3(256), 0, c->stream, op, (const u32*)a, op <= 2 ? (const u32*)b : (const u32*)nullptr, (u32*)out,
@@ -209,20 +213,15 @@ extern "C" int blsgpu_fr_op_device(blsgpu_ctx* c, int op, const void* a, const v
   return BLSGPU_OK;
 }
 extern "C" int blsgpu_fr_op(blsgpu_ctx* c, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, uint8_t* nonzero_flags) { CTX_CLAIM(c);
-  if (!c || (n && (!a || !out))) return bad("fr_op: NULL argument");
-  if (op < 0 || op > 6) return bad("fr_op: unknown op");
-  if (op <= 2 && n && !b) return bad("fr_op: binary op needs b");
+  if (int rc = fr_op_check(c, op, a, b, n, out)) return rc;
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_a.reserve(n * 32) || c->io_b.reserve(n * 32) || c->io_out.reserve(n * 32) || c->flags_a.reserve(n)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, a, n * 32, hipMemcpyHostToDevice, c->stream));
-  if (op <= 2) HIPCHK(hipMemcpyAsync(c->io_b.p, b, n * 32, hipMemcpyHostToDevice, c->stream));
-  int rc = blsgpu_fr_op_device(c, op, c->io_a.p, c->io_b.p, n, c->io_out.p, (op == 4 && nonzero_flags) ? c->flags_a.p : nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  if (op == 4 && nonzero_flags) HIPCHK(hipMemcpyAsync(nonzero_flags, c->flags_a.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  void* da = h.in(c->io_a, a, n * 32);
+  void* db = h.in(c->io_b, op <= 2 ? b : nullptr, n * 32);
+  void* o = h.out(c->io_out, out, n * 32);
+  void* f = (op == 4 && nonzero_flags) ? h.out(c->flags_a, nonzero_flags, n) : nullptr;
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_op_device(c, op, da, db, n, o, f));
 }
 // `Scalar::to_bytes` / `from_bytes` / `from_bytes_wide` over vectors (scalar.rs:284-296, :256-280, :300-331; k_fr_convert)
 static int fr_convert_device(blsgpu_ctx* c, int op, const void* in, size_t n, void* out, void* ok) {
@@ -236,16 +235,12 @@ static int fr_convert_device(blsgpu_ctx* c, int op, const void* in, size_t n, vo
 static int fr_convert_host(blsgpu_ctx* c, int op, const void* in, size_t n, void* out, uint8_t* ok) {
   if (!c || (n && (!in || !out))) return bad("fr conversion: NULL argument");
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  const size_t ib = n * (op == 2 ? 64 : 32);
-  if (c->io_a.reserve(ib) || c->io_out.reserve(n * 32) || c->flags_a.reserve(n)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  { int ru = staged_upload(c, c->io_a.p, in, ib); if (ru) return ru; }
-  int rc = fr_convert_device(c, op, c->io_a.p, n, c->io_out.p, ok ? c->flags_a.p : nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  if (ok) HIPCHK(hipMemcpyAsync(ok, c->flags_a.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  void* di = h.in(c->io_a, in, n * (op == 2 ? 64 : 32));
+  void* o = h.out(c->io_out, out, n * 32);
+  void* f = ok ? h.out(c->flags_a, ok, n) : nullptr;
+  if (h.rc) return h.rc;
+  return h.finish(fr_convert_device(c, op, di, n, o, f));
 }
 extern "C" int blsgpu_fr_to_bytes_device(blsgpu_ctx* c, const void* scalars, size_t n, void* bytes, void* ok) { CTX_CLAIM(c); return fr_convert_device(c, 0, scalars, n, bytes, ok); }
 extern "C" int blsgpu_fr_from_bytes_device(blsgpu_ctx* c, const void* bytes, size_t n, void* scalars, void* ok) { CTX_CLAIM(c); return fr_convert_device(c, 1, bytes, n, scalars, ok); }
@@ -254,9 +249,13 @@ extern "C" int blsgpu_fr_to_bytes(blsgpu_ctx* c, const uint64_t* scalars, size_t
 extern "C" int blsgpu_fr_from_bytes(blsgpu_ctx* c, const uint8_t* bytes, size_t n, uint64_t* scalars, uint8_t* ok) { CTX_CLAIM(c); return fr_convert_host(c, 1, bytes, n, scalars, ok); }
 extern "C" int blsgpu_fr_from_bytes_wide(blsgpu_ctx* c, const uint8_t* bytes, size_t n, uint64_t* scalars) { CTX_CLAIM(c); return fr_convert_host(c, 2, bytes, n, scalars, nullptr); }
 // in-place transform of 2^log_n scalars in device memory (natural order in and out)
-extern "C" int blsgpu_fr_ntt_device(blsgpu_ctx* c, void* d_data, int log_n, int inverse) { CTX_CLAIM(c);
-  if (!c || !d_data) return bad("fr_ntt: NULL argument");
+static int fr_ntt_check(blsgpu_ctx* c, const void* data, int log_n) {
+  if (!c || !data) return bad("fr_ntt: NULL argument");
   if (log_n < 0 || log_n > 28) return bad("fr_ntt: log_n must be in [0, 28]");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_ntt_device(blsgpu_ctx* c, void* d_data, int log_n, int inverse) { CTX_CLAIM(c);
+  if (int rc = fr_ntt_check(c, d_data, log_n)) return rc;
   if (log_n == 0) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
@@ -334,17 +333,11 @@ extern "C" int blsgpu_fr_ntt_device(blsgpu_ctx* c, void* d_data, int log_n, int 
   return BLSGPU_OK;
 }
 extern "C" int blsgpu_fr_ntt(blsgpu_ctx* c, uint64_t* data, int log_n, int inverse) { CTX_CLAIM(c);
-  if (!c || !data) return bad("fr_ntt: NULL argument");
-  if (log_n < 0 || log_n > 28) return bad("fr_ntt: log_n must be in [0, 28]");
-  HIPCHK(hipSetDevice(c->device));
-  const size_t n = (size_t)1 << log_n;
-  if (c->io_a.reserve(n * 32)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, data, n * 32, hipMemcpyHostToDevice, c->stream));
-  int rc = blsgpu_fr_ntt_device(c, c->io_a.p, log_n, inverse);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(data, c->io_a.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  if (int rc = fr_ntt_check(c, data, log_n)) return rc;
+  HostCall h(c);
+  void* d = h.inout(c->io_a, data, ((size_t)1 << log_n) * 32);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_ntt_device(c, d, log_n, inverse));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -373,32 +366,26 @@ template <class F>
 static int point_decode(blsgpu_ctx* c, const uint8_t* bytes, size_t n, int compressed, int checked, uint64_t* xy, uint8_t* inf, uint8_t* ok) {
   if (!c || (n && (!bytes || !xy || !inf || !ok))) return bad("decode: NULL argument");
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
+  HostCall h(c);
   constexpr int CB = Codec<F>::COORD_BYTES, WW = Wire<F>::WORDS;
-  size_t ib = n * (compressed ? CB : 2 * CB), xb = n * 2 * WW * 4;
-  if (c->io_a.reserve(ib) || c->io_out.reserve(xb) || c->flags_a.reserve(n) || c->flags_b.reserve(n)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, bytes, ib, hipMemcpyHostToDevice, c->stream));
-  if (int rc = point_decode_device<F>(c, c->io_a.p, n, compressed, checked, c->io_out.p, c->flags_a.p, c->flags_b.p)) return rc;
-  HIPCHK(hipMemcpyAsync(xy, c->io_out.p, xb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(inf, c->flags_a.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(ok, c->flags_b.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  void* b = h.in(c->io_a, bytes, n * (compressed ? CB : 2 * CB));
+  void* x = h.out(c->io_out, xy, n * 2 * WW * 4);
+  void* i = h.out(c->flags_a, inf, n);
+  void* o = h.out(c->flags_b, ok, n);
+  if (h.rc) return h.rc;
+  return h.finish(point_decode_device<F>(c, b, n, compressed, checked, x, i, o));
 }
 template <class F>
 static int point_encode(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, int compressed, uint8_t* out) {
   if (!c || (n && (!xy || !out))) return bad("encode: NULL argument");
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
+  HostCall h(c);
   constexpr int CB = Codec<F>::COORD_BYTES, WW = Wire<F>::WORDS;
-  size_t ob = n * (compressed ? CB : 2 * CB), xb = n * 2 * WW * 4;
-  if (c->io_a.reserve(xb) || c->io_out.reserve(ob) || c->flags_a.reserve(n)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, xy, xb, hipMemcpyHostToDevice, c->stream));
-  if (inf) HIPCHK(hipMemcpyAsync(c->flags_a.p, inf, n, hipMemcpyHostToDevice, c->stream));
-  if (int rc = point_encode_device<F>(c, c->io_a.p, inf ? c->flags_a.p : nullptr, n, compressed, c->io_out.p)) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, ob, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  void* x = h.in(c->io_a, xy, n * 2 * WW * 4);
+  void* i = h.in(c->flags_a, inf, n);
+  void* o = h.out(c->io_out, out, n * (compressed ? CB : 2 * CB));
+  if (h.rc) return h.rc;
+  return h.finish(point_encode_device<F>(c, x, i, n, compressed, o));
 }
 extern "C" int blsgpu_g1_from_bytes_batch_device(blsgpu_ctx* c, const void* b, size_t n, int compressed, int checked, void* xy, void* inf, void* ok) { CTX_CLAIM(c);
   return point_decode_device<FpPolicy>(c, b, n, compressed, checked, xy, inf, ok);
@@ -487,11 +474,17 @@ __global__ void __launch_bounds__(256) k_bls_verdict(const uint8_t* __restrict__
   if (i >= n) return;
   verdict[i] = !pk_ok[i] ? 2 : !sig_ok[i] ? 3 : is_one[i] ? 1 : 0;
 }
+// dst_max as for h2c_check
+static int verify_check(blsgpu_ctx* c, int mode, const void* pk, const void* sig, const void* offsets, size_t n, const void* dst, size_t dst_len, size_t dst_max,
+                        const void* verdict) {
+  if (!c || (n && (!pk || !sig || !offsets || !verdict)) || (dst_len && !dst)) return bad("bls_verify_batch: NULL argument");
+  if (mode != 0 && mode != 1) return bad("bls_verify_batch: mode must be 0 (public keys in G1) or 1 (public keys in G2)");
+  if (dst_len > dst_max) return bad("bls_verify_batch_device: reduce a DST longer than 255 bytes on the host first");
+  return BLSGPU_OK;
+}
 extern "C" int blsgpu_bls_verify_batch_device(blsgpu_ctx* c, int mode, const void* d_pk, const void* d_sig, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst,
                                               size_t dst_len, void* d_verdict) { CTX_CLAIM(c);
-  if (!c || (n && (!d_pk || !d_sig || !d_offsets || !d_verdict)) || (dst_len && !d_dst)) return bad("bls_verify_batch: NULL argument");
-  if (mode != 0 && mode != 1) return bad("bls_verify_batch: mode must be 0 (public keys in G1) or 1 (public keys in G2)");
-  if (dst_len > 255) return bad("bls_verify_batch_device: reduce a DST longer than 255 bytes on the host first");
+  if (int rc = verify_check(c, mode, d_pk, d_sig, d_offsets, n, d_dst, dst_len, 255, d_verdict)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   // G1-side and G2-side points of the equation: mode 0 = (pk, sig), mode 1 = (sig, pk); the hash goes to the signature's group
@@ -585,31 +578,15 @@ extern "C" int blsgpu_bls_verify_batch_device(blsgpu_ctx* c, int mode, const voi
 }
 extern "C" int blsgpu_bls_verify_batch(blsgpu_ctx* c, int mode, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst,
                                        size_t dst_len, uint8_t* verdict) { CTX_CLAIM(c);
-  if (!c || (n && (!pk || !sig || !offsets || !verdict)) || (dst_len && !dst)) return bad("bls_verify_batch: NULL argument");
-  if (mode != 0 && mode != 1) return bad("bls_verify_batch: mode must be 0 (public keys in G1) or 1 (public keys in G2)");
+  if (int rc = verify_check(c, mode, pk, sig, offsets, n, dst, dst_len, (size_t)-1, verdict)) return rc;
   if (!n) return BLSGPU_OK;
-  for (size_t i = 0; i < n; i++) if (offsets[i] > offsets[i + 1]) return bad("bls_verify_batch: offsets must be non-decreasing");
-  const size_t total = (size_t)offsets[n];
-  if (total && !msgs) return bad("bls_verify_batch: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  uint8_t d[255];
-  const u32 dlen = h2c_reduce_dst(EXPAND_XMD_SHA256, dst, dst_len, d);        // expand_msg.rs:74-95
-  const size_t pkb = n * (mode == 0 ? 48 : 96), sgb = n * (mode == 0 ? 96 : 48);
-  // ONE staging block: pk | sig | msgs | offsets | dst | verdict
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t o_pk = 0, o_sg = up(pkb), o_ms = o_sg + up(sgb), o_of = o_ms + up(total + 16), o_ds = o_of + up((n + 1) * 8), o_vd = o_ds + 256, bytes = o_vd + up(n);
-  if (c->io_a.reserve(bytes)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  uint8_t* b = c->io_a.as<uint8_t>();
-  HIPCHK(hipMemcpyAsync(b + o_pk, pk, pkb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(b + o_sg, sig, sgb, hipMemcpyHostToDevice, c->stream));
-  if (total) HIPCHK(hipMemcpyAsync(b + o_ms, msgs, total, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(b + o_of, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (dlen) HIPCHK(hipMemcpyAsync(b + o_ds, d, dlen, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));                 // `d` lives on this stack frame
-  int rc = blsgpu_bls_verify_batch_device(c, mode, b + o_pk, b + o_sg, b + o_ms, b + o_of, n, b + o_ds, dlen, b + o_vd);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(verdict, b + o_vd, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  void *m, *o, *d; u32 dlen;
+  if (int rc = stage_messages(h, "bls_verify_batch: offsets must be non-decreasing", "bls_verify_batch: NULL argument", EXPAND_XMD_SHA256, msgs, offsets, n, dst, dst_len,
+                              &m, &o, &d, &dlen)) return rc;
+  void* p = h.in(c->io_e, pk, n * (mode == 0 ? 48 : 96));
+  void* s = h.in(c->flags_b, sig, n * (mode == 0 ? 96 : 48));
+  void* v = h.out(c->flags_a, verdict, n);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_bls_verify_batch_device(c, mode, p, s, m, o, n, d, dlen, v));
 }
-

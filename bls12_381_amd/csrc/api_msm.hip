@@ -68,36 +68,31 @@ static int bases_import(blsgpu_ctx* c, const void* d_xy, const void* d_inf, size
   *out = b;
   return BLSGPU_OK;
 }
+static int bases_check(const char* msg, blsgpu_ctx* c, const void* xy, size_t n, blsgpu_bases** out) { return (!c || !out || (n && !xy)) ? bad(msg) : BLSGPU_OK; }
 template <class F>
 static int bases_upload(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, blsgpu_bases** out, bool oneshot = false) {
-  if (!c || !out || (n && !xy)) return bad("bases_upload: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  size_t xb = n * 2 * Wire<F>::WORDS * 4;
-  if (c->io_a.reserve(xb ? xb : 16) || c->flags_a.reserve(n ? n : 16)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (n) { int ru = staged_upload(c, c->io_a.p, xy, xb); if (ru) return ru; }
-  if (n && inf) HIPCHK(hipMemcpyAsync(c->flags_a.p, inf, n, hipMemcpyHostToDevice, c->stream));
-  int rc = bases_import<F>(c, c->io_a.p, inf ? c->flags_a.p : nullptr, n, out, oneshot);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  if (int rc = bases_check("bases_upload: NULL argument", c, xy, n, out)) return rc;
+  HostCall h(c);
+  void* dxy = h.in(c->io_a, xy, n * 2 * Wire<F>::WORDS * 4);
+  void* dinf = h.in(c->flags_a, inf, n);
+  if (h.rc) return h.rc;
+  return h.finish(bases_import<F>(c, dxy, dinf, n, out, oneshot));
 }
 extern "C" int blsgpu_g1_bases_upload(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, blsgpu_bases** out) { CTX_CLAIM(c); return bases_upload<FpPolicy>(c, xy, inf, n, out); }
 extern "C" int blsgpu_g2_bases_upload(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, blsgpu_bases** out) { CTX_CLAIM(c); return bases_upload<Fp2Policy>(c, xy, inf, n, out); }
 extern "C" int blsgpu_g1_bases_from_device(blsgpu_ctx* c, const void* xy, const void* inf, size_t n, blsgpu_bases** out) { CTX_CLAIM(c);
-  if (!c || !out || (n && !xy)) return bad("bases_from_device: NULL argument");
+  if (int rc = bases_check("bases_from_device: NULL argument", c, xy, n, out)) return rc;
   HIPCHK(hipSetDevice(c->device));
   return bases_import<FpPolicy>(c, xy, inf, n, out);
 }
 extern "C" int blsgpu_g2_bases_from_device(blsgpu_ctx* c, const void* xy, const void* inf, size_t n, blsgpu_bases** out) { CTX_CLAIM(c);
-  if (!c || !out || (n && !xy)) return bad("bases_from_device: NULL argument");
+  if (int rc = bases_check("bases_from_device: NULL argument", c, xy, n, out)) return rc;
   HIPCHK(hipSetDevice(c->device));
   return bases_import<Fp2Policy>(c, xy, inf, n, out);
 }
-extern "C" int blsgpu_bases_from_scalars(blsgpu_ctx* c, int group, const uint8_t* scalars, size_t n, blsgpu_bases** out) { CTX_CLAIM(c);
-  if (!c || !out || (n && !scalars) || (group != 1 && group != 2)) return bad("bases_from_scalars: bad argument");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_a.reserve(n ? n * 32 : 16)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (n) HIPCHK(hipMemcpyAsync(c->io_a.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
+// [k_i]G for n one-byte-per-limb scalars already on the device; the fixed-base table of the group is built first when this call needs it
+// (*fb_built: marked ready by the caller once the call has synchronised)
+static int bases_from_scalars_core(blsgpu_ctx* c, int group, const void* d_scalars, size_t n, blsgpu_bases** out, bool* fb_built) {
   blsgpu_bases* b = new blsgpu_bases();
   b->group = group; b->n = n; b->device = c->device;
   size_t words = group == 1 ? Store<FpPolicy>::AFF_WORDS : Store<Fp2Policy>::AFF_WORDS;
@@ -128,20 +123,29 @@ extern "C" int blsgpu_bases_from_scalars(blsgpu_ctx* c, int group, const uint8_t
     if (comb) {
       hipError_t e = hipStreamWaitEvent(c->stream, c->ev_fb[group - 1], 0);
       if (e != hipSuccess) { bases_drop(b); return fail("fixed-base table wait", e, __LINE__); }
-      if (group == 1) KLAUNCH(k_fixed_base<FpPolicy>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->io_a.as<u32>(), c->fb_table[0].as<u32>(), b->rec, n);
-      else KLAUNCH(k_fixed_base<Fp2Policy>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->io_a.as<u32>(), c->fb_table[1].as<u32>(), b->rec, n);
-    } else if (group == 1) KLAUNCH(k_bases_from_scalars<FpPolicy>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->io_a.as<u32>(), b->rec, n);
-    else KLAUNCH(k_bases_from_scalars<Fp2Policy>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->io_a.as<u32>(), b->rec, n);
+      if (group == 1) KLAUNCH(k_fixed_base<FpPolicy>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (const u32*)d_scalars, c->fb_table[0].as<u32>(), b->rec, n);
+      else KLAUNCH(k_fixed_base<Fp2Policy>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (const u32*)d_scalars, c->fb_table[1].as<u32>(), b->rec, n);
+    } else if (group == 1) KLAUNCH(k_bases_from_scalars<FpPolicy>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (const u32*)d_scalars, b->rec, n);
+    else KLAUNCH(k_bases_from_scalars<Fp2Policy>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (const u32*)d_scalars, b->rec, n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(b->ev_ready, c->stream);
     if (e != hipSuccess) { bases_drop(b); return fail("k_bases_from_scalars", e, __LINE__); }
   }
   if (int rc = bases_make_endo(c, b, true)) { bases_drop(b); return rc; }      // [k]G lies in the subgroup by construction
-  {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { bases_drop(b); return fail("bases_from_scalars", e, __LINE__); }     // (a table built in this call stays unmarked: rebuilt next time)
-  }
-  if (fb_built_now) c->fb_ready[group - 1] = true;
+  *fb_built = fb_built_now;
+  *out = b;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_bases_from_scalars(blsgpu_ctx* c, int group, const uint8_t* scalars, size_t n, blsgpu_bases** out) { CTX_CLAIM(c);
+  if (!c || !out || (n && !scalars) || (group != 1 && group != 2)) return bad("bases_from_scalars: bad argument");
+  HostCall h(c);
+  void* ds = h.in(c->io_a, scalars, n * 32);
+  if (h.rc) return h.rc;
+  blsgpu_bases* b = nullptr;
+  bool fb_built = false;
+  int rc = h.finish(bases_from_scalars_core(c, group, ds, n, &b, &fb_built));
+  if (rc) { if (b) bases_drop(b); return rc; }        // (a table built in this call stays unmarked: rebuilt next time)
+  if (fb_built) c->fb_ready[group - 1] = true;
   *out = b;
   return BLSGPU_OK;
 }
@@ -178,23 +182,20 @@ extern "C" int blsgpu_bases_precompute(blsgpu_ctx* c, blsgpu_bases* b, int windo
 }
 
 template <class F>
-static int bases_download(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, size_t count, uint64_t* xy, uint8_t* inf) {
-  size_t xb = count * 2 * Wire<F>::WORDS * 4;
-  if (c->io_out.reserve(xb ? xb : 16) || c->flags_b.reserve(count ? count : 16)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (!count) return BLSGPU_OK;
-  KLAUNCH(k_bases_export<F>, dim3(nblk(count, 256)), dim3(256), 0, c->stream, b->rec + first * Store<F>::AFF_WORDS, c->io_out.as<u32>(),
-                     c->flags_b.as<uint8_t>(), count);
+static int bases_export(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, size_t count, void* d_xy, void* d_inf) {
+  KLAUNCH(k_bases_export<F>, dim3(nblk(count, 256)), dim3(256), 0, c->stream, b->rec + first * Store<F>::AFF_WORDS, (u32*)d_xy, (uint8_t*)d_inf, count);
   LAUNCHCHK();
-  HIPCHK(hipMemcpyAsync(xy, c->io_out.p, xb, hipMemcpyDeviceToHost, c->stream));
-  if (inf) HIPCHK(hipMemcpyAsync(inf, c->flags_b.p, count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
   return BLSGPU_OK;
 }
 extern "C" int blsgpu_bases_download(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, size_t count, uint64_t* xy, uint8_t* inf) { CTX_CLAIM(c);
   if (!c || !b || (count && !xy) || first > b->n || count > b->n - first) return bad("bases_download: bad argument");
   if (b->device != c->device) return bad("bases_download: bases live on another device than the context");
-  HIPCHK(hipSetDevice(c->device));
-  return b->group == 1 ? bases_download<FpPolicy>(c, b, first, count, xy, inf) : bases_download<Fp2Policy>(c, b, first, count, xy, inf);
+  if (!count) return BLSGPU_OK;
+  HostCall h(c);
+  void* dxy = h.out(c->io_out, xy, count * 2 * (b->group == 1 ? Wire<FpPolicy>::WORDS : Wire<Fp2Policy>::WORDS) * 4);
+  void* dinf = h.out(c->flags_b, inf, count);
+  if (h.rc) return h.rc;
+  return h.finish(b->group == 1 ? bases_export<FpPolicy>(c, b, first, count, dxy, dinf) : bases_export<Fp2Policy>(c, b, first, count, dxy, dinf));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -216,12 +217,17 @@ constexpr size_t TEAM_LANES_MAX = 131072;
 #define TEAM_LDS(threads) ((size_t)team_lds_words<F>(threads) * 4)
 
 template <class F>
-static int msm_device(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, const void* d_scalars, size_t n, void* d_out_wire) {
-  if (!c || !bases || !d_out_wire || (n && !d_scalars)) return bad("msm: NULL argument");
+static int msm_check(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, const void* scalars, size_t n, const void* out) {
+  if (!c || !bases || !out || (n && !scalars)) return bad("msm: NULL argument");
   if (bases->group != GroupTag<F>::id) return bad("msm: bases belong to the other group");
   if (first > bases->n || n > bases->n - first) return bad("msm: range exceeds the resident bases");
   if (bases->device != c->device) return bad("msm: bases live on another device than the context");
   if (n > ((size_t)1 << 27)) return bad("msm: n too large for one call (shard the input)");
+  return BLSGPU_OK;
+}
+template <class F>
+static int msm_device(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, const void* d_scalars, size_t n, void* d_out_wire) {
+  if (int rc = msm_check<F>(c, bases, first, d_scalars, n, d_out_wire)) return rc;
   HIPCHK(hipSetDevice(c->device));
   // Calls beyond the sort's index width with the endomorphism split (G1: 2 n > 2^24, G2: 4 n > 2^24) run on plain windows.
   // Cutting them into passes that each keep the split was measured (round 3, 2^24 G1 points on one MI355X: two GLV passes
@@ -560,22 +566,14 @@ static int msm_device(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, co
 
 template <class F>
 static int msm_host(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, const uint8_t* scalars, size_t n, uint64_t* out) {
-  if (!c || !out || (n && !scalars)) return bad("msm: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_b.reserve(n ? n * 32 : 16) || c->io_out.reserve(3 * Wire<F>::WORDS * 4)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  SyncStatus ss(c);
-  int rc = ss.begin();
-  if (rc) return rc;
-  if (n) { int ru = staged_upload(c, c->io_b.p, scalars, n * 32); if (ru) return ru; }
-  rc = msm_device<F>(c, bases, first, c->io_b.p, n, c->io_out.p);
-  if (rc) return rc;
-  rc = blsgpu_join(c);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, 3 * Wire<F>::WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-  rc = ss.fetch();
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return ss.verdict();
+  if (int rc = msm_check<F>(c, bases, first, scalars, n, out)) return rc;
+  HostCall h(c);
+  h.report_status();
+  void* s = h.in(c->io_b, scalars, n * 32);
+  void* o = h.out(c->io_out, out, 3 * Wire<F>::WORDS * 4);
+  if (h.rc) return h.rc;
+  int rc = msm_device<F>(c, bases, first, s, n, o);
+  return h.finish(rc ? rc : blsgpu_join(c));
 }
 extern "C" int blsgpu_g1_msm(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, const uint8_t* s, size_t n, uint64_t* out) { CTX_CLAIM(c); return msm_host<FpPolicy>(c, b, first, s, n, out); }
 extern "C" int blsgpu_g2_msm(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, const uint8_t* s, size_t n, uint64_t* out) { CTX_CLAIM(c); return msm_host<Fp2Policy>(c, b, first, s, n, out); }
@@ -595,8 +593,13 @@ extern "C" int blsgpu_g2_msm_mont_device(blsgpu_ctx* c, const blsgpu_bases* b, s
 // d_scalars + j * n * 32, result j at d_out + j * 3 * WORDS * 4.  The calls go through the pipeline slots, so the sort,
 // accumulation and tail of consecutive MSMs overlap; results are ordered on the context's stream on return.
 template <class F>
+static int msm_many_check(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, const void* scalars, size_t n, size_t k, const void* out) {
+  if (!c || !bases || (k && (!out || (n && !scalars)))) return bad("msm_many: NULL argument");
+  return k ? msm_check<F>(c, bases, first, scalars, n, out) : BLSGPU_OK;
+}
+template <class F>
 static int msm_many_device(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, const void* d_scalars, size_t n, size_t k, void* d_out) {
-  if (!c || !bases || (k && (!d_out || (n && !d_scalars)))) return bad("msm_many: NULL argument");
+  if (int rc = msm_many_check<F>(c, bases, first, d_scalars, n, k, d_out)) return rc;
   const bool was = c->pipelining;
   c->pipelining = true;
   int rc = BLSGPU_OK;
@@ -610,22 +613,14 @@ extern "C" int blsgpu_g1_msm_many_device(blsgpu_ctx* c, const blsgpu_bases* b, s
 extern "C" int blsgpu_g2_msm_many_device(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, const void* s, size_t n, size_t k, void* out) { CTX_CLAIM(c); return msm_many_device<Fp2Policy>(c, b, first, s, n, k, out); }
 template <class F>
 static int msm_many_host(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, const uint8_t* scalars, size_t n, size_t k, uint64_t* out) {
-  if (!c || (k && (!out || (n && !scalars)))) return bad("msm_many: NULL argument");
+  if (int rc = msm_many_check<F>(c, bases, first, scalars, n, k, out)) return rc;
   if (!k) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  const size_t ob = 3 * Wire<F>::WORDS * 4;
-  if (c->io_b.reserve(n * k ? n * k * 32 : 16) || c->io_out.reserve(k * ob)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  SyncStatus ss(c);
-  int rc = ss.begin();
-  if (rc) return rc;
-  if (n) { int ru = staged_upload(c, c->io_b.p, scalars, n * k * 32); if (ru) return ru; }
-  rc = msm_many_device<F>(c, bases, first, c->io_b.p, n, k, c->io_out.p);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, k * ob, hipMemcpyDeviceToHost, c->stream));
-  rc = ss.fetch();
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return ss.verdict();
+  HostCall h(c);
+  h.report_status();
+  void* s = h.in(c->io_b, scalars, n * k * 32);
+  void* o = h.out(c->io_out, out, k * 3 * Wire<F>::WORDS * 4);
+  if (h.rc) return h.rc;
+  return h.finish(msm_many_device<F>(c, bases, first, s, n, k, o));
 }
 extern "C" int blsgpu_g1_msm_many(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, const uint8_t* s, size_t n, size_t k, uint64_t* out) { CTX_CLAIM(c); return msm_many_host<FpPolicy>(c, b, first, s, n, k, out); }
 extern "C" int blsgpu_g2_msm_many(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, const uint8_t* s, size_t n, size_t k, uint64_t* out) { CTX_CLAIM(c); return msm_many_host<Fp2Policy>(c, b, first, s, n, k, out); }
@@ -715,9 +710,10 @@ extern "C" int blsgpu_g2_msm_host(blsgpu_ctx* c, const uint64_t* xy, const uint8
 // ---------------------------------------------------------------------------------------------------
 // batched variable-base scalar multiplication (mulbatch.hip.h): out[i] = [s_i] P_i, N in -> N out
 // ---------------------------------------------------------------------------------------------------
+static int mul_batch_check(blsgpu_ctx* c, const void* xy, const void* scalars, size_t n, const void* out) { return (!c || (n && (!xy || !scalars || !out))) ? bad("mul_batch: NULL argument") : BLSGPU_OK; }
 template <class F>
 static int mul_batch_device(blsgpu_ctx* c, const void* d_xy, const void* d_inf, const void* d_scalars, size_t n, void* d_out) {
-  if (!c || (n && (!d_xy || !d_scalars || !d_out))) return bad("mul_batch: NULL argument");
+  if (int rc = mul_batch_check(c, d_xy, d_scalars, n, d_out)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   if constexpr (MbIO<F>::LANES == 1) {
@@ -742,23 +738,17 @@ static int mul_batch_device(blsgpu_ctx* c, const void* d_xy, const void* d_inf, 
 }
 template <class F>
 static int mul_batch_host(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, const uint8_t* scalars, size_t n, uint64_t* out) {
-  if (!c || (n && (!xy || !scalars || !out))) return bad("mul_batch: NULL argument");
+  if (int rc = mul_batch_check(c, xy, scalars, n, out)) return rc;
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
   constexpr size_t WB = MbIO<F>::WW * 4;
-  if (c->io_a.reserve(n * 2 * WB) || c->io_b.reserve(n * 32) || c->flags_a.reserve(n) || c->io_out.reserve(n * 3 * WB)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  SyncStatus ss(c);
-  int rc = ss.begin();
-  if (rc) return rc;
-  { int ru = staged_upload(c, c->io_a.p, xy, n * 2 * WB); if (!ru) ru = staged_upload(c, c->io_b.p, scalars, n * 32); if (ru) return ru; }
-  if (inf) HIPCHK(hipMemcpyAsync(c->flags_a.p, inf, n, hipMemcpyHostToDevice, c->stream));
-  rc = mul_batch_device<F>(c, c->io_a.p, inf ? c->flags_a.p : nullptr, c->io_b.p, n, c->io_out.p);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * 3 * WB, hipMemcpyDeviceToHost, c->stream));
-  rc = ss.fetch();
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return ss.verdict();
+  HostCall h(c);
+  h.report_status();
+  void* dxy = h.in(c->io_a, xy, n * 2 * WB);
+  void* ds = h.in(c->io_b, scalars, n * 32);
+  void* dinf = h.in(c->flags_a, inf, n);
+  void* o = h.out(c->io_out, out, n * 3 * WB);
+  if (h.rc) return h.rc;
+  return h.finish(mul_batch_device<F>(c, dxy, dinf, ds, n, o));
 }
 extern "C" int blsgpu_g1_mul_batch(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, const uint8_t* s, size_t n, uint64_t* out) { CTX_CLAIM(c); return mul_batch_host<FpPolicy>(c, xy, inf, s, n, out); }
 extern "C" int blsgpu_g2_mul_batch(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, const uint8_t* s, size_t n, uint64_t* out) { CTX_CLAIM(c); return mul_batch_host<Fp2PairPolicy>(c, xy, inf, s, n, out); }
@@ -777,40 +767,32 @@ extern "C" int blsgpu_g2_mul_batch_mont_device(blsgpu_ctx* c, const void* xy, co
 // ---------------------------------------------------------------------------------------------------
 // group helpers
 // ---------------------------------------------------------------------------------------------------
-template <class F>
-static int proj_sum(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint64_t* out) {
-  if (!c || !out || (n && !xyz)) return bad("sum: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  constexpr int WW = Wire<F>::WORDS, PW = Store<F>::PROJ_WORDS;
-  if (c->io_a.reserve(n ? n * 3 * WW * 4 : 16) || c->io_c.reserve((n ? n : 1) * PW * 4) || c->result.reserve(PW * 4) || c->io_out.reserve(3 * WW * 4)) {
-    g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP;
-  }
-  if (n) {
-    HIPCHK(hipMemcpyAsync(c->io_a.p, xyz, n * 3 * WW * 4, hipMemcpyHostToDevice, c->stream));
-    KLAUNCH(k_proj_import<F>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->io_a.as<u32>(), c->io_c.as<u32>(), n);
-  }
-  KLAUNCH(k_proj_sum_team<F>, dim3(1), dim3(TEAM), TEAM_LDS(TEAM), c->stream, c->io_c.as<u32>(), c->result.as<u32>(), n);
-  KLAUNCH(k_proj_export<F>, dim3(1), dim3(256), 0, c->stream, c->result.as<u32>(), c->io_out.as<u32>(), (size_t)1);
-  LAUNCHCHK();
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, 3 * WW * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
-}
 // device-pointer variant: wire-format partials in device memory -> wire-format sum in device memory, asynchronous
+static int sum_check(const char* msg, blsgpu_ctx* c, const void* xyz, size_t n, const void* out) { return (!c || !out || (n && !xyz)) ? bad(msg) : BLSGPU_OK; }
 template <class F>
 static int proj_sum_device(blsgpu_ctx* c, const void* d_xyz, size_t n, void* d_out) {
-  if (!c || !d_out || (n && !d_xyz)) return bad("sum_device: NULL argument");
+  if (int rc = sum_check("sum_device: NULL argument", c, d_xyz, n, d_out)) return rc;
   HIPCHK(hipSetDevice(c->device));
   constexpr int PW = Store<F>::PROJ_WORDS;
   // (a fold queued on the fold stream must not share scratch with calls on the main stream: nothing orders the two)
   DevBuf& recs = c->on_fold_stream ? c->fold_c : c->io_c;
   DevBuf& res = c->on_fold_stream ? c->fold_result : c->result;
-  if (recs.reserve((n ? n : 1) * PW * 4) || res.reserve(PW * 4)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
+  if (recs.reserve((n ? n : 1) * PW * 4) || res.reserve(PW * 4)) { g_err = "hipMalloc failed"; return BLSGPU_ERR_HIP; }
   if (n) KLAUNCH(k_proj_import<F>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (const u32*)d_xyz, recs.as<u32>(), n);
   KLAUNCH(k_proj_sum_team<F>, dim3(1), dim3(TEAM), TEAM_LDS(TEAM), c->stream, recs.as<u32>(), res.as<u32>(), n);
   KLAUNCH(k_proj_export<F>, dim3(1), dim3(256), 0, c->stream, res.as<u32>(), (u32*)d_out, (size_t)1);
   LAUNCHCHK();
   return BLSGPU_OK;
+}
+template <class F>
+static int proj_sum(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint64_t* out) {
+  if (int rc = sum_check("sum: NULL argument", c, xyz, n, out)) return rc;
+  constexpr int WW = Wire<F>::WORDS;
+  HostCall h(c);
+  void* dxyz = h.in(c->io_a, xyz, n * 3 * WW * 4);
+  void* o = h.out(c->io_out, out, 3 * WW * 4);
+  if (h.rc) return h.rc;
+  return h.finish(proj_sum_device<F>(c, dxyz, n, o));
 }
 extern "C" int blsgpu_g1_sum_device(blsgpu_ctx* c, const void* xyz, size_t n, void* out) { CTX_CLAIM(c); return proj_sum_device<FpPolicy>(c, xyz, n, out); }
 extern "C" int blsgpu_g2_sum_device(blsgpu_ctx* c, const void* xyz, size_t n, void* out) { CTX_CLAIM(c); return proj_sum_device<Fp2Policy>(c, xyz, n, out); }
@@ -818,13 +800,15 @@ extern "C" int blsgpu_g1_sum(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint6
 extern "C" int blsgpu_g2_sum(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint64_t* out) { CTX_CLAIM(c); return proj_sum<Fp2Policy>(c, xyz, n, out); }
 
 // device core: projective wire records in device memory -> affine wire coordinates + infinity bytes in device memory (asynchronous)
+// (the host forms take no infinity array when the caller does not want one: inf_ok = true)
+static int normalize_check(blsgpu_ctx* c, const void* xyz, size_t n, const void* xy, bool inf_ok) { return (!c || (n && (!xyz || !xy || !inf_ok))) ? bad("batch_normalize: NULL argument") : BLSGPU_OK; }
 template <class F>
 static int batch_normalize_device(blsgpu_ctx* c, const void* d_xyz, size_t n, void* d_xy, void* d_inf) {
-  if (!c || (n && (!d_xyz || !d_xy || !d_inf))) return bad("batch_normalize: NULL argument");
+  if (int rc = normalize_check(c, d_xyz, n, d_xy, d_inf != nullptr)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   constexpr int PW = Store<F>::PROJ_WORDS;
-  if (c->io_c.reserve(n * PW * 4) || c->io_d.reserve(n * Store<F>::EL * 4)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
+  if (c->io_c.reserve(n * PW * 4) || c->io_d.reserve(n * Store<F>::EL * 4)) { g_err = "hipMalloc failed"; return BLSGPU_ERR_HIP; }
   KLAUNCH(k_proj_import<F>, dim3(nblk(n, 256)), dim3(256), 0, c->stream, (const u32*)d_xyz, c->io_c.as<u32>(), n);
   if (n >= 4096) {
     const int K = normalize_k(n);
@@ -838,17 +822,15 @@ static int batch_normalize_device(blsgpu_ctx* c, const void* d_xyz, size_t n, vo
 }
 template <class F>
 static int batch_normalize(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint64_t* xy, uint8_t* inf) {
-  if (!c || (n && (!xyz || !xy))) return bad("batch_normalize: NULL argument");
+  if (int rc = normalize_check(c, xyz, n, xy, true)) return rc;
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
   constexpr int WW = Wire<F>::WORDS;
-  if (c->io_a.reserve(n * 3 * WW * 4) || c->io_out.reserve(n * 2 * WW * 4) || c->flags_b.reserve(n)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, xyz, n * 3 * WW * 4, hipMemcpyHostToDevice, c->stream));
-  if (int rc = batch_normalize_device<F>(c, c->io_a.p, n, c->io_out.p, c->flags_b.p)) return rc;
-  HIPCHK(hipMemcpyAsync(xy, c->io_out.p, n * 2 * WW * 4, hipMemcpyDeviceToHost, c->stream));
-  if (inf) HIPCHK(hipMemcpyAsync(inf, c->flags_b.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  void* dxyz = h.in(c->io_a, xyz, n * 3 * WW * 4);
+  void* dxy = h.out(c->io_out, xy, n * 2 * WW * 4);
+  void* dinf = h.out(c->flags_b, inf, n);
+  if (h.rc) return h.rc;
+  return h.finish(batch_normalize_device<F>(c, dxyz, n, dxy, dinf));
 }
 extern "C" int blsgpu_g1_batch_normalize_device(blsgpu_ctx* c, const void* xyz, size_t n, void* xy, void* inf) { CTX_CLAIM(c); return batch_normalize_device<FpPolicy>(c, xyz, n, xy, inf); }
 extern "C" int blsgpu_g2_batch_normalize_device(blsgpu_ctx* c, const void* xyz, size_t n, void* xy, void* inf) { CTX_CLAIM(c); return batch_normalize_device<Fp2Policy>(c, xyz, n, xy, inf); }

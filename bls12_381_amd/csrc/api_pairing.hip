@@ -106,46 +106,38 @@ static int pairing_launch(blsgpu_ctx* c, int mode, const void* g1, const void* g
   LAUNCHCHK();
   return BLSGPU_OK;
 }
-static int pairing_host(blsgpu_ctx* c, int mode, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, size_t n, uint64_t* out) {
-  if (!c || (n && (!g1 || !g2 || !out))) return bad("pairing: NULL argument");
-  if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_a.reserve(n * 96) || c->io_b.reserve(n * 192) || c->flags_a.reserve(n) || c->flags_b.reserve(n) || c->io_out.reserve(n * 576)) {
-    g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP;
-  }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, g1, n * 96, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->io_b.p, g2, n * 192, hipMemcpyHostToDevice, c->stream));
-  if (g1inf) HIPCHK(hipMemcpyAsync(c->flags_a.p, g1inf, n, hipMemcpyHostToDevice, c->stream));
-  if (g2inf) HIPCHK(hipMemcpyAsync(c->flags_b.p, g2inf, n, hipMemcpyHostToDevice, c->stream));
-  int rc = pairing_launch(c, mode, c->io_a.p, g1inf ? c->flags_a.p : nullptr, c->io_b.p, g2inf ? c->flags_b.p : nullptr, n, c->io_out.p);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * 576, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+// the G1 / G2 terms of a host call and their infinity flags -> io_a / io_b / flags_a / flags_b (a NULL array stays NULL on the device)
+struct Terms { void *g1, *g1inf, *g2, *g2inf; };
+static Terms stage_terms(HostCall& h, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, size_t n) {
+  blsgpu_ctx* c = h.c;
+  return {h.in(c->io_a, g1, n * 96), h.in(c->flags_a, g1inf, n), h.in(c->io_b, g2, n * 192), h.in(c->flags_b, g2 ? g2inf : nullptr, n)};
 }
-extern "C" int blsgpu_pairing_batch(blsgpu_ctx* c, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, size_t n, uint64_t* out) { CTX_CLAIM(c);
-  return pairing_host(c, 0, g1, g1inf, g2, g2inf, n, out);
-}
-extern "C" int blsgpu_miller_loop_batch(blsgpu_ctx* c, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, size_t n, uint64_t* out) { CTX_CLAIM(c);
-  return pairing_host(c, 1, g1, g1inf, g2, g2inf, n, out);
-}
+static int pairing_check(const char* msg, blsgpu_ctx* c, const void* g1, const void* g2, size_t n, const void* out) { return (!c || (n && (!g1 || !g2 || !out))) ? bad(msg) : BLSGPU_OK; }
 extern "C" int blsgpu_pairing_batch_device(blsgpu_ctx* c, const void* g1, const void* g1inf, const void* g2, const void* g2inf, size_t n, void* out) { CTX_CLAIM(c);
-  if (!c || (n && (!g1 || !g2 || !out))) return bad("pairing: NULL argument");
+  if (int rc = pairing_check("pairing: NULL argument", c, g1, g2, n, out)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   return pairing_launch(c, 0, g1, g1inf, g2, g2inf, n, out);
 }
-
 extern "C" int blsgpu_miller_loop_batch_device(blsgpu_ctx* c, const void* g1, const void* g1inf, const void* g2, const void* g2inf, size_t n, void* out) { CTX_CLAIM(c);
-  if (!c || (n && (!g1 || !g2 || !out))) return bad("miller_loop: NULL argument");
+  if (int rc = pairing_check("miller_loop: NULL argument", c, g1, g2, n, out)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   return pairing_launch(c, 1, g1, g1inf, g2, g2inf, n, out);
 }
-extern "C" int blsgpu_final_exponentiation_device(blsgpu_ctx* c, const void* in, size_t n, void* out) { CTX_CLAIM(c);
-  if (!c || (n && (!in || !out))) return bad("final_exponentiation: NULL argument");
+// mode 0: full pairing, 1: Miller loop only
+static int pairing_host(blsgpu_ctx* c, int mode, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, size_t n, uint64_t* out) {
+  if (int rc = pairing_check("pairing: NULL argument", c, g1, g2, n, out)) return rc;
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
+  HostCall h(c);
+  const Terms t = stage_terms(h, g1, g1inf, g2, g2inf, n);
+  void* o = h.out(c->io_out, out, n * 576);
+  if (h.rc) return h.rc;
+  return h.finish(mode == 0 ? blsgpu_pairing_batch_device(c, t.g1, t.g1inf, t.g2, t.g2inf, n, o) : blsgpu_miller_loop_batch_device(c, t.g1, t.g1inf, t.g2, t.g2inf, n, o));
+}
+extern "C" int blsgpu_pairing_batch(blsgpu_ctx* c, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, size_t n, uint64_t* out) { CTX_CLAIM(c); return pairing_host(c, 0, g1, g1inf, g2, g2inf, n, out); }
+extern "C" int blsgpu_miller_loop_batch(blsgpu_ctx* c, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, size_t n, uint64_t* out) { CTX_CLAIM(c); return pairing_host(c, 1, g1, g1inf, g2, g2inf, n, out); }
+static int final_exp_launch(blsgpu_ctx* c, const void* in, size_t n, void* out) {
   const int layout = pairing_layout_for(c, n);
   if (layout < 0) return wide_missing(c);
   if (layout == 256) wide_launch(c, 2, in, nullptr, nullptr, nullptr, n, out);
@@ -153,6 +145,22 @@ extern "C" int blsgpu_final_exponentiation_device(blsgpu_ctx* c, const void* in,
   else KLAUNCH(k_final_exp, dim3(nblk(n * PL, PAIRING_BLOCK)), dim3(PAIRING_BLOCK), 0, c->stream, (const u32*)in, (u32*)out, n);
   LAUNCHCHK();
   return BLSGPU_OK;
+}
+static int final_exp_check(blsgpu_ctx* c, const void* in, size_t n, const void* out) { return (!c || (n && (!in || !out))) ? bad("final_exponentiation: NULL argument") : BLSGPU_OK; }
+extern "C" int blsgpu_final_exponentiation_device(blsgpu_ctx* c, const void* in, size_t n, void* out) { CTX_CLAIM(c);
+  if (int rc = final_exp_check(c, in, n, out)) return rc;
+  if (!n) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  return final_exp_launch(c, in, n, out);
+}
+extern "C" int blsgpu_final_exponentiation_batch(blsgpu_ctx* c, const uint64_t* in, size_t n, uint64_t* out) { CTX_CLAIM(c);
+  if (int rc = final_exp_check(c, in, n, out)) return rc;
+  if (!n) return BLSGPU_OK;
+  HostCall h(c);
+  void* i = h.in(c->io_a, in, n * 576);
+  void* o = h.out(c->io_out, out, n * 576);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_final_exponentiation_device(c, i, n, o));
 }
 
 // product of n Fp12 wire values already in device memory (d_in) -> one wire value (d_out); tree of k_fp12_prod
@@ -184,8 +192,9 @@ static int fp12_product_device(blsgpu_ctx* c, const u32* d_in, size_t n, u32* d_
   if (in != d_out) HIPCHK(hipMemcpyAsync(d_out, in, 576, hipMemcpyDeviceToDevice, c->stream));
   return BLSGPU_OK;
 }
+static int fp12_product_check(blsgpu_ctx* c, const void* in, size_t n, const void* out) { return (!c || !out || (n && !in)) ? bad("fp12_product: NULL argument") : BLSGPU_OK; }
 extern "C" int blsgpu_fp12_product_device(blsgpu_ctx* c, const void* in, size_t n, void* out) { CTX_CLAIM(c);
-  if (!c || !out || (n && !in)) return bad("fp12_product: NULL argument");
+  if (int rc = fp12_product_check(c, in, n, out)) return rc;
   HIPCHK(hipSetDevice(c->device));
   return fp12_product_device(c, (const u32*)in, n, (u32*)out);
 }
@@ -193,65 +202,55 @@ extern "C" int blsgpu_fp12_product_device(blsgpu_ctx* c, const void* in, size_t 
 constexpr int MML_IMPL_DEFAULT = 1;
 static int mmlp_launch(blsgpu_ctx* c, const void* g1, const void* g1inf, const void* g2, const void* g2inf, const void* qidx, const blsgpu_g2_prepared* p, const void* d_off,
                        size_t nseg, size_t total, int kuni, int kmax, void* out);
+static int mml_check(blsgpu_ctx* c, const void* g1, const void* g2, size_t n, const void* out) { return (!c || !out || (n && (!g1 || !g2))) ? bad("multi_miller_loop: NULL argument") : BLSGPU_OK; }
 extern "C" int blsgpu_multi_miller_loop_device(blsgpu_ctx* c, const void* g1, const void* g1inf, const void* g2, const void* g2inf, size_t n, void* out) { CTX_CLAIM(c);
-  if (!c || !out || (n && (!g1 || !g2))) return bad("multi_miller_loop: NULL argument");
+  if (int rc = mml_check(c, g1, g2, n, out)) return rc;
   HIPCHK(hipSetDevice(c->device));
-  if (c->io_out.reserve((n ? n : 1) * 576)) { g_err = "hipMalloc failed"; return BLSGPU_ERR_HIP; }
+  if (c->mml_vals.reserve((n ? n : 1) * 576)) { g_err = "hipMalloc failed"; return BLSGPU_ERR_HIP; }
   // terms per accumulator: as many as still leave two wavefronts per SIMD (2^17 lanes) busy
   int K = 1;
   while (K < MML_MAX_K && n / (2 * (size_t)K) >= 65536) K *= 2;
   if (K == 1) {
-    if (n) { int rc = pairing_launch(c, 1, g1, g1inf, g2, g2inf, n, c->io_out.p); if (rc) return rc; }
-    return fp12_product_device(c, c->io_out.as<u32>(), n, (u32*)out);
+    if (n) { int rc = pairing_launch(c, 1, g1, g1inf, g2, g2inf, n, c->mml_vals.p); if (rc) return rc; }
+    return fp12_product_device(c, c->mml_vals.as<u32>(), n, (u32*)out);
   }
   if (c->mmlp_k > 0) K = c->mmlp_k;
   const size_t groups = (n + K - 1) / K;
   const int impl = c->mml_impl ? c->mml_impl : MML_IMPL_DEFAULT;
   if (impl == 1) {
     KLAUNCH(k_multi_miller_shared, dim3(nblk(groups * PL, PAIRING_BLOCK)), dim3(PAIRING_BLOCK), 0, c->stream, (const u32*)g1, (const uint8_t*)g1inf,
-                       (const u32*)g2, (const uint8_t*)g2inf, c->io_out.as<u32>(), n, K);
+                       (const u32*)g2, (const uint8_t*)g2inf, c->mml_vals.as<u32>(), n, K);
     LAUNCHCHK();
   } else {
-    int rc = mmlp_launch(c, g1, g1inf, g2, g2inf, nullptr, nullptr, nullptr, groups, n, K, K, c->io_out.p);
+    int rc = mmlp_launch(c, g1, g1inf, g2, g2inf, nullptr, nullptr, nullptr, groups, n, K, K, c->mml_vals.p);
     if (rc) return rc;
   }
-  return fp12_product_device(c, c->io_out.as<u32>(), groups, (u32*)out);
+  return fp12_product_device(c, c->mml_vals.as<u32>(), groups, (u32*)out);
 }
 extern "C" int blsgpu_multi_miller_loop(blsgpu_ctx* c, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, size_t n, uint64_t* out) { CTX_CLAIM(c);
-  if (!c || !out || (n && (!g1 || !g2))) return bad("multi_miller_loop: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_a.reserve(n ? n * 96 : 16) || c->io_b.reserve(n ? n * 192 : 16) || c->flags_a.reserve(n ? n : 16) || c->flags_b.reserve(n ? n : 16) || c->result.reserve(576)) {
-    g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP;
-  }
-  if (n) {
-    HIPCHK(hipMemcpyAsync(c->io_a.p, g1, n * 96, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->io_b.p, g2, n * 192, hipMemcpyHostToDevice, c->stream));
-    if (g1inf) HIPCHK(hipMemcpyAsync(c->flags_a.p, g1inf, n, hipMemcpyHostToDevice, c->stream));
-    if (g2inf) HIPCHK(hipMemcpyAsync(c->flags_b.p, g2inf, n, hipMemcpyHostToDevice, c->stream));
-  }
-  int rc = blsgpu_multi_miller_loop_device(c, c->io_a.p, g1inf ? c->flags_a.p : nullptr, c->io_b.p, g2inf ? c->flags_b.p : nullptr, n, c->result.p);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->result.p, 576, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  if (int rc = mml_check(c, g1, g2, n, out)) return rc;
+  HostCall h(c);
+  const Terms t = stage_terms(h, g1, g1inf, g2, g2inf, n);
+  void* o = h.out(c->io_out, out, 576);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_multi_miller_loop_device(c, t.g1, t.g1inf, t.g2, t.g2inf, n, o));
 }
 // ---- N independent multi_miller_loops in one call (bulk signature verification: N equations of k pairings each) -------------------
 // Segment s = terms [off[s], off[s + 1]).  Miller values per term on the throughput kernels (or the wide path when there are few),
 // one segmented Fp12 product, one batched final exponentiation.  The product of independently squared per-term values is the
 // reference's shared-accumulator value exactly (Fp12 is a field: same element, canonical limbs).
 constexpr size_t MML_SEG_SHARED_MIN = 49152;      // segments from which blsgpu_multi_miller_loop_many shares squarings inside a segment
-static int final_exp_launch(blsgpu_ctx* c, const void* in, size_t n, void* out) {
-  const int layout = pairing_layout_for(c, n);
-  if (layout < 0) return wide_missing(c);
-  if (layout == 256) wide_launch(c, 2, in, nullptr, nullptr, nullptr, n, out);
-  else if (layout == 4) KLAUNCH(k_final_exp_quad, dim3(nblk(n * QL, QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, c->stream, (const u32*)in, (u32*)out, n);
-  else KLAUNCH(k_final_exp, dim3(nblk(n * PL, PAIRING_BLOCK)), dim3(PAIRING_BLOCK), 0, c->stream, (const u32*)in, (u32*)out, n);
-  LAUNCHCHK();
+static int mml_many_check(blsgpu_ctx* c, const void* g1, const void* g2, const void* offsets, size_t nseg, size_t total, const void* out) { return (!c || (nseg && (!offsets || !out)) || (total && (!g1 || !g2))) ? bad("multi_miller_loop_many: NULL argument") : BLSGPU_OK; }
+// offsets[0..nseg] of a host _many form: offsets[0] == 0 and non-decreasing; *longest = the longest segment (at least 1)
+static int segments_of(const char* what, const uint64_t* offsets, size_t nseg, size_t* longest) {
+  if (offsets[0] != 0) return bad((std::string(what) + ": offsets[0] must be 0").c_str());
+  if (!scan_offsets(offsets, nseg, longest)) return bad((std::string(what) + ": offsets must be non-decreasing").c_str());
+  if (!*longest) *longest = 1;
   return BLSGPU_OK;
 }
 extern "C" int blsgpu_multi_miller_loop_many_device(blsgpu_ctx* c, const void* g1, const void* g1inf, const void* g2, const void* g2inf, const void* d_offsets, size_t nseg,
                                                     size_t total, size_t max_seg_terms, int final_exp, void* out) { CTX_CLAIM(c);
-  if (!c || (nseg && (!d_offsets || !out)) || (total && (!g1 || !g2))) return bad("multi_miller_loop_many: NULL argument");
+  if (int rc = mml_many_check(c, g1, g2, d_offsets, nseg, total, out)) return rc;
   if (!nseg) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   // runs per segment of the segmented product: 1 when the caller bounds the segments by 32 terms; otherwise (bound unknown or larger)
@@ -267,7 +266,7 @@ extern "C" int blsgpu_multi_miller_loop_many_device(blsgpu_ctx* c, const void* g
   }
   // the shared-accumulator kernel is the lane-pair layout's: a context pinned to the quad (or wide) layout keeps the per-term path
   const bool seg_shared = total && max_seg_terms >= 2 && max_seg_terms <= (size_t)MML_MAX_K && nseg >= MML_SEG_SHARED_MIN && (c->pairing_layout == 0 || c->pairing_layout == 2);
-  if ((!seg_shared && c->io_out.reserve((total ? total : 1) * 576)) || (!seg_shared && parts > 1 && c->io_c.reserve(nseg * parts * 576)) || (final_exp && c->io_d.reserve(nseg * 576))) {
+  if ((!seg_shared && c->mml_vals.reserve((total ? total : 1) * 576)) || (!seg_shared && parts > 1 && c->io_c.reserve(nseg * parts * 576)) || (final_exp && c->io_d.reserve(nseg * 576))) {
     g_err = "hipMalloc failed"; return BLSGPU_ERR_HIP;
   }
   u32* prod = final_exp ? c->io_d.as<u32>() : (u32*)out;
@@ -280,8 +279,8 @@ extern "C" int blsgpu_multi_miller_loop_many_device(blsgpu_ctx* c, const void* g
     LAUNCHCHK();
     return final_exp ? final_exp_launch(c, prod, nseg, out) : BLSGPU_OK;
   }
-  if (total) { int rc = pairing_launch(c, 1, g1, g1inf, g2, g2inf, total, c->io_out.p); if (rc) return rc; }
-  KLAUNCH(k_fp12_prod_seg_quad, dim3(nblk(nseg * parts * QL, QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, c->stream, c->io_out.as<u32>(), (const unsigned long long*)d_offsets,
+  if (total) { int rc = pairing_launch(c, 1, g1, g1inf, g2, g2inf, total, c->mml_vals.p); if (rc) return rc; }
+  KLAUNCH(k_fp12_prod_seg_quad, dim3(nblk(nseg * parts * QL, QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, c->stream, c->mml_vals.as<u32>(), (const unsigned long long*)d_offsets,
                      nseg, total, parts, parts > 1 ? c->io_c.as<u32>() : prod);
   LAUNCHCHK();
   if (parts > 1) {
@@ -292,34 +291,18 @@ extern "C" int blsgpu_multi_miller_loop_many_device(blsgpu_ctx* c, const void* g
 }
 extern "C" int blsgpu_multi_miller_loop_many(blsgpu_ctx* c, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, const uint64_t* offsets, size_t nseg,
                                              int final_exp, uint64_t* out) { CTX_CLAIM(c);
-  if (!c || (nseg && (!offsets || !out))) return bad("multi_miller_loop_many: NULL argument");
+  if (int rc = mml_many_check(c, g1, g2, offsets, nseg, 0, out)) return rc;
   if (!nseg) return BLSGPU_OK;
-  if (offsets[0] != 0) return bad("multi_miller_loop_many: offsets[0] must be 0");
   size_t max_k = 0;
-  for (size_t i = 0; i < nseg; i++) {
-    if (offsets[i] > offsets[i + 1]) return bad("multi_miller_loop_many: offsets must be non-decreasing");
-    if (offsets[i + 1] - offsets[i] > max_k) max_k = (size_t)(offsets[i + 1] - offsets[i]);
-  }
+  if (int rc = segments_of("multi_miller_loop_many", offsets, nseg, &max_k)) return rc;
   const size_t n = (size_t)offsets[nseg];
-  if (n && (!g1 || !g2)) return bad("multi_miller_loop_many: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_a.reserve(n ? n * 96 : 16) || c->io_b.reserve(n ? n * 192 : 16) || c->flags_a.reserve(n ? n : 16) || c->flags_b.reserve(n ? n : 16) || c->io_e.reserve((nseg + 1) * 8) ||
-      c->io_f.reserve(nseg * 576)) {
-    g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP;
-  }
-  if (n) {
-    HIPCHK(hipMemcpyAsync(c->io_a.p, g1, n * 96, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->io_b.p, g2, n * 192, hipMemcpyHostToDevice, c->stream));
-    if (g1inf) HIPCHK(hipMemcpyAsync(c->flags_a.p, g1inf, n, hipMemcpyHostToDevice, c->stream));
-    if (g2inf) HIPCHK(hipMemcpyAsync(c->flags_b.p, g2inf, n, hipMemcpyHostToDevice, c->stream));
-  }
-  HIPCHK(hipMemcpyAsync(c->io_e.p, offsets, (nseg + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  int rc = blsgpu_multi_miller_loop_many_device(c, c->io_a.p, g1inf ? c->flags_a.p : nullptr, c->io_b.p, g2inf ? c->flags_b.p : nullptr, c->io_e.p, nseg, n, max_k ? max_k : 1, final_exp,
-                                                c->io_f.p);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_f.p, nseg * 576, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  if (int rc = mml_many_check(c, g1, g2, offsets, nseg, n, out)) return rc;       // (again: the terms are known now)
+  HostCall h(c);
+  const Terms t = stage_terms(h, g1, g1inf, g2, g2inf, n);
+  void* off = h.in(c->io_e, offsets, (nseg + 1) * 8);
+  void* o = h.out(c->io_out, out, nseg * 576);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_multi_miller_loop_many_device(c, t.g1, t.g1inf, t.g2, t.g2inf, off, nseg, n, max_k, final_exp, o));
 }
 // ---------------------------------------------------------------------------------------------------
 // G2Prepared resident on the device (prep.hip.h): pairings.rs:487-546 (the table), :554-603 (its consumers)
@@ -330,9 +313,13 @@ static void prepared_drop(blsgpu_g2_prepared* p) {
   if (p->ev_ready) hipEventDestroy(p->ev_ready);
   delete p;
 }
-extern "C" int blsgpu_g2_prepare_device(blsgpu_ctx* c, const void* d_g2, const void* d_inf, size_t m, blsgpu_g2_prepared** out) { CTX_CLAIM(c);
-  if (!c || !out || (m && !d_g2)) return bad("g2_prepare: NULL argument");
+static int g2_prepare_check(blsgpu_ctx* c, const void* g2, size_t m, blsgpu_g2_prepared** out) {
+  if (!c || !out || (m && !g2)) return bad("g2_prepare: NULL argument");
   if (m >= 0xfffffff0ull) return bad("g2_prepare: too many points for 32-bit table indices");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_g2_prepare_device(blsgpu_ctx* c, const void* d_g2, const void* d_inf, size_t m, blsgpu_g2_prepared** out) { CTX_CLAIM(c);
+  if (int rc = g2_prepare_check(c, d_g2, m, out)) return rc;
   HIPCHK(hipSetDevice(c->device));
   blsgpu_g2_prepared* p = new blsgpu_g2_prepared();
   p->device = c->device; p->n = m;
@@ -348,16 +335,14 @@ extern "C" int blsgpu_g2_prepare_device(blsgpu_ctx* c, const void* d_g2, const v
   return BLSGPU_OK;
 }
 extern "C" int blsgpu_g2_prepare(blsgpu_ctx* c, const uint64_t* g2, const uint8_t* inf, size_t m, blsgpu_g2_prepared** out) { CTX_CLAIM(c);
-  if (!c || !out || (m && !g2)) return bad("g2_prepare: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_b.reserve(m ? m * 192 : 16) || c->flags_b.reserve(m ? m : 16)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (m) HIPCHK(hipMemcpyAsync(c->io_b.p, g2, m * 192, hipMemcpyHostToDevice, c->stream));
-  if (m && inf) HIPCHK(hipMemcpyAsync(c->flags_b.p, inf, m, hipMemcpyHostToDevice, c->stream));
+  if (int rc = g2_prepare_check(c, g2, m, out)) return rc;
+  HostCall h(c);
+  void* q = h.in(c->io_b, g2, m * 192);
+  void* qi = h.in(c->flags_b, inf, m);
+  if (h.rc) return h.rc;
   blsgpu_g2_prepared* p = nullptr;
-  int rc = blsgpu_g2_prepare_device(c, c->io_b.p, inf ? c->flags_b.p : nullptr, m, &p);
-  if (rc) return rc;
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) { prepared_drop(p); return fail("g2_prepare", e, __LINE__); }
+  int rc = h.finish(blsgpu_g2_prepare_device(c, q, qi, m, &p));
+  if (rc) { if (p) prepared_drop(p); return rc; }           // (a failed synchronisation: the new table is freed)
   *out = p;
   return BLSGPU_OK;
 }
@@ -371,16 +356,14 @@ extern "C" void blsgpu_g2_prepared_free(blsgpu_g2_prepared* p) {
 extern "C" int blsgpu_g2_prepared_coeffs(blsgpu_ctx* c, const blsgpu_g2_prepared* p, size_t index, uint64_t* out, uint8_t* out_inf) { CTX_CLAIM(c);
   if (!c || !p || !out || index >= p->n) return bad("g2_prepared_coeffs: bad argument");
   if (p->device != c->device) return bad("g2_prepared_coeffs: the table lives on another device than the context");
-  HIPCHK(hipSetDevice(c->device));
-  const size_t bytes = (size_t)PREP_STEPS * 3 * 24 * 4;
-  if (c->io_out.reserve(bytes)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
+  HostCall h(c);
+  u32* o = (u32*)h.out(c->io_out, out, (size_t)PREP_STEPS * 3 * 24 * 4);
+  if (h.rc) return h.rc;
   HIPCHK(hipStreamWaitEvent(c->stream, p->ev_ready, 0));
-  KLAUNCH(k_g2_prepared_export, dim3(1), dim3(256), 0, c->stream, p->tab, index, c->io_out.as<u32>());
+  KLAUNCH(k_g2_prepared_export, dim3(1), dim3(256), 0, c->stream, p->tab, index, o);
   LAUNCHCHK();
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  if (out_inf) HIPCHK(hipMemcpyAsync(out_inf, p->inf + index, 1, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  if (out_inf) HIPCHK(hipMemcpyAsync(out_inf, p->inf + index, 1, hipMemcpyDeviceToHost, c->stream));      // (straight from the table)
+  return h.finish(BLSGPU_OK);
 }
 // one launch of k_mml_prep_quad: nseg quads, work area sized for kmax term slots per quad
 static int mmlp_launch(blsgpu_ctx* c, const void* g1, const void* g1inf, const void* g2, const void* g2inf, const void* qidx, const blsgpu_g2_prepared* p, const void* d_off,
@@ -443,32 +426,16 @@ static int check_qidx(const uint32_t* qidx, size_t n, const blsgpu_g2_prepared* 
   }
   return BLSGPU_OK;
 }
-// host-pointer staging shared by the two prepared entry points: g1 -> io_a, g2 -> io_b, flags -> flags_a/b, indices -> io_e
-static int mmlp_stage(blsgpu_ctx* c, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, const uint32_t* qidx, size_t n) {
-  if (c->io_a.reserve(n ? n * 96 : 16) || c->io_b.reserve(n ? n * 192 : 16) || c->flags_a.reserve(n ? n : 16) || c->flags_b.reserve(n ? n : 16) || c->io_e.reserve(n ? n * 4 : 16)) {
-    g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP;
-  }
-  if (!n) return BLSGPU_OK;
-  HIPCHK(hipMemcpyAsync(c->io_a.p, g1, n * 96, hipMemcpyHostToDevice, c->stream));
-  if (g2) HIPCHK(hipMemcpyAsync(c->io_b.p, g2, n * 192, hipMemcpyHostToDevice, c->stream));
-  if (g1inf) HIPCHK(hipMemcpyAsync(c->flags_a.p, g1inf, n, hipMemcpyHostToDevice, c->stream));
-  if (g2 && g2inf) HIPCHK(hipMemcpyAsync(c->flags_b.p, g2inf, n, hipMemcpyHostToDevice, c->stream));
-  if (qidx) HIPCHK(hipMemcpyAsync(c->io_e.p, qidx, n * 4, hipMemcpyHostToDevice, c->stream));
-  return BLSGPU_OK;
-}
 extern "C" int blsgpu_multi_miller_loop_prepared(blsgpu_ctx* c, const uint64_t* g1, const uint8_t* g1inf, const uint64_t* g2, const uint8_t* g2inf, const uint32_t* qidx,
                                                  const blsgpu_g2_prepared* p, size_t n, uint64_t* out) { CTX_CLAIM(c);
   if (!c || !out || (n && !g1)) return bad("multi_miller_loop_prepared: NULL argument");
   if (int rc = check_qidx(qidx, n, p, g2)) return rc;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->result.reserve(576)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (int rc = mmlp_stage(c, g1, g1inf, g2, g2inf, qidx, n)) return rc;
-  int rc = blsgpu_multi_miller_loop_prepared_device(c, c->io_a.p, g1inf ? c->flags_a.p : nullptr, g2 ? c->io_b.p : nullptr, (g2 && g2inf) ? c->flags_b.p : nullptr,
-                                                    qidx ? c->io_e.p : nullptr, p, n, c->result.p);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->result.p, 576, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  const Terms t = stage_terms(h, g1, g1inf, g2, g2inf, n);
+  void* q = h.in(c->io_f, qidx, n * 4);
+  void* o = h.out(c->io_out, out, 576);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_multi_miller_loop_prepared_device(c, t.g1, t.g1inf, t.g2, t.g2inf, q, p, n, o));
 }
 extern "C" int blsgpu_multi_miller_loop_prepared_many_device(blsgpu_ctx* c, const void* g1, const void* g1inf, const void* g2, const void* g2inf, const void* qidx,
                                                              const blsgpu_g2_prepared* p, const void* d_off, size_t nseg, size_t total, size_t max_seg_terms, int final_exp,
@@ -493,44 +460,22 @@ extern "C" int blsgpu_multi_miller_loop_prepared_many(blsgpu_ctx* c, const uint6
                                                       const blsgpu_g2_prepared* p, const uint64_t* offsets, size_t nseg, int final_exp, uint64_t* out) { CTX_CLAIM(c);
   if (!c || (nseg && (!offsets || !out))) return bad("multi_miller_loop_prepared_many: NULL argument");
   if (!nseg) return BLSGPU_OK;
-  if (offsets[0] != 0) return bad("multi_miller_loop_prepared_many: offsets[0] must be 0");
   size_t max_k = 0;
-  for (size_t i = 0; i < nseg; i++) {
-    if (offsets[i] > offsets[i + 1]) return bad("multi_miller_loop_prepared_many: offsets must be non-decreasing");
-    if (offsets[i + 1] - offsets[i] > max_k) max_k = (size_t)(offsets[i + 1] - offsets[i]);
-  }
+  if (int rc = segments_of("multi_miller_loop_prepared_many", offsets, nseg, &max_k)) return rc;
   const size_t n = (size_t)offsets[nseg];
   if (n && !g1) return bad("multi_miller_loop_prepared_many: NULL argument");
   if (int rc = check_qidx(qidx, n, p, g2)) return rc;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_f.reserve(nseg * 576) || c->io_c.reserve((nseg + 1) * 8)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (int rc = mmlp_stage(c, g1, g1inf, g2, g2inf, qidx, n)) return rc;
-  HIPCHK(hipMemcpyAsync(c->io_c.p, offsets, (nseg + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  int rc = blsgpu_multi_miller_loop_prepared_many_device(c, c->io_a.p, g1inf ? c->flags_a.p : nullptr, g2 ? c->io_b.p : nullptr, (g2 && g2inf) ? c->flags_b.p : nullptr,
-                                                         qidx ? c->io_e.p : nullptr, p, c->io_c.p, nseg, n, max_k ? max_k : 1, final_exp, c->io_f.p);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->io_f.p, nseg * 576, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  const Terms t = stage_terms(h, g1, g1inf, g2, g2inf, n);
+  void* q = h.in(c->io_f, qidx, n * 4);
+  void* off = h.in(c->io_e, offsets, (nseg + 1) * 8);
+  void* o = h.out(c->io_out, out, nseg * 576);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_multi_miller_loop_prepared_many_device(c, t.g1, t.g1inf, t.g2, t.g2inf, q, p, off, nseg, n, max_k, final_exp, o));
 }
-extern "C" int blsgpu_final_exponentiation_batch(blsgpu_ctx* c, const uint64_t* in, size_t n, uint64_t* out) { CTX_CLAIM(c);
-  if (!c || (n && (!in || !out))) return bad("final_exponentiation: NULL argument");
-  if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_a.reserve(n * 576) || c->io_out.reserve(n * 576)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, in, n * 576, hipMemcpyHostToDevice, c->stream));
-  const int layout = pairing_layout_for(c, n);
-  if (layout < 0) return wide_missing(c);
-  if (layout == 256) wide_launch(c, 2, c->io_a.p, nullptr, nullptr, nullptr, n, c->io_out.p);
-  else if (layout == 4) KLAUNCH(k_final_exp_quad, dim3(nblk(n * QL, QUAD_BLOCK)), dim3(QUAD_BLOCK), 0, c->stream, c->io_a.as<u32>(), c->io_out.as<u32>(), n);
-  else KLAUNCH(k_final_exp, dim3(nblk(n * PL, PAIRING_BLOCK)), dim3(PAIRING_BLOCK), 0, c->stream, c->io_a.as<u32>(), c->io_out.as<u32>(), n);
-  LAUNCHCHK();
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * 576, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
-}
+static int gt_mul_scalar_check(blsgpu_ctx* c, const void* gt, const void* scalars, size_t n, const void* out) { return (!c || (n && (!gt || !scalars || !out))) ? bad("gt_mul_scalar: NULL argument") : BLSGPU_OK; }
 extern "C" int blsgpu_gt_mul_scalar_batch_device(blsgpu_ctx* c, const void* gt, const void* scalars, size_t n, void* out) { CTX_CLAIM(c);
-  if (!c || (n && (!gt || !scalars || !out))) return bad("gt_mul_scalar: NULL argument");
+  if (int rc = gt_mul_scalar_check(c, gt, scalars, n, out)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
   KLAUNCH(k_gt_mul_scalar, dim3(nblk(n * PL, PAIRING_BLOCK)), dim3(PAIRING_BLOCK), 0, c->stream, (const u32*)gt, (const u32*)scalars, (u32*)out, n, c->scalar_form);
@@ -567,28 +512,22 @@ extern "C" int blsgpu_gt_is_identity_device(blsgpu_ctx* c, const void* gt, size_
   return BLSGPU_OK;
 }
 extern "C" int blsgpu_gt_mul_scalar_batch(blsgpu_ctx* c, const uint64_t* gt, const uint8_t* scalars, size_t n, uint64_t* out) { CTX_CLAIM(c);
-  if (!c || (n && (!gt || !scalars || !out))) return bad("gt_mul_scalar: NULL argument");
+  if (int rc = gt_mul_scalar_check(c, gt, scalars, n, out)) return rc;
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_a.reserve(n * 576) || c->io_b.reserve(n * 32) || c->io_out.reserve(n * 576)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, gt, n * 576, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
-  KLAUNCH(k_gt_mul_scalar, dim3(nblk(n * PL, PAIRING_BLOCK)), dim3(PAIRING_BLOCK), 0, c->stream, c->io_a.as<u32>(), c->io_b.as<u32>(), c->io_out.as<u32>(), n, c->scalar_form);
-  LAUNCHCHK();
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * 576, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  HostCall h(c);
+  void* g = h.in(c->io_a, gt, n * 576);
+  void* s = h.in(c->io_b, scalars, n * 32);
+  void* o = h.out(c->io_out, out, n * 576);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_gt_mul_scalar_batch_device(c, g, s, n, o));
 }
 extern "C" int blsgpu_fp12_product(blsgpu_ctx* c, const uint64_t* in, size_t n, uint64_t* out) { CTX_CLAIM(c);
-  if (!c || !out || (n && !in)) return bad("fp12_product: NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->io_a.reserve(n ? n * 576 : 16) || c->result.reserve(576)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  if (n) HIPCHK(hipMemcpyAsync(c->io_a.p, in, n * 576, hipMemcpyHostToDevice, c->stream));
-  int rc = fp12_product_device(c, c->io_a.as<u32>(), n, c->result.as<u32>());
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, c->result.p, 576, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  if (int rc = fp12_product_check(c, in, n, out)) return rc;
+  HostCall h(c);
+  void* i = h.in(c->io_a, in, n * 576);
+  void* o = h.out(c->io_out, out, 576);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fp12_product_device(c, i, n, o));
 }
 
 // ---- Fp6 / Fp12 self-test hooks (the kernels live with the pairing code) ------------------------------------------------------------

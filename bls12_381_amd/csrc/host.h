@@ -177,7 +177,8 @@ struct blsgpu_ctx {
   } slot[NSLOT];
   int next_slot = 0;
   unsigned long long msm_calls = 0;
-  DevBuf result, io_a, io_b, io_c, io_d, io_e, io_f, io_out, flags_a, flags_b;
+  DevBuf result, io_a, io_b, io_c, io_d, io_e, io_f, io_out, flags_a, flags_b;     // staging and core scratch: see HostCall below
+  DevBuf mml_vals;                      // Miller values per term of multi_miller_loop_device / _many_device
   int mmlp_k = 0;                       // A/B hook (env BLSGPU_MMLP_K): terms per accumulator of ONE long product (0 = automatic)
   int mml_impl = 0;                     // A/B hook (env BLSGPU_MML_IMPL): kernel behind blsgpu_multi_miller_loop_device with K > 1 -- 0 = automatic, 1 = k_multi_miller_shared
                                         // (rounds 2-4), 4 = k_mml_prep_quad with no prepared term
@@ -237,17 +238,6 @@ template <> struct GroupTag<Fp2Policy> { static constexpr int id = 2; };
 
 static inline unsigned nblk(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
-// A synchronous entry point owns its verdict: its kernels report into d_status[2] (cleared on the caller's stream before anything
-// of the call is enqueued), the word comes back with the call's result, and neither an earlier asynchronous call's flag is
-// blamed on this call nor is it cleared by it.
-struct SyncStatus {
-  blsgpu_ctx* c; u32 host = 0;
-  explicit SyncStatus(blsgpu_ctx* c_) : c(c_) { c->status_word = c->d_status + 2; }
-  ~SyncStatus() { c->status_word = c->d_status; }
-  int begin() { HIPCHK(hipMemsetAsync(c->d_status + 2, 0, 4, c->stream)); return BLSGPU_OK; }
-  int fetch() { HIPCHK(hipMemcpyAsync(&host, c->d_status + 2, 4, hipMemcpyDeviceToHost, c->stream)); return BLSGPU_OK; }      // then synchronise the stream
-  int verdict() const { return host ? bad("msm: a scalar is not canonical (>= r); Scalar::to_bytes never produces such bytes (scalar.rs:284-296)") : BLSGPU_OK; }
-};
 // one call with another scalar form than the context's setting (the *_mont entry points; the byte-format compositions pin SCALAR_BYTES)
 struct ScalarFormScope {
   blsgpu_ctx* c; int saved;
@@ -262,19 +252,91 @@ struct blsgpu_g2_prepared { int device = 0; size_t n = 0; u32* tab = nullptr; ui
 int staged_upload(blsgpu_ctx* c, void* dst, const void* src, size_t bytes);      // api_ctx.hip
 void acc_harvest(blsgpu_ctx* c, bool wait);                                       // api_ctx.hip (MSM accumulation timings)
 
+// ---- host-pointer entry points ------------------------------------------------------------------------------------------------
+// Every host-pointer entry point is  check -> stage -> device core -> finish:  it runs the argument check of its operation, stages its
+// arguments through ONE HostCall, calls the core its *_device twin calls, and lets HostCall copy the results back and synchronise.
+//
+// The context's DevBufs fall into two sets:
+//   staging       io_a, io_b, io_e, io_f, io_out, flags_a, flags_b: written by host-pointer entry points and host-only hooks alone
+//                 (through HostCall).  Every such call ends with a synchronised stream, so the next one may reuse them.
+//   core scratch  result, io_c, io_d, mml_vals and the named buffers (mmlp_*, fold_*, fr_*, h2c_uniform, ver, ...): used by the cores
+//                 behind the *_device entry points, whose work may still be in flight on a stream the caller has since left
+//                 (blsgpu_set_stream).  No function reachable from a *_device entry point names a staging buffer, so a host call
+//                 never stages into scratch that an asynchronous call is still using.
+struct HostCall {
+  blsgpu_ctx* c;
+  int rc = BLSGPU_OK;                   // the first failure of hipSetDevice, a reservation or an upload (the later steps are skipped)
+  struct Back { void* dst; const void* src; size_t bytes; };
+  Back back[4]; int nback = 0;          // the copies back, enqueued by finish()
+  bool status = false; u32 status_host = 0;
+  uint8_t keep[255]; bool keep_queued = false;       // host bytes an upload reads after in() returned (the reduced DST): live until finish()
+  explicit HostCall(blsgpu_ctx* c_) : c(c_) { hipError_t e = hipSetDevice(c->device); if (e != hipSuccess) rc = fail("hipSetDevice", e, __LINE__); }
+  ~HostCall() {
+    if (status) c->status_word = c->d_status;
+    if (keep_queued) (void)hipStreamSynchronize(c->stream);       // an error path left an upload of `keep` queued
+  }
+  bool reserve(DevBuf& b, size_t bytes) {
+    if (!rc && b.reserve(bytes < 16 ? 16 : bytes)) { g_err = "hipMalloc(io) failed"; rc = BLSGPU_ERR_HIP; }
+    return !rc;
+  }
+  // host -> b (staged_upload); the device pointer, or nullptr for a NULL source (optional flag arrays, an absent g2)
+  void* in(DevBuf& b, const void* src, size_t bytes) {
+    if (!src || !reserve(b, bytes)) return nullptr;
+    if (bytes) rc = staged_upload(c, b.p, src, bytes);
+    if (src == keep && bytes) keep_queued = true;
+    return rc ? nullptr : b.p;
+  }
+  // a result the core writes into b, copied to dst by finish() (not copied when dst is NULL: the core still gets the buffer)
+  void* out(DevBuf& b, void* dst, size_t bytes) {
+    if (!reserve(b, bytes)) return nullptr;
+    if (dst && bytes) back[nback++] = {dst, b.p, bytes};
+    return b.p;
+  }
+  void* inout(DevBuf& b, void* p, size_t bytes) { return in(b, p, bytes) ? out(b, p, bytes) : nullptr; }
+  // opt-in: the call owns its verdict.  Its kernels report into d_status[2] (cleared on the stream before anything of the call is
+  // enqueued), the word comes back with the result, and neither an earlier asynchronous call's flag is blamed on this call nor cleared by it.
+  void report_status() {
+    if (rc) return;
+    status = true;
+    c->status_word = c->d_status + 2;
+    hipError_t e = hipMemsetAsync(c->d_status + 2, 0, 4, c->stream);
+    if (e != hipSuccess) rc = fail("hipMemsetAsync(status)", e, __LINE__);
+  }
+  // rc of the core -> the call's result: the copies back, one synchronisation of the stream, the verdict
+  int finish(int core_rc) {
+    if (rc) return rc;
+    if (core_rc) return core_rc;
+    for (int i = 0; i < nback; i++) HIPCHK(hipMemcpyAsync(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(hipMemcpyAsync(&status_host, c->d_status + 2, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    keep_queued = false;
+    return status_host ? bad("msm: a scalar is not canonical (>= r); Scalar::to_bytes never produces such bytes (scalar.rs:284-296)") : BLSGPU_OK;
+  }
+};
+
+// offsets[0..n] of n segments: true when non-decreasing; *longest = the longest segment
+static inline bool scan_offsets(const uint64_t* offsets, size_t n, size_t* longest = nullptr) {
+  size_t m = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (offsets[i] > offsets[i + 1]) return false;
+    if (offsets[i + 1] - offsets[i] > m) m = (size_t)(offsets[i + 1] - offsets[i]);
+  }
+  if (longest) *longest = m;
+  return true;
+}
+
 // host side of the element-wise self-test hooks (blsgpu_fp_op .. blsgpu_fp12_op): stage, launch, fetch
 template <class Launch>
 static int elem_op_run(blsgpu_ctx* c, int words, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, Launch launch) {
   if (!c || (n && (!a || !out))) return bad("op: NULL argument");
   if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  size_t bytes = n * words * 4;
-  if (c->io_a.reserve(bytes) || c->io_b.reserve(bytes) || c->io_out.reserve(bytes)) { g_err = "hipMalloc(io) failed"; return BLSGPU_ERR_HIP; }
-  HIPCHK(hipMemcpyAsync(c->io_a.p, a, bytes, hipMemcpyHostToDevice, c->stream));
-  if (b) HIPCHK(hipMemcpyAsync(c->io_b.p, b, bytes, hipMemcpyHostToDevice, c->stream));
-  launch(c->io_a.as<u32>(), b ? c->io_b.as<u32>() : (const u32*)nullptr, c->io_out.as<u32>());
+  HostCall h(c);
+  const size_t bytes = n * words * 4;
+  const u32* x = (const u32*)h.in(c->io_a, a, bytes);
+  const u32* y = (const u32*)h.in(c->io_b, b, bytes);
+  u32* o = (u32*)h.out(c->io_out, out, bytes);
+  if (h.rc) return h.rc;
+  launch(x, y, o);
   LAUNCHCHK();
-  HIPCHK(hipMemcpyAsync(out, c->io_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLSGPU_OK;
+  return h.finish(BLSGPU_OK);
 }

@@ -2958,7 +2958,7 @@ def test_bench_plain_run_dumps_the_last_step_reproducibly(tmp_path):
     assert bytes(got[0].astype(np.uint8)) == want
 
 
-def test_round6_entry_points_edge_cases_and_argument_errors(ctx):
+def test_round6_entry_points_edge_cases_and_argument_errors(ctx, golden_dir):
     """round-6 entry points: empty inputs are values (the identity, nothing written), NULL / out-of-range arguments are status codes with a
     message, the scalar form of a context is restored by the *_mont entry points, and the kernel-timing facility reports what was launched"""
     import ctypes
@@ -2999,6 +2999,11 @@ def test_round6_entry_points_edge_cases_and_argument_errors(ctx):
     assert lib.blsgpu_expand_message_batch(ctx.h, 0, P(m), P(np.array([1, 0], dtype=np.uint64)), 1, P(m), 1, 32, P(out)) == ERR_ARG and b"offsets" in lib.blsgpu_last_error()
     assert lib.blsgpu_hash_to_scalar_batch(ctx.h, 0, P(m), P(off), 1, P(m), 1, 2000, P(out)) == ERR_ARG                 # 2000 * 48 > 65535
     assert lib.blsgpu_hash_to_curve_expander_batch(ctx.h, 3, 1, P(m), P(off), 1, P(m), 1, 0, P(out)) == ERR_ARG        # group 3
+    # oversized lengths are argument errors, found before anything is reserved or staged, and the context stays usable
+    assert lib.blsgpu_expand_message_batch(ctx.h, 0, P(m), P(off), 1, P(m), 1, 1 << 40, P(out)) == ERR_ARG and b"65535" in lib.blsgpu_last_error()
+    assert lib.blsgpu_hash_to_scalar_batch(ctx.h, 0, P(m), P(off), 1, P(m), 1, 1 << 40, P(out)) == ERR_ARG
+    t = next(t for t in _h2c_vectors(golden_dir)["expand_msg"] if "sha256" in t["test"])
+    assert bytes(ctx.expand_message(A.EXPAND_XMD_SHA256, [bytes.fromhex(t["msg"])], bytes.fromhex(t["dst"]), t["len_in_bytes"])[0]).hex() == t["out"]
     # kernel timing: off by default (empty report), on: one line per kernel of the calls made, cleared by the report
     assert ctx.kernel_timing_report() == {}
     ctx.kernel_timing(True)
