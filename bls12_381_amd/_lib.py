@@ -85,6 +85,10 @@ SIGNATURES = {
     "blsgpu_g2_msm_many": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_sz, c_vp]),
     "blsgpu_g1_msm_many_device": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_sz, c_vp]),
     "blsgpu_g2_msm_many_device": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_sz, c_vp]),
+    "blsgpu_g1_msm_segments": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_g2_msm_segments": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_g1_msm_segments_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_vp]),
+    "blsgpu_g2_msm_segments_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_vp]),
     "blsgpu_set_msm_window": (c_int, [c_vp, c_int]),
     "blsgpu_g1_mul_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "blsgpu_g2_mul_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

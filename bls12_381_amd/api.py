@@ -332,6 +332,32 @@ class Context:
         check(fn(self.h, bases.handle, 0, _ptr(s), n, k, _ptr(out)), "msm_many")
         return out
 
+    def msm_segments(self, bases, scalars, offsets, base_first=None):
+        """k independent MSMs in one call (blsgpu_g{1,2}_msm_segments): segment j = scalars[offsets[j]:offsets[j+1]] over
+        bases[base_first[j] : base_first[j] + len_j] (base_first None: bases[offsets[j] : offsets[j+1]]).  scalars: ints /
+        Scalars / (total, 32) uint8 (`Scalar::to_bytes`); offsets: k + 1 values.  Returns (k, 18|36) uint64 projective limbs."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError("msm_segments: offsets needs k + 1 entries")
+        k = off.shape[0] - 1
+        s = scalars_to_bytes(scalars) if len(scalars) else np.zeros((0, 32), dtype=np.uint8)
+        if s.shape[0] != int(off[-1]):
+            raise ValueError("msm_segments: offsets[k] differs from the number of scalars")
+        bf = None if base_first is None else np.ascontiguousarray(base_first, dtype=np.uint32).reshape(-1)
+        if bf is not None and bf.shape[0] != k:
+            raise ValueError("msm_segments: base_first needs k entries")
+        out = np.zeros((k, 18 if bases.group == 1 else 36), dtype=np.uint64)
+        fn = self.lib.blsgpu_g1_msm_segments if bases.group == 1 else self.lib.blsgpu_g2_msm_segments
+        check(fn(self.h, bases.handle, _ptr(bf), _ptr(off), _ptr(s), k, _ptr(out)), "msm_segments")
+        return out
+
+    def msm_segments_device(self, bases, d_scalars, d_offsets, k, total, d_out, d_base_first=None):
+        """device form of msm_segments: u32 offsets (k + 1) / base_first (k or None), scalars in the context's scalar form and the
+        (k, 18|36) u64 result in device memory; enqueued on the context's stream (contract violations: reported by synchronize())"""
+        fn = self.lib.blsgpu_g1_msm_segments_device if bases.group == 1 else self.lib.blsgpu_g2_msm_segments_device
+        check(fn(self.h, bases.handle, ctypes.c_void_p(d_base_first) if d_base_first else None, ctypes.c_void_p(d_offsets),
+                 ctypes.c_void_p(d_scalars) if d_scalars else None, k, total, ctypes.c_void_p(d_out)), "msm_segments_device")
+
     def msm_bytes(self, group, bases_uncompressed, scalars):
         """MSM on the reference's public encodings: bases = n uncompressed encodings (bytes), scalars = ints / (n,32) bytes;
         returns the uncompressed encoding of the sum."""

@@ -3,6 +3,7 @@
 #include "host.h"
 #include "abi_kernels.hip.h"
 #include "mulbatch.hip.h"
+#include "msm_seg.hip.h"
 
 // ---------------------------------------------------------------------------------------------------
 // bases
@@ -624,6 +625,91 @@ static int msm_many_host(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first,
 }
 extern "C" int blsgpu_g1_msm_many(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, const uint8_t* s, size_t n, size_t k, uint64_t* out) { CTX_CLAIM(c); return msm_many_host<FpPolicy>(c, b, first, s, n, k, out); }
 extern "C" int blsgpu_g2_msm_many(blsgpu_ctx* c, const blsgpu_bases* b, size_t first, const uint8_t* s, size_t n, size_t k, uint64_t* out) { CTX_CLAIM(c); return msm_many_host<Fp2Policy>(c, b, first, s, n, k, out); }
+
+// k independent small MSMs, segment j = scalars [offsets[j], offsets[j+1]) over bases [base_first[j], base_first[j] + len_j)
+// (msm_seg.hip.h): two launches per batch of segments on the context's stream, scratch of their own (a pipelined msm_device still
+// in flight keeps its slot buffers), no slot of the MSM pipeline.
+static_assert(BLSGPU_SEG_LEN_MAX == SEG_LEN_MAX, "include/bls12_381_hip.h and limits.h disagree on the segment length limit");
+constexpr size_t SEG_K_MAX = (size_t)1 << 27;
+constexpr size_t SEG_BATCH_BYTES = (size_t)64 << 20;     // window sums of one batch of segments
+template <class F>
+static int msm_segments_check(blsgpu_ctx* c, const blsgpu_bases* bases, const void* offsets, const void* scalars, size_t k, size_t total, const void* out) {
+  if (!c || !bases || (k && (!offsets || !out)) || (total && !scalars)) return bad("msm_segments: NULL argument");
+  if (bases->group != GroupTag<F>::id) return bad("msm_segments: bases belong to the other group");
+  if (bases->device != c->device) return bad("msm_segments: bases live on another device than the context");
+  if (total > ((size_t)1 << 27)) return bad("msm_segments: more than 2^27 scalars in one call");
+  if (k > SEG_K_MAX) return bad("msm_segments: more than 2^27 segments in one call");
+  return BLSGPU_OK;
+}
+template <class F, int MODE, class FK>
+static int msm_segments_launch(blsgpu_ctx* c, const blsgpu_bases* bases, const u32* bf, const u32* off, const u32* s, size_t k, size_t total, u32* out) {
+  typedef SegCfg<FK, MODE> C;
+  constexpr int PW = Store<F>::PROJ_WORDS, WW = Wire<F>::WORDS;
+  const size_t per_seg = (size_t)C::NWIN * PW * 4;
+  size_t batch = SEG_BATCH_BYTES / per_seg;
+  if (batch > k) batch = k;
+  if (c->seg_wsum.reserve(batch * per_seg) || c->seg_rec.reserve(batch * PW * 4)) { g_err = "hipMalloc(msm_segments scratch) failed"; return BLSGPU_ERR_HIP; }
+  for (size_t s0 = 0; s0 < k; s0 += batch) {
+    const u32 nb = (u32)(k - s0 < batch ? k - s0 : batch);
+    KLAUNCH((k_msm_seg_accumulate<FK, MODE>), dim3(nb * C::NGRP), dim3(SEG_THREADS), 0, c->stream, bases->rec, bases->endo, bases->n, bf, off, s,
+            (u32)s0, (u32)total, c->scalar_form, c->status_word, c->seg_wsum.as<u32>());
+    KLAUNCH((k_msm_seg_combine<FK, C::NWIN>), dim3(nblk((size_t)nb * C::LPA, 256)), dim3(256), 0, c->stream, c->seg_wsum.as<u32>(), c->seg_rec.as<u32>(), nb);
+    KLAUNCH(k_proj_export<F>, dim3(nblk(nb, 256)), dim3(256), 0, c->stream, c->seg_rec.as<u32>(), out + s0 * 3 * WW, (size_t)nb);
+    LAUNCHCHK();
+  }
+  return BLSGPU_OK;
+}
+template <class F>
+static int msm_segments_device(blsgpu_ctx* c, const blsgpu_bases* bases, const void* d_bf, const void* d_off, const void* d_s, size_t k, size_t total, void* d_out) {
+  if (int rc = msm_segments_check<F>(c, bases, d_off, d_s, k, total, d_out)) return rc;
+  if (!k) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  // the records (and images) may have been written on another stream than this call's (blsgpu_set_stream after the upload)
+  if (!bases->ready_seen) {
+    if (hipEventQuery(bases->ev_ready) == hipSuccess) bases->ready_seen = true;
+    else HIPCHK(hipStreamWaitEvent(c->stream, bases->ev_ready, 0));
+  }
+  // the endomorphism split only for sets in the subgroup (tested or vouched for) whose images are resident, as in msm_device
+  const bool split = (bases->subgroup == 1 || bases->subgroup == 2) && bases->endo && !c->no_glv;
+  const u32 *bf = (const u32*)d_bf, *off = (const u32*)d_off, *s = (const u32*)d_s;
+  u32* out = (u32*)d_out;
+  if constexpr (GroupTag<F>::id == 1)
+    return split ? msm_segments_launch<F, SEG_GLV, FpPolicy>(c, bases, bf, off, s, k, total, out) : msm_segments_launch<F, SEG_PLAIN, FpPolicy>(c, bases, bf, off, s, k, total, out);
+  else
+    return split ? msm_segments_launch<F, SEG_GLS, Fp2PairPolicy>(c, bases, bf, off, s, k, total, out) : msm_segments_launch<F, SEG_PLAIN, Fp2PairPolicy>(c, bases, bf, off, s, k, total, out);
+}
+template <class F>
+static int msm_segments_host(blsgpu_ctx* c, const blsgpu_bases* bases, const uint32_t* base_first, const uint32_t* offsets, const uint8_t* scalars, size_t k, uint64_t* out) {
+  if (!offsets && k) return bad("msm_segments: NULL argument");
+  const size_t total = k ? offsets[k] : 0;
+  if (int rc = msm_segments_check<F>(c, bases, offsets, scalars, k, total, out)) return rc;
+  if (!k) return BLSGPU_OK;
+  // everything is checked before anything is staged: the kernel's own checks are the device form's
+  for (size_t j = 0; j < k; j++) {
+    if (offsets[j + 1] < offsets[j]) return bad("msm_segments: offsets decrease");
+    const size_t len = offsets[j + 1] - offsets[j];
+    if (len > SEG_LEN_MAX) return bad("msm_segments: a segment is longer than BLSGPU_SEG_LEN_MAX");
+    const size_t first = base_first ? base_first[j] : offsets[j];
+    if (first + len > bases->n) return bad("msm_segments: a segment's bases exceed the resident set");
+  }
+  ScalarFormScope bytes_form(c, SCALAR_BYTES);        // the host form's scalars ARE `Scalar::to_bytes()` output, whatever the context's setting
+  HostCall h(c);
+  h.report_status();
+  void* doff = h.in(c->io_a, offsets, (k + 1) * 4);
+  void* dbf = h.in(c->io_e, base_first, k * 4);
+  void* ds = h.in(c->io_b, scalars, total * 32);
+  void* o = h.out(c->io_out, out, k * 3 * Wire<F>::WORDS * 4);
+  if (h.rc) return h.rc;
+  return h.finish(msm_segments_device<F>(c, bases, dbf, doff, ds, k, total, o));
+}
+extern "C" int blsgpu_g1_msm_segments(blsgpu_ctx* c, const blsgpu_bases* b, const uint32_t* bf, const uint32_t* off, const uint8_t* s, size_t k, uint64_t* out) { CTX_CLAIM(c);
+  return msm_segments_host<FpPolicy>(c, b, bf, off, s, k, out); }
+extern "C" int blsgpu_g2_msm_segments(blsgpu_ctx* c, const blsgpu_bases* b, const uint32_t* bf, const uint32_t* off, const uint8_t* s, size_t k, uint64_t* out) { CTX_CLAIM(c);
+  return msm_segments_host<Fp2Policy>(c, b, bf, off, s, k, out); }
+extern "C" int blsgpu_g1_msm_segments_device(blsgpu_ctx* c, const blsgpu_bases* b, const void* bf, const void* off, const void* s, size_t k, size_t total, void* out) { CTX_CLAIM(c);
+  return msm_segments_device<FpPolicy>(c, b, bf, off, s, k, total, out); }
+extern "C" int blsgpu_g2_msm_segments_device(blsgpu_ctx* c, const blsgpu_bases* b, const void* bf, const void* off, const void* s, size_t k, size_t total, void* out) { CTX_CLAIM(c);
+  return msm_segments_device<Fp2Policy>(c, b, bf, off, s, k, total, out); }
 // Repeated one-shot MSMs over the SAME base array (a drop-in caller that passes its SRS slice on every call: the reference's surface
 // has no place for a resident handle).  Opt-in (blsgpu_set_bases_cache): a base array is recognised by its length and a fingerprint of
 // 64 evenly spaced points -- the caller promises not to change an array it passes again.  First sight: the one-shot path as always.

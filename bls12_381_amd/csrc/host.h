@@ -198,6 +198,7 @@ struct blsgpu_ctx {
   bool ver_consts_ready = false; hipEvent_t ev_ver = nullptr;
   hipStream_t ver_stream[2] = {nullptr, nullptr}; hipEvent_t ev_ver_side[3] = {};     // the independent stages of the chain run side by side
   DevBuf h2c_uniform;                   // uniform bytes between k_expand_message and the kernels that consume them (expand.hip.h)
+  DevBuf seg_wsum, seg_rec;             // segmented MSM (msm_seg.hip.h): window sums and results of a batch of segments -- not the slots' buffers
   DevBuf fb_stage;                      // staging of the one-byte scalars the tables are built from
   DevBuf fb_table[2];                   // fixed-base comb tables of the generators (k_fixed_base): 32 x 256 affine records each, built at first use
   hipEvent_t ev_fb[2] = {};             // recorded where a table was built; awaited by every user (the caller may switch streams)

@@ -154,6 +154,33 @@ int blsgpu_g1_msm_many(blsgpu_ctx* ctx, const blsgpu_bases* bases, size_t first,
 int blsgpu_g2_msm_many(blsgpu_ctx* ctx, const blsgpu_bases* bases, size_t first, const uint8_t* scalars, size_t n, size_t k, uint64_t* out_xyz);
 int blsgpu_g1_msm_many_device(blsgpu_ctx* ctx, const blsgpu_bases* bases, size_t first, const void* d_scalars, size_t n, size_t k, void* d_out_xyz);
 int blsgpu_g2_msm_many_device(blsgpu_ctx* ctx, const blsgpu_bases* bases, size_t first, const void* d_scalars, size_t n, size_t k, void* d_out_xyz);
+/* Segmented MSM: k independent small MSMs of different lengths, each over its own slice of the resident bases, in one call
+ * (e.g. the verifier equations of many proofs, randomised batch checks grouped by key, commitments to many short polynomials):
+ *   out[j] = sum_{i < len_j} scalars[offsets[j] + i] * bases[base_first[j] + i],   len_j = offsets[j+1] - offsets[j],  j < k.
+ * offsets holds k + 1 non-decreasing u32 values with offsets[0] = 0; total = offsets[k] scalars of 32 bytes.  base_first holds k
+ * u32 values; base_first == NULL means base_first[j] = offsets[j] (points and scalars side by side).  Slices may overlap (a shared
+ * SRS prefix: base_first all 0).  Results are k projective wire points (18 / 36 u64 each): possibly another representative than
+ * `*_msm` returns, the same affine point.  Exact for every curve point, as `*_msm` is: the endomorphism split is used only for sets
+ * in the subgroup (state 1 or 2) whose images are resident, plain 256-bit windows otherwise.  An empty segment gives the identity;
+ * k = 0 does nothing.
+ * Limits: len_j <= BLSGPU_SEG_LEN_MAX, total <= 2^27, k <= 2^27.  Longer MSMs belong to `*_msm` / `*_msm_many` (at 4096 points
+ * the segmented path is still faster than `*_msm_many` over shared bases; profiles/msm_segments_time.json).
+ * Host form: scalars are ALWAYS `Scalar::to_bytes()` output, whatever blsgpu_set_scalar_form says (as `*_msm_bytes`).  Offsets,
+ * lengths and base ranges are checked before anything is staged (BLSGPU_ERR_ARG); a scalar >= r gives BLSGPU_ERR_ARG from the call.
+ * Device form: d_offsets / d_base_first / d_scalars / d_out_xyz in device memory, `total` = offsets[k] as the caller knows it; the
+ * scalars follow the context's scalar form (a `blsgpu_fr_from_bytes_device` -> segments chain needs no conversion).  Enqueued on the
+ * context's stream without synchronising.  A segment that breaks the rules above (decreasing offsets, offsets[j+1] > total, too
+ * long, bases outside the set) and a scalar >= r are reported by the next blsgpu_synchronize (BLSGPU_ERR_ARG); the value of a bad
+ * segment is unspecified.  Both forms use scratch of their own, not the buffers of pipelined `*_msm_device` calls in flight. */
+#define BLSGPU_SEG_LEN_MAX 4096
+int blsgpu_g1_msm_segments(blsgpu_ctx* ctx, const blsgpu_bases* bases, const uint32_t* base_first, const uint32_t* offsets,
+                           const uint8_t* scalars, size_t k, uint64_t* out_xyz);
+int blsgpu_g2_msm_segments(blsgpu_ctx* ctx, const blsgpu_bases* bases, const uint32_t* base_first, const uint32_t* offsets,
+                           const uint8_t* scalars, size_t k, uint64_t* out_xyz);
+int blsgpu_g1_msm_segments_device(blsgpu_ctx* ctx, const blsgpu_bases* bases, const void* d_base_first, const void* d_offsets,
+                                  const void* d_scalars, size_t k, size_t total, void* d_out_xyz);
+int blsgpu_g2_msm_segments_device(blsgpu_ctx* ctx, const blsgpu_bases* bases, const void* d_base_first, const void* d_offsets,
+                                  const void* d_scalars, size_t k, size_t total, void* d_out_xyz);
 /* Opt-in cache for callers that pass the SAME base array to the one-shot entry points again and again (a drop-in `msm(&bases, &scalars)`
  * over an SRS: the reference's surface has no resident handle).  entries = 0 (default) switches it off and drops what is cached.  An
  * array is recognised by its length and a fingerprint of 64 evenly spaced points, so the caller promises NOT to modify an array it
