@@ -10,6 +10,7 @@ arrays, so they can be handed to / taken from a Rust caller unchanged.
 Only (de)serialisation (big-endian byte encodings, src/notes/serialization.rs) and `Scalar` bookkeeping
 run on the host in Python integers; they are format conversion, not part of the compute path.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -75,6 +76,11 @@ def scalars_are_canonical(sb):
         lt |= eq & (w[:, k] < _R_WORDS[k])
         eq &= w[:, k] == _R_WORDS[k]
     return bool(lt.all())
+
+
+def _builds_bytes(scalars):
+    """True when scalars_to_bytes builds the bytes itself (ints / Scalars), False when it passes a raw uint8 array through"""
+    return not (isinstance(scalars, np.ndarray) and scalars.dtype == np.uint8)
 
 
 def scalars_to_bytes(scalars):
@@ -173,6 +179,7 @@ class Context:
         check(self.lib.blsgpu_create(device, ctypes.byref(h)), "blsgpu_create")
         self.h = h
         self.device = device
+        self.scalar_form = SCALAR_BYTES
 
     def close(self):
         if getattr(self, "h", None):
@@ -281,7 +288,8 @@ class Context:
         n = s.shape[0]
         out = np.zeros(18 if bases.group == 1 else 36, dtype=np.uint64)
         fn = self.lib.blsgpu_g1_msm if bases.group == 1 else self.lib.blsgpu_g2_msm
-        check(fn(self.h, bases.handle, first, _ptr(s), n, _ptr(out)), "msm")
+        with self._bytes_form(_builds_bytes(scalars)):
+            check(fn(self.h, bases.handle, first, _ptr(s), n, _ptr(out)), "msm")
         return out
 
     def msm_device(self, bases, d_scalars, n, d_out, first=0):
@@ -290,8 +298,24 @@ class Context:
 
     # scalars as the reference stores them: (n, 4) u64 Montgomery limbs of `Scalar([u64; 4])` (scalar.rs:23-27); `to_bytes` runs on the device
     def set_scalar_form(self, form):
-        """SCALAR_BYTES (0, default) or SCALAR_MONT (1) for every later scalar argument of this context (blsgpu_set_scalar_form)"""
+        """SCALAR_BYTES (0, default) or SCALAR_MONT (1) for every later scalar argument of this context (blsgpu_set_scalar_form).
+        Raw uint8 scalar arrays and device pointers are read in this form; ints and Scalars are always converted to canonical bytes
+        and read as such (the wrappers pin SCALAR_BYTES for those calls)."""
         check(self.lib.blsgpu_set_scalar_form(self.h, int(form)), "set_scalar_form")
+        self.scalar_form = int(form)
+
+    @contextlib.contextmanager
+    def _bytes_form(self, built):
+        """SCALAR_BYTES for one call whose scalar bytes the wrapper `built` itself from ints / Scalars; the context's form is restored
+        afterwards"""
+        if not built or self.scalar_form == SCALAR_BYTES:
+            yield
+            return
+        check(self.lib.blsgpu_set_scalar_form(self.h, SCALAR_BYTES), "set_scalar_form")
+        try:
+            yield
+        finally:
+            check(self.lib.blsgpu_set_scalar_form(self.h, self.scalar_form), "set_scalar_form")
 
     def msm_mont(self, bases, scalar_limbs, first=0):
         """sum_i scalars[i] * bases[first+i] with scalars as (n, 4) u64 Montgomery limbs (`&[Scalar]` memory)."""
@@ -322,14 +346,17 @@ class Context:
 
     def msm_many(self, bases, scalar_sets):
         """k MSMs over the same resident bases; scalar_sets: (k, n, 32) uint8 (or a list of k scalar lists).  Returns (k, 18|36)."""
+        built = False
         if isinstance(scalar_sets, np.ndarray) and scalar_sets.dtype == np.uint8:
             s = np.ascontiguousarray(scalar_sets)
         else:
             s = np.stack([scalars_to_bytes(x) for x in scalar_sets])
+            built = any(_builds_bytes(x) for x in scalar_sets)
         k, n = s.shape[0], s.shape[1]
         out = np.zeros((k, 18 if bases.group == 1 else 36), dtype=np.uint64)
         fn = self.lib.blsgpu_g1_msm_many if bases.group == 1 else self.lib.blsgpu_g2_msm_many
-        check(fn(self.h, bases.handle, 0, _ptr(s), n, k, _ptr(out)), "msm_many")
+        with self._bytes_form(built):
+            check(fn(self.h, bases.handle, 0, _ptr(s), n, k, _ptr(out)), "msm_many")
         return out
 
     def msm_segments(self, bases, scalars, offsets, base_first=None):
@@ -389,7 +416,8 @@ class Context:
         inf = _flags(infinity, xy.shape[0])
         out = np.zeros(18 if group == 1 else 36, dtype=np.uint64)
         fn = self.lib.blsgpu_g1_msm_host if group == 1 else self.lib.blsgpu_g2_msm_host
-        check(fn(self.h, _ptr(xy), _ptr(inf), _ptr(s), xy.shape[0], _ptr(out)), "msm_host")
+        with self._bytes_form(_builds_bytes(scalars)):
+            check(fn(self.h, _ptr(xy), _ptr(inf), _ptr(s), xy.shape[0], _ptr(out)), "msm_host")
         return out
 
     def mul_batch(self, group, xy, infinity, scalars):
@@ -403,7 +431,8 @@ class Context:
         inf = _flags(infinity, xy.shape[0])
         out = np.zeros((xy.shape[0], 18 if group == 1 else 36), dtype=np.uint64)
         fn = self.lib.blsgpu_g1_mul_batch if group == 1 else self.lib.blsgpu_g2_mul_batch
-        check(fn(self.h, _ptr(xy), _ptr(inf), _ptr(s), xy.shape[0], _ptr(out)), "mul_batch")
+        with self._bytes_form(_builds_bytes(scalars)):
+            check(fn(self.h, _ptr(xy), _ptr(inf), _ptr(s), xy.shape[0], _ptr(out)), "mul_batch")
         return out
 
     def mul_batch_device(self, group, d_xy, d_inf, d_scalars, n, d_out):
@@ -773,7 +802,8 @@ class Context:
         if sb.shape[0] != gt.shape[0]:
             raise ValueError("gt_mul_scalar_batch: lengths differ")
         out = np.zeros_like(gt)
-        check(self.lib.blsgpu_gt_mul_scalar_batch(self.h, _ptr(gt), _ptr(sb), gt.shape[0], _ptr(out)), "gt_mul_scalar_batch")
+        with self._bytes_form(_builds_bytes(scalars)):
+            check(self.lib.blsgpu_gt_mul_scalar_batch(self.h, _ptr(gt), _ptr(sb), gt.shape[0], _ptr(out)), "gt_mul_scalar_batch")
         return out
 
     # device-pointer variants (asynchronous on the context's stream); pointers are plain ints (e.g. tensor.data_ptr())
@@ -855,6 +885,7 @@ class Group:
         h = ctypes.c_void_p()
         check(self.lib.blsgpu_group_create(devs, len(devices), ctypes.byref(h)), "group_create")
         self.h = h
+        self.scalar_form = SCALAR_BYTES
 
     def close(self):
         if getattr(self, "h", None):
@@ -869,6 +900,15 @@ class Group:
 
     def __len__(self):
         return int(self.lib.blsgpu_group_size(self.h))
+
+    def _set_members_form(self, form):
+        for k in range(len(self)):
+            check(self.lib.blsgpu_set_scalar_form(ctypes.c_void_p(self.lib.blsgpu_group_ctx(self.h, k)), int(form)), "set_scalar_form")
+
+    def set_scalar_form(self, form):
+        """Context.set_scalar_form on every member (what the `*_sharded_device` MSMs read); `msm` with ints / Scalars still pins SCALAR_BYTES"""
+        self._set_members_form(form)
+        self.scalar_form = int(form)
 
     def set_assume_subgroup(self, on):
         for k in range(len(self)):
@@ -893,7 +933,14 @@ class Group:
         sb = scalars_to_bytes(scalars)
         out = np.zeros(18 if bases.gid == 1 else 36, dtype=np.uint64)
         fn = self.lib.blsgpu_g1_msm_sharded if bases.gid == 1 else self.lib.blsgpu_g2_msm_sharded
-        check(fn(self.h, bases.handle, _ptr(sb), sb.shape[0], _ptr(out)), "msm_sharded")
+        pin = _builds_bytes(scalars) and self.scalar_form != SCALAR_BYTES
+        if pin:
+            self._set_members_form(SCALAR_BYTES)
+        try:
+            check(fn(self.h, bases.handle, _ptr(sb), sb.shape[0], _ptr(out)), "msm_sharded")
+        finally:
+            if pin:
+                self._set_members_form(self.scalar_form)
         return out
 
     # device-pointer, asynchronous MSMs on every member (the pipelined headline path from one process)

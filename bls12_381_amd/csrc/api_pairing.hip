@@ -478,7 +478,8 @@ extern "C" int blsgpu_gt_mul_scalar_batch_device(blsgpu_ctx* c, const void* gt, 
   if (int rc = gt_mul_scalar_check(c, gt, scalars, n, out)) return rc;
   if (!n) return BLSGPU_OK;
   HIPCHK(hipSetDevice(c->device));
-  KLAUNCH(k_gt_mul_scalar, dim3(nblk(n * PL, PAIRING_BLOCK)), dim3(PAIRING_BLOCK), 0, c->stream, (const u32*)gt, (const u32*)scalars, (u32*)out, n, c->scalar_form);
+  KLAUNCH(k_gt_mul_scalar, dim3(nblk(n * PL, PAIRING_BLOCK)), dim3(PAIRING_BLOCK), 0, c->stream, (const u32*)gt, (const u32*)scalars, (u32*)out, n, c->scalar_form,
+          c->status_word);
   LAUNCHCHK();
   return BLSGPU_OK;
 }
@@ -515,6 +516,7 @@ extern "C" int blsgpu_gt_mul_scalar_batch(blsgpu_ctx* c, const uint64_t* gt, con
   if (int rc = gt_mul_scalar_check(c, gt, scalars, n, out)) return rc;
   if (!n) return BLSGPU_OK;
   HostCall h(c);
+  h.report_status();
   void* g = h.in(c->io_a, gt, n * 576);
   void* s = h.in(c->io_b, scalars, n * 32);
   void* o = h.out(c->io_out, out, n * 576);

@@ -304,7 +304,8 @@ int blsgpu_final_exponentiation_batch(blsgpu_ctx* ctx, const uint64_t* in_f, siz
 /* out = prod of n Fp12 values (`MillerLoopResult + MillerLoopResult`, src/pairings.rs:179-186; `Gt + Gt`). */
 int blsgpu_fp12_product(blsgpu_ctx* ctx, const uint64_t* in_f, size_t n, uint64_t out_f[72]);
 /* `&Gt * &Scalar` (src/pairings.rs:297-322) for n (element, scalar) pairs: out[i] = gt[i] "times" scalars[i], i.e. the
- * Fp12 power by the canonical little-endian 32-byte scalar (double-and-add over its 255 low bits). */
+ * Fp12 power by the canonical little-endian 32-byte scalar (double-and-add over its 255 low bits).  A scalar >= r (bytes, or limbs
+ * in BLSGPU_SCALAR_MONT) gives BLSGPU_ERR_ARG. */
 int blsgpu_gt_mul_scalar_batch(blsgpu_ctx* ctx, const uint64_t* gt, const uint8_t* scalars, size_t n, uint64_t* out);
 /* Device-pointer variants (inputs/outputs in device memory, asynchronous on the context's stream). */
 int blsgpu_pairing_batch_device(blsgpu_ctx* ctx, const void* d_g1_xy, const void* d_g1_inf, const void* d_g2_xy, const void* d_g2_inf, size_t n, void* d_out_gt);
@@ -570,6 +571,8 @@ int blsgpu_g1_from_bytes_batch_device(blsgpu_ctx* ctx, const void* d_bytes, size
 int blsgpu_g2_from_bytes_batch_device(blsgpu_ctx* ctx, const void* d_bytes, size_t n, int compressed, int checked, void* d_xy, void* d_infinity, void* d_ok);
 int blsgpu_g1_to_bytes_batch_device(blsgpu_ctx* ctx, const void* d_xy, const void* d_infinity, size_t n, int compressed, void* d_out);
 int blsgpu_g2_to_bytes_batch_device(blsgpu_ctx* ctx, const void* d_xy, const void* d_infinity, size_t n, int compressed, void* d_out);
+/* (d_scalars must be 16-byte aligned, as device allocations are: the kernel reads each 32-byte scalar as two 16-byte loads.  A scalar
+ * >= r, as bytes or as limbs, is reported by the next blsgpu_synchronize.) */
 int blsgpu_gt_mul_scalar_batch_device(blsgpu_ctx* ctx, const void* d_gt, const void* d_scalars, size_t n, void* d_out);
 /* d_flags[i] = 1 if gt[i] == Gt::identity() (= Fp12::one(), src/pairings.rs:211-218), else 0: the verdict of an equation
  * prod e(P_j, Q_j) == 1 without bringing 576 B per equation to the host.  (d_gt must be 16-byte aligned, as device allocations are.) */

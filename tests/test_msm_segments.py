@@ -3,6 +3,7 @@
 Every result is compared as an affine point with the reference definition (the C oracle's double-and-add + Sum per segment) on a
 sample of segments, and with the existing MSM path (`ctx.msm` / `point_sum`) where that covers the whole call."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -318,3 +319,261 @@ def test_between_pipelined_msm_device(ctx, group):
     for i in range(3):
         assert got[i] == _aff(ctx, group, ctx.msm(bases, S[i * n:(i + 1) * n]))[0], i
     assert _aff(ctx, group, d_seg.cpu().numpy().view(np.uint64)) == _aff(ctx, group, ctx.msm_segments(bases, S[3 * n:3 * n + int(off[-1])], off))
+
+
+# ---- edges of the kernel's own scalar recoding, chunk loop and batch loop, in all four (group, mode) configurations ----------------
+# split: the default context over subgroup bases (G1 GLV halves, G2 psi digits); plain: a context created with BLSGPU_NO_GLV = 1, whose
+# 64 windows of 4 bits span 2 (G1) or 4 (G2) workgroups that each recompute the signed digits of the windows below their own.
+CONFIGS = [(1, "split"), (1, "plain"), (2, "split"), (2, "plain")]
+CONFIG_IDS = ["g1-glv", "g1-plain", "g2-gls", "g2-plain"]
+SEG_BATCH_BYTES = 64 << 20                                         # api_msm.hip: window sums of one batch of segments
+PROJ_WORDS = {1: 44, 2: 84}                                        # msm.hip.h Store<FpPolicy / Fp2Policy>::PROJ_WORDS
+NWIN = {(1, "split"): 32, (1, "plain"): 64, (2, "split"): 16, (2, "plain"): 64}     # msm_seg.hip.h SegCfg::NWIN
+
+
+@pytest.fixture(scope="module")
+def plain_ctx():
+    import bls12_381_amd as b
+    os.environ["BLSGPU_NO_GLV"] = "1"
+    try:
+        c = b.Context(0)
+    finally:
+        os.environ.pop("BLSGPU_NO_GLV")
+    yield c
+    c.close()
+
+
+def _pick(ctx, plain_ctx, mode):
+    return plain_ctx if mode == "plain" else ctx
+
+
+def _gen_multiples(group, exps):
+    """[e mod r] G for every e by the C oracle's double-and-add, as _aff gives points: affine limb bytes, None for the identity"""
+    gen = o.G1_GEN if group == 1 else o.G2_GEN
+    g, _ = _wire(group, [gen])
+    sb = np.stack([np.frombuffer((int(e) % o.R_ORDER).to_bytes(32, "little"), dtype=np.uint8) for e in exps])
+    xy, inf = c_oracle.mul_batch_affine(group, np.tile(g, (len(exps), 1)), None, sb)
+    return [None if inf[i] else xy[i].tobytes() for i in range(len(exps))]
+
+
+def _bytes(vals):
+    return np.stack([np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8) for v in vals]) if len(vals) else np.zeros((0, 32), np.uint8)
+
+
+def _seg_exps(ks, ss, off, bf=None):
+    """the discrete log of every segment over bases [k_i] G: sum_i k[base_first_j + i] s[offsets_j + i] mod r"""
+    out = []
+    for j in range(len(off) - 1):
+        f = int(off[j]) if bf is None else int(bf[j])
+        out.append(sum(ks[f + i] * ss[int(off[j]) + i] for i in range(int(off[j + 1] - off[j]))) % o.R_ORDER)
+    return out
+
+
+def _run_vs_oracle(c, group, ks, ss, lens, bf=None, bases=None):
+    """segments over bases [k_i] G: every segment against the oracle; returns the (k, 18|36) result"""
+    off = _offsets(lens)
+    if bases is None:
+        bases = c.bases_from_scalars(group, _bytes(ks))
+    out = c.msm_segments(bases, _bytes(ss), off, base_first=bf)
+    got = _aff(c, group, out)
+    want = _gen_multiples(group, _seg_exps(ks, ss, off, bf))
+    bad = [j for j in range(len(lens)) if got[j] != want[j]]
+    assert not bad, "segments %s differ from the oracle (first scalar %s)" % (bad[:8], hex(ss[int(off[bad[0]])]) if lens[bad[0]] else "-")
+    return out
+
+
+def _rand(n, seed):
+    r = o.SplitMix64(seed)
+    return [r.scalar() for _ in range(n)]
+
+
+def _carry_values():
+    """scalars whose 4-bit signed recoding carries through long runs and across the window groups of plain mode (bits 64, 128, 192)
+    and of the GLV / psi sub-scalars, plus the top of the range [2^254, r): reduced mod r"""
+    rr = o.R_ORDER
+    v = []
+    for m in range(1, 64):
+        t = 1 << (4 * m)
+        v += [t - 1, t - 8, t - 9, t, t + 1, int("8" * m, 16), int("9" * m, 16)]
+    for b in (64, 128, 192):
+        for lo in (0x8, 0x9, 0xF):
+            for hi in (0x0, 0x7, 0x8, 0x9, 0xF):
+                v.append((lo << (b - 4)) | (hi << b))
+        v += [(1 << b) - 1 + (0x8 << b), int("8" * (b // 4), 16) + (0x9 << b), int("9" * (b // 4 + 1), 16), int("F" * (b // 4 + 2), 16),
+              (0x8 << (b - 4)) + (1 << (b - 4)) - 1, ((1 << 8) - 1) << (b - 4)]
+    for top in (4, 5, 6, 7):
+        t = top << 252
+        v += [t, t + 1, t + int("8" * 63, 16), t + int("9" * 63, 16), t + (1 << 252) - 1, t + (0x8 << 248), t + (0xF << 188) + (0x9 << 192)]
+    v += [rr - 1, rr - 8, rr - 9, rr - (1 << 128), (1 << 254) + (1 << 128) - 1]
+    return sorted({x % rr for x in v})
+
+
+def _boundary_values(group):
+    import decomp_model
+    return decomp_model.glv_candidates() if group == 1 else decomp_model.gls_candidates()
+
+
+@pytest.mark.parametrize("group,mode", CONFIGS, ids=CONFIG_IDS)
+def test_full_range_scalars(ctx, plain_ctx, group, mode):
+    """scalars uniform in [0, r) (almost half of them >= 2^254): every segment against the oracle, all of them through point_sum against
+    one MSM over the concatenation"""
+    from bls12_381_amd import synthetic
+    c = _pick(ctx, plain_ctx, mode)
+    rs = np.random.RandomState(201 + group)
+    lens = rs.randint(0, 41, size=300 if group == 1 else 150)
+    total = int(lens.sum())
+    kb, sb = synthetic.scalars(total, 211 + group), synthetic.scalars(total, 221 + group)
+    assert (sb[:, 31] >= 0x40).sum() > total // 3
+    ks, ss = synthetic.to_ints(kb), synthetic.to_ints(sb)
+    bases = c.bases_from_scalars(group, kb)
+    out = _run_vs_oracle(c, group, ks, ss, lens, bases=bases)
+    assert _aff(c, group, c.point_sum(group, out)) == _aff(c, group, c.msm(bases, sb))
+    bases.free()
+
+
+@pytest.mark.parametrize("group,mode", CONFIGS, ids=CONFIG_IDS)
+def test_decomposition_boundaries(ctx, plain_ctx, group, mode):
+    """every branch value of the GLV (G1) / psi (G2) split of tests/decomp_model.py as a product of its own, then all in one segment"""
+    c = _pick(ctx, plain_ctx, mode)
+    vals = _boundary_values(group)
+    n = len(vals)
+    ks = _rand(n, 231 + group)
+    bases = c.bases_from_scalars(group, _bytes(ks))
+    _run_vs_oracle(c, group, ks, vals, [1] * n, bases=bases)
+    _run_vs_oracle(c, group, ks, vals, [n], bf=np.zeros(1, np.uint32), bases=bases)
+    bases.free()
+
+
+@pytest.mark.parametrize("group,mode", CONFIGS, ids=CONFIG_IDS)
+def test_signed_recoding_carries(ctx, plain_ctx, group, mode):
+    """2^(4m) - 1, - 8, - 9, + 0, + 1 and the all-8 / all-9 nibble runs for m = 1..63, nibbles 8 / 9 / F straddling bits 64, 128 and 192,
+    and [2^254, r) with top nibbles 4..7: each as a product of its own, then all in one segment (several 128-scalar chunks)"""
+    c = _pick(ctx, plain_ctx, mode)
+    vals = _carry_values()
+    n = len(vals)
+    ks = _rand(n, 241 + group)
+    bases = c.bases_from_scalars(group, _bytes(ks))
+    _run_vs_oracle(c, group, ks, vals, [1] * n, bases=bases)
+    _run_vs_oracle(c, group, ks, vals, [n], bf=np.zeros(1, np.uint32), bases=bases)
+    bases.free()
+
+
+@pytest.mark.parametrize("group,mode", CONFIGS, ids=CONFIG_IDS)
+def test_chunk_and_list_shapes(ctx, plain_ctx, group, mode):
+    """lengths at the 128-scalar chunk boundaries up to SEG_LEN_MAX over a shared prefix; one base and one scalar over a whole segment
+    (every digit in one bucket per window: the longest lists, mostly doublings); P, -P alternating with equal scalars (accumulators
+    back at the identity again and again, within and across chunks; for G2 the complete-addition tail and its return to XYZZ)"""
+    c = _pick(ctx, plain_ctx, mode)
+    lens = [127, 128, 129, 255, 256, 257, 4095, 4096]
+    ks = _rand(SEG_LEN_MAX, 251 + group)
+    ss = _rand(sum(lens), 261 + group)
+    _run_vs_oracle(c, group, ks, ss, lens, bf=np.zeros(len(lens), np.uint32))
+    k, s, t = _rand(3, 271 + group)
+    ks = [k] * SEG_LEN_MAX
+    _run_vs_oracle(c, group, ks, [s] * SEG_LEN_MAX + [t] * 3000, [SEG_LEN_MAX, 3000], bf=np.zeros(2, np.uint32))
+    ks = [k, o.R_ORDER - k] * (SEG_LEN_MAX // 2 + 1)
+    lens = [SEG_LEN_MAX, SEG_LEN_MAX - 1, SEG_LEN_MAX, 129, 2000]
+    ss = [s] * (3 * SEG_LEN_MAX - 1 + 129) + [t, t, s, s] * 500          # the last: P, -P under t, then P, -P under s
+    out = _run_vs_oracle(c, group, ks, ss, lens, bf=np.array([0, 0, 1, 2, 0], np.uint32))
+    got = _aff(c, group, out)
+    assert got[0] is None and got[2] is None and got[4] is None and got[1] is not None and got[3] is not None
+
+
+@pytest.mark.parametrize("group,mode", CONFIGS, ids=CONFIG_IDS)
+def test_more_than_two_batches(ctx, plain_ctx, group, mode):
+    """k >= 2 x batch + 7 short segments, batch = SEG_BATCH_BYTES / (NWIN x PROJ_WORDS x 4): three launches of the batch loop, each with
+    its own seg0 and output offset over the same window-sum scratch; the host and the device form"""
+    import torch
+    c = _pick(ctx, plain_ctx, mode)
+    batch = SEG_BATCH_BYTES // (NWIN[(group, mode)] * PROJ_WORDS[group] * 4)
+    k = 2 * batch + 7
+    rs = np.random.RandomState(281 + group)
+    lens = rs.randint(0, 4, size=k)
+    check = [0, batch - 1, batch, batch + 1, 2 * batch, k - 1]
+    lens[check] = 3
+    off = _offsets(lens)
+    total = int(off[-1])
+    from bls12_381_amd import synthetic
+    kb, sb = synthetic.scalars(total, 291 + group), synthetic.scalars(total, 301 + group)
+    bases = c.bases_from_scalars(group, kb)
+    out = c.msm_segments(bases, sb, off)
+    got = _aff(c, group, out)
+    whole = _aff(c, group, c.msm(bases, sb))
+    assert _aff(c, group, c.point_sum(group, out)) == whole
+    assert whole == _gen_multiples(group, [synthetic.dot_mod_r(kb, sb)])
+    ks, ss = {}, {}
+    for j in check:
+        for i in range(int(off[j]), int(off[j + 1])):
+            ks[i] = int.from_bytes(kb[i].tobytes(), "little"); ss[i] = int.from_bytes(sb[i].tobytes(), "little")
+    want = _gen_multiples(group, [sum(ks[i] * ss[i] for i in range(int(off[j]), int(off[j + 1]))) for j in check])
+    assert [got[j] for j in check] == want
+    dev = torch.device("cuda", 0)
+    d_s = torch.from_numpy(sb).to(dev)
+    d_off = torch.from_numpy(off.view(np.int32)).to(dev)
+    d_out = torch.zeros((k, 18 if group == 1 else 36), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    c.msm_segments_device(bases, d_s.data_ptr(), d_off.data_ptr(), k, total, d_out.data_ptr())
+    c.synchronize()
+    dgot = _aff(c, group, d_out.cpu().numpy().view(np.uint64))
+    assert [dgot[j] for j in check] == want
+    assert dgot == got
+    bases.free()
+
+
+_BAD = [o.R_ORDER, o.R_ORDER + 1, (1 << 255) + 5, (1 << 256) - 1]
+
+
+@pytest.mark.parametrize("group,mode", CONFIGS, ids=CONFIG_IDS)
+def test_mont_device_form_at_the_edges(ctx, plain_ctx, group, mode):
+    """the boundary and carry values as `Scalar` limbs (fr_from_bytes_device -> msm_segments_device with SCALAR_MONT): the same points as
+    the byte form; bytes >= r and limbs >= r reported by synchronize() in each form, and a valid call afterwards is clean"""
+    import torch
+    import bls12_381_amd as b
+    c = _pick(ctx, plain_ctx, mode)
+    dev = torch.device("cuda", 0)
+    vals = _boundary_values(group) + _carry_values()
+    n = len(vals)
+    lens = [1] * n + [n]
+    off = _offsets(lens)
+    bf = np.array(list(range(n)) + [0], dtype=np.uint32)
+    ks = _rand(n, 311 + group)
+    bases = c.bases_from_scalars(group, _bytes(ks))
+    S = _bytes(vals + vals)
+    want = _aff(c, group, c.msm_segments(bases, S, off, base_first=bf))
+    assert want == _gen_multiples(group, _seg_exps(ks, vals + vals, off, bf))
+    d_bytes = torch.from_numpy(S).to(dev)
+    d_limbs = torch.zeros((2 * n, 4), dtype=torch.int64, device=dev)
+    d_off = torch.from_numpy(off.view(np.int32)).to(dev)
+    d_bf = torch.from_numpy(bf.view(np.int32)).to(dev)
+    d_out = torch.zeros((n + 1, 18 if group == 1 else 36), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    c.fr_from_bytes_device(d_bytes.data_ptr(), 2 * n, d_limbs.data_ptr())
+    run = lambda d_s: c.msm_segments_device(bases, d_s.data_ptr(), d_off.data_ptr(), n + 1, 2 * n, d_out.data_ptr(), d_base_first=d_bf.data_ptr())
+    c.set_scalar_form(b.api.SCALAR_MONT)
+    try:
+        run(d_limbs)
+        c.synchronize()
+        assert _aff(c, group, d_out.cpu().numpy().view(np.uint64)) == want
+        for v in _BAD:                                             # limbs >= r
+            bad = d_limbs.clone()
+            bad[n + 3] = torch.from_numpy(np.frombuffer(v.to_bytes(32, "little"), dtype=np.int64).copy()).to(dev)
+            torch.cuda.synchronize()
+            run(bad)
+            with pytest.raises(b.BlsGpuError, match="canonical"):
+                c.synchronize()
+        run(d_limbs)
+        c.synchronize()
+    finally:
+        c.set_scalar_form(b.api.SCALAR_BYTES)
+    for v in _BAD:                                                 # bytes >= r
+        bad = d_bytes.clone()
+        bad[5] = torch.from_numpy(np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint8).copy()).to(dev)
+        torch.cuda.synchronize()
+        run(bad)
+        with pytest.raises(b.BlsGpuError, match="canonical"):
+            c.synchronize()
+    d_out.zero_()
+    run(d_bytes)
+    c.synchronize()
+    assert _aff(c, group, d_out.cpu().numpy().view(np.uint64)) == want
+    bases.free()
