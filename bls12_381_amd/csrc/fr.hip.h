@@ -264,7 +264,7 @@ constexpr int FR_TILE_LOG = 10;                  // 1024 elements x 9 limbs = 36
 // is not in place).  Stages alternate R (sums kept unreduced) and F (sums reduced), see the bound table above.
 __global__ void __launch_bounds__(256, FR_TILE_WAVES) k_fr_tile(const u32* __restrict__ x, u32* __restrict__ y, const u32* __restrict__ tw, int log_n,
                                                  int tl, const u32* __restrict__ scale) {
-  extern __shared__ u32 lds[];                   // 2^tl elements, limb-interleaved: limb k of element e at lds[k * 2^tl + e]
+  BLS_DYN_LDS(lds);                   // 2^tl elements, limb-interleaved: limb k of element e at lds[k * 2^tl + e]
   const int T = 1 << tl;
   const size_t base = (size_t)blockIdx.x << tl;
   for (int e = threadIdx.x; e < T; e += blockDim.x) {
@@ -335,7 +335,7 @@ __global__ void __launch_bounds__(256, FR_TILE_WAVES) k_fr_tile(const u32* __res
 constexpr int FR_COLS_LOG = 12;                    // largest tile the host may ask for: 4096 elements x 9 limbs = 144 KB of the CU's 160 KB
 constexpr int FR_COLS_BLOCK = 1024;
 __global__ void __launch_bounds__(FR_COLS_BLOCK) k_fr_cols(const u32* src, u32* dst, const u32* __restrict__ tw, int lh_top, int d, int lk) {
-  extern __shared__ u32 lds[];
+  BLS_DYN_LDS(lds);
   const int T = 1 << (d + lk), K = 1 << lk;
   const int ls = lh_top - d + 1;
   const size_t lo = ((size_t)blockIdx.x & (((size_t)1 << (ls - lk)) - 1)) << lk;

@@ -471,7 +471,7 @@ __global__ void __launch_bounds__(256) k_bases_endo_g2(const u32* __restrict__ r
 template <int WORDS>
 __global__ void __launch_bounds__(SORT_THREADS) k_sort_hist(const u32* __restrict__ scalars, u32* __restrict__ ghist, int n, int c, int nwin,
                                                    int fine_bits, int ncoarse, int merged, u32* __restrict__ status) {
-  extern __shared__ u32 lh[];
+  BLS_DYN_LDS(lh);
   const int nc = (merged ? 1 : nwin) * ncoarse;
   for (int i = threadIdx.x; i < nc; i += SORT_THREADS) lh[i] = 0;
   __syncthreads();
@@ -516,7 +516,7 @@ template <int WORDS>
 __global__ void __launch_bounds__(SORT_THREADS) k_sort_scatter(const u32* __restrict__ scalars, const u32* __restrict__ gbase, u32* __restrict__ gcur,
                                                       u32* __restrict__ coarse_out, int n, int c, int nwin, int fine_bits, int ncoarse,
                                                       int merged, u32 stride) {
-  extern __shared__ u32 lh[];          // [nc] counts, then reused as running local ranks; [nc] bases
+  BLS_DYN_LDS(lh);          // [nc] counts, then reused as running local ranks; [nc] bases
   const int nc = (merged ? 1 : nwin) * ncoarse;
   u32* lbase = lh + nc;
   for (int i = threadIdx.x; i < nc; i += SORT_THREADS) lh[i] = 0;
@@ -1054,7 +1054,7 @@ __global__ void __launch_bounds__(256) k_tree_sum(const u32* __restrict__ E, u32
 template <class F>
 __global__ void __launch_bounds__(256) k_wsum_level_team(const u32* __restrict__ E, u32* __restrict__ Rout, u32* __restrict__ Tout,
                                                          int nseg, int n, int M, int off) {
-  extern __shared__ u32 team_lds[];
+  BLS_DYN_LDS(team_lds);
   __builtin_amdgcn_s_setprio(3);
   const int tl = threadIdx.x & (TEAM - 1);
   u32* mbox = team_lds + (threadIdx.x / TEAM) * TEAM_SLOTS * TeamTraits<F>::WORDS;
@@ -1080,7 +1080,7 @@ __global__ void __launch_bounds__(256) k_wsum_level_team(const u32* __restrict__
 template <class F>
 __global__ void __launch_bounds__(256) k_wsum_level_team2(const u32* __restrict__ E, u32* __restrict__ Rout, u32* __restrict__ Tout,
                                                           int nseg, int n, int M, int off) {
-  extern __shared__ u32 team_lds[];
+  BLS_DYN_LDS(team_lds);
   __builtin_amdgcn_s_setprio(3);
   constexpr int PW = Store<F>::PROJ_WORDS, W = TeamTraits<F>::WORDS;
   const int tl = threadIdx.x & (TEAM - 1);
@@ -1107,7 +1107,7 @@ __global__ void __launch_bounds__(256) k_wsum_level_team2(const u32* __restrict_
 }
 template <class F>
 __global__ void __launch_bounds__(256) k_tree_sum_team(const u32* __restrict__ E, u32* __restrict__ out, int nseg, int n, int M) {
-  extern __shared__ u32 team_lds[];
+  BLS_DYN_LDS(team_lds);
   __builtin_amdgcn_s_setprio(3);
   const int tl = threadIdx.x & (TEAM - 1);
   u32* mbox = team_lds + (threadIdx.x / TEAM) * TEAM_SLOTS * TeamTraits<F>::WORDS;
@@ -1138,7 +1138,7 @@ struct TreeJobs {
 };
 template <class F>
 __global__ void __launch_bounds__(256) k_tree_sum_team_multi(TreeJobs J) {
-  extern __shared__ u32 team_lds[];
+  BLS_DYN_LDS(team_lds);
   __builtin_amdgcn_s_setprio(3);
   const int tl = threadIdx.x & (TEAM - 1);
   u32* mbox = team_lds + (threadIdx.x / TEAM) * TEAM_SLOTS * TeamTraits<F>::WORDS;
@@ -1166,7 +1166,7 @@ __global__ void __launch_bounds__(256) k_tree_sum_team_multi(TreeJobs J) {
 }
 template <class F>
 __global__ void __launch_bounds__(256) k_shift_add_team(const u32* __restrict__ x, const u32* __restrict__ y, u32* __restrict__ out, int nseg, int k) {
-  extern __shared__ u32 team_lds[];
+  BLS_DYN_LDS(team_lds);
   __builtin_amdgcn_s_setprio(3);
   const int tl = threadIdx.x & (TEAM - 1);
   u32* mbox = team_lds + (threadIdx.x / TEAM) * TEAM_SLOTS * TeamTraits<F>::WORDS;
@@ -1184,7 +1184,7 @@ __global__ void __launch_bounds__(256) k_shift_add_team(const u32* __restrict__ 
 // (launch with a single block of TEAM threads)
 template <class F>
 __global__ void __launch_bounds__(64) k_msm_combine_team(const u32* __restrict__ wsums, u32* __restrict__ out, int nwin, int c) {
-  extern __shared__ u32 team_lds[];
+  BLS_DYN_LDS(team_lds);
   __builtin_amdgcn_s_setprio(3);
   const int tl = threadIdx.x & (TEAM - 1);
   u32* mbox = team_lds;
@@ -1200,7 +1200,7 @@ __global__ void __launch_bounds__(64) k_msm_combine_team(const u32* __restrict__
 // sum of n records by one team (cross-rank fold)
 template <class F>
 __global__ void __launch_bounds__(64) k_proj_sum_team(const u32* __restrict__ rec, u32* __restrict__ out, size_t n) {
-  extern __shared__ u32 team_lds[];
+  BLS_DYN_LDS(team_lds);
   const int tl = threadIdx.x & (TEAM - 1);
   Proj<F> acc = pt_identity<F>();
   for (size_t i = 0; i < n; i++) { Proj<F> p; load_proj<F>(rec + i * Store<F>::PROJ_WORDS, p); acc = pt_add_team<F>(acc, p, team_lds, tl); }

@@ -7,10 +7,7 @@
 #include <vector>
 
 thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuGroup g_emu_group;
-#if EMU_LANES > 8
-EmuQuadBarriers g_emu_quads;
-#endif
+EmuState g_emu;
 
 #include "pairing.hip.h"
 #ifdef EMU_WITH_QUAD

@@ -1,0 +1,181 @@
+"""Builds the MSM emulation library (tests/simt/emu_msm.cpp) and runs its entry points in a CHILD process (tests/test_simt_msm.py).
+
+The library is built with trapping bounds / shift checks, and every buffer the kernels read ends flush against an inaccessible page
+(emu_guarded), so a kernel bug ends the process that runs it: `run(jobs)` starts `python tests/simt_msm_child.py IN OUT` with the
+pickled jobs, under a time limit, and turns a signal, a time-out or a non-zero exit into a pytest failure that names the job.
+
+A job is a dict with "op" and "label"; the result list has one dict per job:
+  bases       group, xy (n, 12|24 u64 wire), inf (n u8) or None, [endo], [check]  -> rec, endo (u32 words), nbad
+  segments    bases (index of an earlier bases job), split, offsets, scalars (total, 8 u32), form, k, [base_first], [batch], [total],
+              [nbases]                                                            -> out (k, 18|36 u64), status, wsums (wire, last batch)
+  decompose   group, scalars (n, 8 u32), form                                     -> out (u32 words), status
+  accumulate  bases, nsplit, sorted, items (m, 3 u32), ctrl (4 u32), max_items, ndest, [bases2_endo]    -> records (ndest, 18 u64 wire)
+Test infrastructure only: the product never imports this file."""
+import ctypes
+import os
+import pickle
+import signal
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+LIB = os.path.join(ROOT, "build", "libemu_msm_test.so")
+AFF_WORDS = {1: 32, 2: 64}
+PROJ_WORDS = {1: 44, 2: 84}
+WIRE = {1: 6, 2: 12}                                               # u64 limbs per field element on the wire
+NWIN = {(1, 1): 32, (1, 0): 64, (2, 1): 16, (2, 0): 64}            # msm_seg.hip.h SegCfg::NWIN by (group, split)
+
+
+def build():
+    """build/libemu_msm_test.so, rebuilt when a source is newer (as the other emulation libraries are)"""
+    os.makedirs(os.path.dirname(LIB), exist_ok=True)
+    src = os.path.join(ROOT, "tests", "simt", "emu_msm.cpp")
+    csrc = os.path.join(ROOT, "bls12_381_amd", "csrc")
+    deps = [src, os.path.join(ROOT, "tests", "simt", "hip", "hip_runtime.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
+    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
+        tmp = LIB + ".tmp%d" % os.getpid()
+        subprocess.check_call([CLANG, "-O1", "-std=c++17", "-pthread", "-fPIC", "-shared", "-Wno-unused-value", "-Wno-psabi",
+                               "-fsanitize=bounds,shift", "-fsanitize-trap=all",
+                               "-I" + os.path.join(ROOT, "tests", "simt"), "-I" + csrc, src, "-o", tmp])
+        os.replace(tmp, LIB)
+    return LIB
+
+
+def run(jobs, timeout=300):
+    """the jobs in a fresh child process; returns their results or fails the calling test"""
+    import pytest
+    with tempfile.TemporaryDirectory() as d:
+        fin, fout = os.path.join(d, "in.pkl"), os.path.join(d, "out.pkl")
+        with open(fin, "wb") as fh:
+            pickle.dump(jobs, fh)
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=True)
+        except subprocess.TimeoutExpired as e:
+            err = e.stderr if isinstance(e.stderr, str) else (e.stderr or b"").decode()
+            pytest.fail("the emulation did not finish in %d s (a lane waiting for a partner that never comes?); last job: %s" % (timeout, _last_job(err)))
+        if p.returncode != 0:
+            what = "signal %s" % signal.Signals(-p.returncode).name if p.returncode < 0 else "exit status %d" % p.returncode
+            hint = {"SIGILL": " (a trapping bounds / shift check)", "SIGTRAP": " (a trapping bounds / shift check)",
+                    "SIGSEGV": " (an access outside a guarded buffer)"}.get(what.split()[-1], "")
+            pytest.fail("the emulation child ended with %s%s in job: %s\n%s" % (what, hint, _last_job(p.stderr), p.stderr[-2000:]))
+        with open(fout, "rb") as fh:
+            return pickle.load(fh)
+
+
+def _last_job(err):
+    marks = [l for l in (err or "").splitlines() if l.startswith("JOB ")]
+    return marks[-1][4:] if marks else "(none started)"
+
+
+# ---- child side --------------------------------------------------------------------------------------------------------------
+class _Child:
+    def __init__(self):
+        self.lib = ctypes.CDLL(LIB)
+        self.lib.emu_guarded.restype = ctypes.c_void_p
+        self.lib.emu_guarded.argtypes = [ctypes.c_size_t]
+        self.results = []
+
+    def guarded(self, a):
+        """a copy of the array that ends flush against an inaccessible page; returns its address (None for None)"""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        n = max(a.nbytes, 4)
+        p = self.lib.emu_guarded(n)
+        assert p, "emu_guarded failed"
+        if a.nbytes:
+            ctypes.memmove(p + n - a.nbytes, a.ctypes.data, a.nbytes)
+        return ctypes.c_void_p(p + n - a.nbytes)
+
+    def out(self, words):
+        """zeroed guarded u32 output buffer as a numpy view"""
+        n = max(words, 1) * 4
+        p = self.lib.emu_guarded(n)
+        buf = (ctypes.c_uint32 * max(words, 1)).from_address(p)
+        a = np.frombuffer(buf, dtype=np.uint32)
+        a[:] = 0
+        return a[:words] if words else a[:0], ctypes.c_void_p(p)
+
+    def bases(self, j):
+        g = j["group"]
+        xy = np.ascontiguousarray(j["xy"], dtype=np.uint64).reshape(-1, 2 * WIRE[g])
+        n = xy.shape[0]
+        rec, prec = self.out(n * AFF_WORDS[g])
+        inf = None if j.get("inf") is None else np.ascontiguousarray(j["inf"], dtype=np.uint8)
+        self.lib.emu_bases_import(g, self.guarded(xy), self.guarded(inf), prec, ctypes.c_size_t(n))
+        res = {"rec": rec.copy(), "n": n, "group": g, "endo": None, "nbad": None}
+        if j.get("check"):
+            bad, pbad = self.out(1)
+            self.lib.emu_bases_subgroup_check(g, self.guarded(rec), ctypes.c_size_t(n), pbad)
+            res["nbad"] = int(bad[0])
+        if j.get("endo"):
+            endo, pendo = self.out(n * AFF_WORDS[g] * (1 if g == 1 else 4))
+            self.lib.emu_bases_endo(g, self.guarded(rec), pendo, ctypes.c_size_t(n))
+            res["endo"] = endo.copy()
+        return res
+
+    def segments(self, j):
+        b = self.results[j["bases"]]
+        g, split = b["group"], int(j["split"])
+        k = int(j["k"])
+        batch = int(j.get("batch") or max(k, 1))
+        off = np.ascontiguousarray(j["offsets"], dtype=np.uint32)
+        s = np.ascontiguousarray(j["scalars"], dtype=np.uint32).reshape(-1, 8)
+        total = int(j["total"]) if j.get("total") is not None else s.shape[0]
+        nbases = int(j["nbases"]) if j.get("nbases") is not None else b["n"]
+        bf = None if j.get("base_first") is None else np.ascontiguousarray(j["base_first"], dtype=np.uint32)
+        nwin, pw, ww = NWIN[(g, split)], PROJ_WORDS[g], 2 * WIRE[g]
+        status, pstatus = self.out(1)
+        wsums, pws = self.out(batch * nwin * pw)
+        srec, psrec = self.out(batch * pw)
+        out, pout = self.out(k * 3 * ww)
+        endo = self.guarded(b["endo"]) if split else None
+        assert not split or b["endo"] is not None
+        self.lib.emu_msm_segments(g, split, self.guarded(b["rec"]), endo, ctypes.c_size_t(nbases), self.guarded(bf), self.guarded(off), self.guarded(s),
+                                  ctypes.c_size_t(k), ctypes.c_size_t(batch), ctypes.c_size_t(total), int(j["form"]), pstatus, pws, psrec, pout)
+        nlast = (k - 1) % batch + 1 if k else 0
+        wire, pwire = self.out(nlast * nwin * 3 * ww)
+        self.lib.emu_proj_export(g, self.guarded(wsums), pwire, ctypes.c_size_t(nlast * nwin))
+        return {"out": out.copy().view(np.uint64).reshape(k, 3 * WIRE[g]), "status": int(status[0]),
+                "wsums": wire.copy().view(np.uint64).reshape(nlast, nwin, 3 * WIRE[g])}
+
+    def decompose(self, j):
+        s = np.ascontiguousarray(j["scalars"], dtype=np.uint32).reshape(-1, 8)
+        n = s.shape[0]
+        out, pout = self.out(n * 8)
+        status, pstatus = self.out(1)
+        self.lib.emu_decompose(int(j["group"]), self.guarded(s), pout, n, pstatus, int(j["form"]))
+        return {"out": out.copy(), "status": int(status[0])}
+
+    def accumulate(self, j):
+        b = self.results[j["bases"]]
+        assert b["group"] == 1
+        items = np.ascontiguousarray(j["items"], dtype=np.uint32).reshape(-1, 3)
+        ndest = int(j["ndest"])
+        rec, prec = self.out(ndest * PROJ_WORDS[1])
+        bases2 = self.guarded(b["endo"]) if j.get("bases2_endo") else None
+        self.lib.emu_msm_accumulate_g1(self.guarded(b["rec"]), bases2, ctypes.c_uint32(int(j["nsplit"])), self.guarded(np.ascontiguousarray(j["sorted"], dtype=np.uint32)),
+                                       self.guarded(items), self.guarded(np.ascontiguousarray(j["ctrl"], dtype=np.uint32)), prec, ctypes.c_uint32(int(j["max_items"])))
+        wire, pwire = self.out(ndest * 36)
+        self.lib.emu_proj_export(1, self.guarded(rec), pwire, ctypes.c_size_t(ndest))
+        return {"records": wire.copy().view(np.uint64).reshape(ndest, 18)}
+
+
+def _main(fin, fout):
+    with open(fin, "rb") as fh:
+        jobs = pickle.load(fh)
+    c = _Child()
+    for i, j in enumerate(jobs):
+        sys.stderr.write("JOB %d %s: %s\n" % (i, j["op"], j.get("label", "")))
+        sys.stderr.flush()
+        c.results.append(getattr(c, j["op"])(j))
+    with open(fout, "wb") as fh:
+        pickle.dump(c.results, fh)
+
+
+if __name__ == "__main__":
+    _main(sys.argv[1], sys.argv[2])

@@ -10,6 +10,7 @@ import pytest
 
 from oracle import bls12_381_ref as o
 from oracle import c_oracle
+from msm_edge_values import boundary_values as _boundary_values, carry_values as _carry_values
 
 pytestmark = pytest.mark.gpu
 
@@ -385,32 +386,6 @@ def _run_vs_oracle(c, group, ks, ss, lens, bf=None, bases=None):
 def _rand(n, seed):
     r = o.SplitMix64(seed)
     return [r.scalar() for _ in range(n)]
-
-
-def _carry_values():
-    """scalars whose 4-bit signed recoding carries through long runs and across the window groups of plain mode (bits 64, 128, 192)
-    and of the GLV / psi sub-scalars, plus the top of the range [2^254, r): reduced mod r"""
-    rr = o.R_ORDER
-    v = []
-    for m in range(1, 64):
-        t = 1 << (4 * m)
-        v += [t - 1, t - 8, t - 9, t, t + 1, int("8" * m, 16), int("9" * m, 16)]
-    for b in (64, 128, 192):
-        for lo in (0x8, 0x9, 0xF):
-            for hi in (0x0, 0x7, 0x8, 0x9, 0xF):
-                v.append((lo << (b - 4)) | (hi << b))
-        v += [(1 << b) - 1 + (0x8 << b), int("8" * (b // 4), 16) + (0x9 << b), int("9" * (b // 4 + 1), 16), int("F" * (b // 4 + 2), 16),
-              (0x8 << (b - 4)) + (1 << (b - 4)) - 1, ((1 << 8) - 1) << (b - 4)]
-    for top in (4, 5, 6, 7):
-        t = top << 252
-        v += [t, t + 1, t + int("8" * 63, 16), t + int("9" * 63, 16), t + (1 << 252) - 1, t + (0x8 << 248), t + (0xF << 188) + (0x9 << 192)]
-    v += [rr - 1, rr - 8, rr - 9, rr - (1 << 128), (1 << 254) + (1 << 128) - 1]
-    return sorted({x % rr for x in v})
-
-
-def _boundary_values(group):
-    import decomp_model
-    return decomp_model.glv_candidates() if group == 1 else decomp_model.gls_candidates()
 
 
 @pytest.mark.parametrize("group,mode", CONFIGS, ids=CONFIG_IDS)

@@ -3,7 +3,12 @@
 The GPU box is where these kernels are timed and tested at size (tests/test_gpu_parity.py); this file lets the CPU suite run
 the very same device functions -- pair-lane and quad-lane towers, Miller loop, final exponentiation -- bit for bit against
 the oracle, so that a change in the tower code is checked before it ever reaches a GPU.  The emulation library is test
-infrastructure: it is built into build/ (git-ignored) from tests/simt/emu_pairing.cpp and is never loaded by the product."""
+infrastructure: it is built into build/ (git-ignored) from tests/simt/emu_pairing.cpp and is never loaded by the product.
+
+The MSM side has a host emulation of its own, built from tests/simt/emu_msm.cpp over the same stand-in header and checked by
+tests/test_simt_msm.py: the segmented MSM in its four instantiations, k_glv_decompose / k_gls_decompose, the endomorphism images,
+the subgroup check and k_msm_accumulate<FpPolicy>.  Not covered there yet: the sort / item-list / tail kernels of the large MSM
+(k_sort_*, k_item_*, k_wsum_*, k_tree_sum*, k_msm_heavy) and k_msm_accumulate_g2pair."""
 import ctypes
 import os
 import subprocess
