@@ -62,6 +62,22 @@ def _flags(f, n):
     return f
 
 
+FR_GENERATOR = 7                          # scalar.rs:99-105 GENERATOR (`MULTIPLICATIVE_GENERATOR` :708): the usual coset shift
+
+
+def _coset_limbs(coset):
+    """None | Python int in [1, r) | four Montgomery limbs -> four Montgomery limbs (np.uint64) or None"""
+    if coset is None:
+        return None
+    if isinstance(coset, (int, np.integer)):
+        g = int(coset)
+        if not 0 < g < R_ORDER:
+            raise ValueError("coset: an integer shift must be in [1, r)")
+        v = (g << 256) % R_ORDER
+        return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+    return _u64(coset, (4,)).copy()
+
+
 _R_WORDS = np.frombuffer(R_ORDER.to_bytes(32, "little"), dtype="<u8")
 SCALAR_BYTES, SCALAR_MONT = 0, 1          # include/bls12_381_hip.h: BLSGPU_SCALAR_BYTES / BLSGPU_SCALAR_MONT
 EXPAND_XMD_SHA256, EXPAND_XMD_SHA512, EXPAND_XOF_SHAKE128, EXPAND_XOF_SHAKE256 = 0, 1, 2, 3      # BLSGPU_EXPAND_*
@@ -595,6 +611,24 @@ class Context:
 
     def fr_ntt_device(self, d_ptr, log_n, inverse=False):
         check(self.lib.blsgpu_fr_ntt_device(self.h, d_ptr, log_n, 1 if inverse else 0), "fr_ntt_device")
+
+    def fr_ntt_many(self, values, inverse=False, coset=None):
+        """k independent transforms in one call: `values` is a (k, n, 4) u64 array of Montgomery limbs, n a power of two; returns a new
+        array.  coset: None, or the shift g as a Python int in [1, r) or four Montgomery limbs (FR_GENERATOR = 7 is the reference's):
+        forward gives the values on g * <w>, inverse takes them back (include/bls12_381_hip.h)."""
+        v = np.array(values, dtype=np.uint64)
+        if v.ndim != 3 or v.shape[2] != 4:
+            raise ValueError("fr_ntt_many: expected a (k, n, 4) array")
+        k, n = v.shape[0], v.shape[1]
+        if k and (n == 0 or n & (n - 1)):
+            raise ValueError("fr_ntt_many: the vector length must be a power of two")
+        v = np.ascontiguousarray(v)
+        check(self.lib.blsgpu_fr_ntt_many(self.h, _ptr(v), max(n.bit_length() - 1, 0), k, 1 if inverse else 0, _ptr(_coset_limbs(coset))), "fr_ntt_many")
+        return v
+
+    def fr_ntt_many_device(self, d_ptr, log_n, k, inverse=False, coset=None):
+        """the same on k * 2^log_n scalars in device memory, in place, asynchronous on the context's stream (`coset` stays a host value)"""
+        check(self.lib.blsgpu_fr_ntt_many_device(self.h, d_ptr, log_n, k, 1 if inverse else 0, _ptr(_coset_limbs(coset))), "fr_ntt_many_device")
 
     def fr_to_bytes(self, limbs, return_flags=False):
         """`Scalar::to_bytes` (scalar.rs:284-296) over (n, 4) u64 Montgomery limbs -> (n, 32) uint8; flags: limbs below r"""

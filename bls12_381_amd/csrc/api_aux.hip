@@ -2,6 +2,7 @@
 #define BLS_TU_NAME "api_aux.hip"
 #include "host.h"
 #include "fr.hip.h"
+#include "fr_plan.h"
 #include "h2c.hip.h"
 #include "expand_kernels.hip.h"
 #include "codec.hip.h"
@@ -254,14 +255,10 @@ static int fr_ntt_check(blsgpu_ctx* c, const void* data, int log_n) {
   if (log_n < 0 || log_n > 28) return bad("fr_ntt: log_n must be in [0, 28]");
   return BLSGPU_OK;
 }
-extern "C" int blsgpu_fr_ntt_device(blsgpu_ctx* c, void* d_data, int log_n, int inverse) { CTX_CLAIM(c);
-  if (int rc = fr_ntt_check(c, d_data, log_n)) return rc;
-  if (log_n == 0) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
+// the twiddle tables of (log_n, direction), built on first use and awaited by every user; fr_tw[dir] is reserved by the caller
+static int fr_twiddles_ready(blsgpu_ctx* c, int log_n, int dir) {
   hipStream_t st = c->stream;
-  const int dir = inverse ? 1 : 0;
-  const size_t n = (size_t)1 << log_n, half = n >> 1;
-  if (c->fr_tw[dir].reserve(n * 32) || c->fr_tmp.reserve(n * 32) || c->fr_ninv.reserve(64)) { g_err = "hipMalloc(fr scratch) failed"; return BLSGPU_ERR_HIP; }
+  const size_t half = ((size_t)1 << log_n) >> 1;
   if (c->fr_tw_log[dir] != log_n) {
     KLAUNCH(k_fr_twiddles, dim3(nblk((half + FR_TW_RUN - 1) / FR_TW_RUN, 256)), dim3(256), 0, st, c->fr_tw[dir].as<u32>(), log_n, dir);
     if (log_n > 1) KLAUNCH(k_fr_tw_levels, dim3(nblk(half, 256)), dim3(256), 0, st, c->fr_tw[dir].as<u32>(), log_n);
@@ -270,6 +267,39 @@ extern "C" int blsgpu_fr_ntt_device(blsgpu_ctx* c, void* d_data, int log_n, int 
     HIPCHK(hipEventRecord(c->ev_fr[dir], st));
   }
   HIPCHK(hipStreamWaitEvent(st, c->ev_fr[dir], 0));
+  return BLSGPU_OK;
+}
+// n^-1 (pre-scaled like the twiddles) in fr_ninv, likewise
+static int fr_ninv_ready(blsgpu_ctx* c, int log_n) {
+  hipStream_t st = c->stream;
+  if (c->fr_ninv_log != log_n) {
+    KLAUNCH(k_fr_ninv, dim3(1), dim3(64), 0, st, c->fr_ninv.as<u32>(), log_n); c->fr_ninv_log = log_n;
+    HIPCHK(hipEventRecord(c->ev_fr[2], st));
+  }
+  HIPCHK(hipStreamWaitEvent(st, c->ev_fr[2], 0));
+  return BLSGPU_OK;
+}
+// k_fr_cols needs 144 KB of dynamic LDS per workgroup (gfx950 has 160 KB per CU): asked for once per context
+static void fr_cols_probe(blsgpu_ctx* c) {
+  if (c->fr_cols_ok >= 0) return;
+  int lds_max = 0;
+  const size_t want = ((size_t)9 << FR_COLS_LOG) * 4;
+  c->fr_cols_ok = 0;
+  if (c->fr_cols_want && hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) == hipSuccess && (size_t)lds_max >= want &&
+      hipFuncSetAttribute((const void*)k_fr_cols<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess &&
+      hipFuncSetAttribute((const void*)k_fr_cols<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess)
+    c->fr_cols_ok = 1;
+  (void)hipGetLastError();
+}
+extern "C" int blsgpu_fr_ntt_device(blsgpu_ctx* c, void* d_data, int log_n, int inverse) { CTX_CLAIM(c);
+  if (int rc = fr_ntt_check(c, d_data, log_n)) return rc;
+  if (log_n == 0) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const int dir = inverse ? 1 : 0;
+  const size_t n = (size_t)1 << log_n;
+  if (c->fr_tw[dir].reserve(n * 32) || c->fr_tmp.reserve(n * 32) || c->fr_ninv.reserve(64)) { g_err = "hipMalloc(fr scratch) failed"; return BLSGPU_ERR_HIP; }
+  if (int rc = fr_twiddles_ready(c, log_n, dir)) return rc;
   u32* data = (u32*)d_data;
   u32* tmp = c->fr_tmp.as<u32>();
   const u32* tw = c->fr_tw[dir].as<u32>();
@@ -283,15 +313,7 @@ extern "C" int blsgpu_fr_ntt_device(blsgpu_ctx* c, void* d_data, int log_n, int 
   // round 5: the top log_n - tl stages on column tiles in LDS (k_fr_cols), at most ten stages per pass over the data; needs 144 KB of
   // dynamic LDS per workgroup (gfx950 has 160 KB per CU) -- the stage-pair passes below remain for a device that refuses it and as the
   // A/B twin (BLSGPU_NTT_IMPL=stage)
-  if (c->fr_cols_ok < 0) {
-    int lds_max = 0;
-    const size_t want = ((size_t)9 << FR_COLS_LOG) * 4;
-    c->fr_cols_ok = 0;
-    if (c->fr_cols_want && hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) == hipSuccess && (size_t)lds_max >= want &&
-        hipFuncSetAttribute((const void*)k_fr_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess)
-      c->fr_cols_ok = 1;
-    (void)hipGetLastError();
-  }
+  fr_cols_probe(c);
   // Measured on MI355X (tools/ntt_time.py): tiles of 2^11 elements, at most seven stages per pass, 512 lanes per workgroup (two workgroups
   // per CU overlap their load / barrier / store phases): 2.52-2.55 ms at 2^24 and 11.2 ms at 2^26 against 2.85-2.91 / 12.2-12.4 ms for the
   // stage-pair passes (-11 % / -10 %); at 2^20 and 2^22 the two are equal within the run-to-run spread (0.155-0.17 / 0.60-0.66 ms): the
@@ -307,27 +329,23 @@ extern "C" int blsgpu_fr_ntt_device(blsgpu_ctx* c, void* d_data, int log_n, int 
       const int d = (lh + 1 - tl + (passes - ps) - 1) / (passes - ps);      // the remaining stages split evenly over the remaining passes
       const int ls = lh - d + 1;
       const int lk = tlog - d < ls ? tlog - d : ls;
-      KLAUNCH(k_fr_cols, dim3((unsigned)(n >> (d + lk))), dim3(block), ((size_t)9 << (d + lk)) * 4, st, src, cur, tw, lh, d, lk);
+      KLAUNCH(k_fr_cols<false>, dim3((unsigned)(n >> (d + lk))), dim3(block), ((size_t)9 << (d + lk)) * 4, st, src, cur, tw, lh, d, lk, (const u32*)nullptr, log_n);
       src = cur; lh -= d;
     }
   }
   while (lh - 1 >= tl) {                                // two stages per pass over the data
-    KLAUNCH(k_fr_stage2, dim3(nblk(n / 4, 256)), dim3(256), 0, st, src, cur, tw, log_n, lh);
+    KLAUNCH(k_fr_stage2<false>, dim3(nblk(n / 4, 256)), dim3(256), 0, st, src, cur, tw, log_n, lh, n / 4, (const u32*)nullptr);
     src = cur; lh -= 2;
   }
-  if (lh >= tl) { KLAUNCH(k_fr_stage1, dim3(nblk(n / 2, 256)), dim3(256), 0, st, src, cur, tw, log_n, lh); src = cur; lh--; }
+  if (lh >= tl) { KLAUNCH(k_fr_stage1<false>, dim3(nblk(n / 2, 256)), dim3(256), 0, st, src, cur, tw, log_n, lh, n / 2, (const u32*)nullptr); src = cur; lh--; }
   LAUNCHCHK();
   const u32* scale = nullptr;
   if (inverse) {
-    if (c->fr_ninv_log != log_n) {
-      KLAUNCH(k_fr_ninv, dim3(1), dim3(64), 0, st, c->fr_ninv.as<u32>(), log_n); c->fr_ninv_log = log_n;
-      HIPCHK(hipEventRecord(c->ev_fr[2], st));
-    }
-    HIPCHK(hipStreamWaitEvent(st, c->ev_fr[2], 0));
+    if (int rc = fr_ninv_ready(c, log_n)) return rc;
     scale = c->fr_ninv.as<u32>();
   }
   u32* dst = src == data ? tmp : data;
-  KLAUNCH(k_fr_tile, dim3((unsigned)(n >> tl)), dim3(256), ((size_t)9 << tl) * 4, st, src, dst, tw, log_n, tl, scale);
+  KLAUNCH(k_fr_tile<false>, dim3((unsigned)(n >> tl)), dim3(256), ((size_t)9 << tl) * 4, st, src, dst, tw, log_n, tl, scale, n, (const u32*)nullptr, (const u32*)nullptr);
   LAUNCHCHK();
   if (dst != data) HIPCHK(hipMemcpyAsync(data, tmp, n * 32, hipMemcpyDeviceToDevice, st));
   return BLSGPU_OK;
@@ -338,6 +356,93 @@ extern "C" int blsgpu_fr_ntt(blsgpu_ctx* c, uint64_t* data, int log_n, int inver
   void* d = h.inout(c->io_a, data, ((size_t)1 << log_n) * 32);
   if (h.rc) return h.rc;
   return h.finish(blsgpu_fr_ntt_device(c, d, log_n, inverse));
+}
+// ---- k independent transforms in one call, optionally on a coset (fr_plan.h decides the launches) ----------------------------------------
+// every argument check of both forms: before any staging, reservation or launch
+static int fr_ntt_many_check(blsgpu_ctx* c, const void* data, int log_n, size_t k, const uint64_t* coset) {
+  if (!c || (k && !data)) return bad("fr_ntt_many: NULL argument");
+  if (log_n < 0 || log_n > 28) return bad("fr_ntt_many: log_n must be in [0, 28]");
+  if (k > (((size_t)1 << 28) >> log_n)) return bad("fr_ntt_many: k * 2^log_n must not exceed 2^28");
+  if (coset) {
+    if (!(coset[0] | coset[1] | coset[2] | coset[3])) return bad("fr_ntt_many: the coset shift must not be zero");
+    bool below = false;                              // the limbs as an integer against r, from the top word down
+    for (int i = 7; i >= 0; i--) {
+      const u32 w = (u32)(coset[i >> 1] >> (32 * (i & 1)));
+      if (w != FR_MOD_C.w[i]) { below = w < FR_MOD_C.w[i]; break; }
+    }
+    if (!below) return bad("fr_ntt_many: the coset shift is not a canonical Scalar (limbs >= r)");
+  }
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_ntt_many_device(blsgpu_ctx* c, void* d_data, int log_n, size_t k, int inverse, const uint64_t* coset) { CTX_CLAIM(c);
+  if (int rc = fr_ntt_many_check(c, d_data, log_n, k, coset)) return rc;
+  if (!k || log_n == 0) return BLSGPU_OK;             // the plan has no step for these (fr_plan.h): nothing to set up either
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const int dir = inverse ? 1 : 0;
+  const size_t n = (size_t)1 << log_n;
+  fr_cols_probe(c);
+  FrColsShape shape;
+  if (c->diag.ntt_cols[0]) { shape.tlog = c->diag.ntt_cols[0]; shape.dmax = c->diag.ntt_cols[1]; shape.block = c->diag.ntt_cols[2]; }
+  // the column-tile passes where the single transform takes them: per-vector size from 2^20 (api_aux.hip above), or forced
+  const FrPlan plan = fr_plan_many(log_n, k, inverse != 0, coset != nullptr, c->fr_cols_ok && (log_n >= 20 || c->fr_cols_want == 2), shape);
+  if (c->fr_tw[dir].reserve(n * 32) || c->fr_ninv.reserve(64) || (plan.needs_tmp && c->fr_tmp.reserve(plan.total * 32)) || (coset && c->fr_cs[dir].reserve(n * 32))) {
+    g_err = "hipMalloc(fr scratch) failed"; return BLSGPU_ERR_HIP;
+  }
+  if (int rc = fr_twiddles_ready(c, log_n, dir)) return rc;
+  const u32* cs = nullptr;
+  if (coset) {
+    if (c->fr_cs_log[dir] != log_n || memcmp(c->fr_cs_g[dir], coset, 32)) {
+      FrArg g;
+      for (int i = 0; i < 8; i++) g.w[i] = (u32)(coset[i >> 1] >> (32 * (i & 1)));
+      KLAUNCH(k_fr_coset_table, dim3(nblk((n + FR_TW_RUN - 1) / FR_TW_RUN, 256)), dim3(256), 0, st, c->fr_cs[dir].as<u32>(), g, log_n, dir);
+      LAUNCHCHK();
+      c->fr_cs_log[dir] = log_n; memcpy(c->fr_cs_g[dir], coset, 32);
+      HIPCHK(hipEventRecord(c->ev_fr_cs[dir], st));
+    }
+    HIPCHK(hipStreamWaitEvent(st, c->ev_fr_cs[dir], 0));
+    cs = c->fr_cs[dir].as<u32>();
+  }
+  const u32* scale = nullptr;
+  if (inverse && !coset) {
+    if (int rc = fr_ninv_ready(c, log_n)) return rc;
+    scale = c->fr_ninv.as<u32>();
+  }
+  u32* buf[2] = {(u32*)d_data, c->fr_tmp.as<u32>()};
+  const u32* tw = c->fr_tw[dir].as<u32>();
+  for (int i = 0; i < plan.n_steps; i++) {
+    const FrStep& s = plan.step[i];
+    const u32* src = buf[s.src];
+    u32* dst = buf[s.dst];
+    switch (s.kernel) {
+      case FR_K_COLS:
+        if (s.coset_in) KLAUNCH(k_fr_cols<true>, dim3(s.grid), dim3(s.block), s.lds, st, src, dst, tw, s.lh, s.d, s.lk, cs, log_n);
+        else KLAUNCH(k_fr_cols<false>, dim3(s.grid), dim3(s.block), s.lds, st, src, dst, tw, s.lh, s.d, s.lk, (const u32*)nullptr, log_n);
+        break;
+      case FR_K_STAGE2:
+        if (s.coset_in) KLAUNCH(k_fr_stage2<true>, dim3(s.grid), dim3(s.block), s.lds, st, src, dst, tw, log_n, s.lh, plan.total / 4, cs);
+        else KLAUNCH(k_fr_stage2<false>, dim3(s.grid), dim3(s.block), s.lds, st, src, dst, tw, log_n, s.lh, plan.total / 4, (const u32*)nullptr);
+        break;
+      case FR_K_STAGE1:
+        if (s.coset_in) KLAUNCH(k_fr_stage1<true>, dim3(s.grid), dim3(s.block), s.lds, st, src, dst, tw, log_n, s.lh, plan.total / 2, cs);
+        else KLAUNCH(k_fr_stage1<false>, dim3(s.grid), dim3(s.block), s.lds, st, src, dst, tw, log_n, s.lh, plan.total / 2, (const u32*)nullptr);
+        break;
+      default:
+        KLAUNCH(k_fr_tile<true>, dim3(s.grid), dim3(s.block), s.lds, st, src, dst, tw, log_n, s.d, scale, plan.total, s.coset_in ? cs : (const u32*)nullptr,
+                s.coset_out ? cs : (const u32*)nullptr);
+        break;
+    }
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_ntt_many(blsgpu_ctx* c, uint64_t* data, int log_n, size_t k, int inverse, const uint64_t* coset) { CTX_CLAIM(c);
+  if (int rc = fr_ntt_many_check(c, data, log_n, k, coset)) return rc;
+  if (!k) return BLSGPU_OK;
+  HostCall h(c);
+  void* d = h.inout(c->io_a, data, (k << log_n) * 32);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_ntt_many_device(c, d, log_n, k, inverse, coset));
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 // fr_ntt states the definition the kernels are tested against.
 #pragma once
 #include "scalar.hip.h"
+#include "fr_plan.h"
 
 namespace bls {
 
@@ -220,27 +221,39 @@ DEV Fr frl_canon(const FrL& a) { return fr_cond_sub(frl_pack(a), 0); }
 // k_fr_stage2 performs TWO consecutive stages (h and h/2) on four elements per lane.  Values in memory between
 // passes are in [0, 2r) (only the last kernel canonicalises).
 // (src and dst may be the same buffer: every lane reads its own elements before it writes them)
-__global__ void __launch_bounds__(256) k_fr_stage1(const u32* src, u32* x, const u32* __restrict__ tw, int log_n, int log_h) {
+// The butterfly blocks of 2^(log_h+1) elements and their twiddles are addressed by the offset inside the block, so the same kernels run
+// over k vectors of 2^log_n laid end to end: `lanes` = k 2^(log_n-1) (stage1) / k 2^(log_n-2) (stage2).  COSET: the pass is the first
+// one of a forward coset transform and multiplies element p by cs[p mod 2^log_n] = 2^5 g^(p mod n) as it loads it.
+// loaded A1 V2 x canonical table entry -> A1 V2, the bounds every stage expects of a loaded element
+// (one out-of-line copy of the product for all coset multiplications of a kernel: they are one per element next to ~10 butterflies)
+DEVNI FrL frl_mul_entry(const FrL& v, const u32* entry) { return frl_mul(v, frl_load(entry)); }
+template <bool COSET> DEV FrL frl_load_shifted(const u32* src, size_t p, const u32* cs, int log_n) {
+  FrL v = frl_load(src + p * 8);
+  if (COSET) v = frl_mul_entry(v, cs + (p & (((size_t)1 << log_n) - 1)) * 8);
+  return v;
+}
+template <bool COSET>
+__global__ void __launch_bounds__(256) k_fr_stage1(const u32* src, u32* x, const u32* __restrict__ tw, int log_n, int log_h, size_t lanes, const u32* __restrict__ cs) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t half = (size_t)1 << (log_n - 1);
-  if (t >= half) return;
+  if (t >= lanes) return;
   const size_t h = (size_t)1 << log_h;
   const size_t i = t & (h - 1), blk = t >> log_h;
   const size_t p = (blk << (log_h + 1)) + i;
-  FrL a = frl_load(src + p * 8), b = frl_load(src + (p + h) * 8);
+  FrL a = frl_load_shifted<COSET>(src, p, cs, log_n), b = frl_load_shifted<COSET>(src, p + h, cs, log_n);
   FrL w = frl_load(tw + (fr_tw_off(log_h) + i) * 8);
   fr_store(x + p * 8, frl_pack(frl_reduce(frl_add(a, b))));
   fr_store(x + (p + h) * 8, frl_pack(frl_mul(frl_sub<1>(a, b), w)));
 }
-__global__ void __launch_bounds__(256) k_fr_stage2(const u32* src, u32* x, const u32* __restrict__ tw, int log_n, int log_h) {
+template <bool COSET>
+__global__ void __launch_bounds__(256) k_fr_stage2(const u32* src, u32* x, const u32* __restrict__ tw, int log_n, int log_h, size_t lanes, const u32* __restrict__ cs) {
   // stages with half-spans h = 2^log_h and h/2; lane t owns elements p, p + h/2, p + h, p + 3h/2
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t quarter = (size_t)1 << (log_n - 2);
-  if (t >= quarter) return;
+  if (t >= lanes) return;
   const size_t q = (size_t)1 << (log_h - 1);           // h / 2
   const size_t i = t & (q - 1), blk = t >> (log_h - 1);
   const size_t p = (blk << (log_h + 1)) + i;
-  FrL a0 = frl_load(src + p * 8), a1 = frl_load(src + (p + q) * 8), a2 = frl_load(src + (p + 2 * q) * 8), a3 = frl_load(src + (p + 3 * q) * 8);
+  FrL a0 = frl_load_shifted<COSET>(src, p, cs, log_n), a1 = frl_load_shifted<COSET>(src, p + q, cs, log_n);
+  FrL a2 = frl_load_shifted<COSET>(src, p + 2 * q, cs, log_n), a3 = frl_load_shifted<COSET>(src, p + 3 * q, cs, log_n);
   FrL w0 = frl_load(tw + (fr_tw_off(log_h) + i) * 8), w1 = frl_load(tw + (fr_tw_off(log_h) + i + q) * 8);
   FrL w2 = frl_load(tw + (fr_tw_off(log_h - 1) + i) * 8);          // second stage: half-span q, same offset i
   // stage h (R): pairs (a0, a2), (a1, a3)
@@ -258,17 +271,35 @@ __global__ void __launch_bounds__(256) k_fr_stage2(const u32* src, u32* x, const
 #define FR_TILE_WAVES 4
 #endif
 constexpr int FR_TILE_LOG = 10;                  // 1024 elements x 9 limbs = 36 KB of LDS per workgroup
+static_assert(FR_TILE_LOG == FR_PLAN_TILE_LOG, "fr_plan.h and fr.hip.h disagree on the tile");
 // Runs the stages with half-spans 2^(tl-1) ... 1 on each aligned tile of 2^tl elements (tl = min(FR_TILE_LOG,
 // log_n)), then writes element p of the (bit-reversed) result to its natural position bitrev(p), optionally
 // scaled (the inverse transform's n^-1), in canonical form.  `x` is read, `y` written (they differ: the permutation
 // is not in place).  Stages alternate R (sums kept unreduced) and F (sums reduced), see the bound table above.
-__global__ void __launch_bounds__(256, FR_TILE_WAVES) k_fr_tile(const u32* __restrict__ x, u32* __restrict__ y, const u32* __restrict__ tw, int log_n,
-                                                 int tl, const u32* __restrict__ scale) {
+//
+// MANY (blsgpu_fr_ntt_many): the array is `total` = k 2^log_n elements, k vectors end to end, and a tile is 2^tl CONSECUTIVE elements of
+// it.  With log_n <= tl a tile is 2^(tl - log_n) whole vectors: the stage loop starts at half-span 2^(log_n-1) (the butterfly blocks of
+// 2^log_n elements tile the LDS array, the twiddle index is the offset inside the block), the last tile is guarded by `total`, and
+// the bit reversal stays inside the vector.  A workgroup that owns whole vectors has read all of them into LDS before its first store,
+// so in that case x == y is allowed (the transform runs in place); with log_n > tl the tile holds the low stages of part of a vector
+// and x != y as above.  cs_in: forward coset table, cs_in[j] = 2^5 g^j, multiplied in on the load; cs_out: inverse coset table,
+// cs_out[j] = 2^5 n^-1 g^-j, which takes the place of `scale` on the store of natural position j.
+template <bool MANY> struct FrTileArgs { typedef const u32* __restrict__ in; typedef u32* __restrict__ out; };
+template <> struct FrTileArgs<true> { typedef const u32* in; typedef u32* out; };
+template <bool MANY>
+__global__ void __launch_bounds__(256, FR_TILE_WAVES) k_fr_tile(typename FrTileArgs<MANY>::in x, typename FrTileArgs<MANY>::out y, const u32* __restrict__ tw, int log_n,
+                                                 int tl, const u32* __restrict__ scale, size_t total, const u32* __restrict__ cs_in, const u32* __restrict__ cs_out) {
   BLS_DYN_LDS(lds);                   // 2^tl elements, limb-interleaved: limb k of element e at lds[k * 2^tl + e]
   const int T = 1 << tl;
   const size_t base = (size_t)blockIdx.x << tl;
+  const size_t vmask = ((size_t)1 << log_n) - 1;                  // MANY: position inside the vector
   for (int e = threadIdx.x; e < T; e += blockDim.x) {
-    FrL v = frl_load(x + (base + e) * 8);
+    FrL v;
+    if (MANY && base + e >= total) { for (int k = 0; k < 9; k++) v.l[k] = 0; }      // past the last vector: zeros, never stored
+    else {
+      v = frl_load(x + (base + e) * 8);
+      if (MANY && cs_in) v = frl_mul_entry(v, cs_in + ((base + e) & vmask) * 8);      // A1 V2 x canonical 2^5 g^j -> A1 V2
+    }
 #pragma unroll
     for (int k = 0; k < 9; k++) lds[k * T + e] = v.l[k];
   }
@@ -276,7 +307,7 @@ __global__ void __launch_bounds__(256, FR_TILE_WAVES) k_fr_tile(const u32* __res
   // Two stages per round trip through LDS: lane t owns the four elements p, p + q, p + 2q, p + 3q (q = half-span of the second
   // stage) and runs an R stage (sums kept unreduced) and an F stage (sums reduced) on them in registers, exactly like
   // k_fr_stage2 -- half the LDS traffic and half the barriers of one stage per pass.  An odd tile depth leaves one R stage.
-  int lh = tl - 1;
+  int lh = (MANY && log_n < tl ? log_n : tl) - 1;
   for (; lh >= 1; lh -= 2) {
     const int q = 1 << (lh - 1);
     for (int t = threadIdx.x; t < T / 4; t += blockDim.x) {
@@ -313,13 +344,17 @@ __global__ void __launch_bounds__(256, FR_TILE_WAVES) k_fr_tile(const u32* __res
   FrL sc;
   if (scale) sc = frl_load(scale);
   for (int e = threadIdx.x; e < T; e += blockDim.x) {
+    const size_t p = base + e;
+    if (MANY && p >= total) break;
     FrL v;
 #pragma unroll
     for (int k = 0; k < 9; k++) v.l[k] = lds[k * T + e];
-    if (scale) v = frl_mul(v, sc);                // A <= 2 V <= 4 -> A1 V2
+    size_t r;
+    if (MANY) r = (p & ~vmask) | (size_t)(__brevll((unsigned long long)(p & vmask)) >> (64 - log_n));
+    else r = (size_t)(__brevll((unsigned long long)p) >> (64 - log_n));
+    if (MANY && cs_out) v = frl_mul_entry(v, cs_out + (r & vmask) * 8);      // A <= 2 V <= 4 x canonical 2^5 n^-1 g^-j -> A1 V2
+    else if (scale) v = frl_mul(v, sc);           // A <= 2 V <= 4 -> A1 V2
     else v = frl_reduce(v);
-    const size_t p = base + e;
-    const size_t r = (size_t)(__brevll((unsigned long long)p) >> (64 - log_n));
     fr_store(y + r * 8, frl_canon(v));
   }
 }
@@ -334,14 +369,16 @@ __global__ void __launch_bounds__(256, FR_TILE_WAVES) k_fr_tile(const u32* __res
 // Block b = (hi, chunk): hi = b >> (ls - lk) selects the aligned block of 2^(lh_top+1) elements, chunk the K columns inside a stride.
 constexpr int FR_COLS_LOG = 12;                    // largest tile the host may ask for: 4096 elements x 9 limbs = 144 KB of the CU's 160 KB
 constexpr int FR_COLS_BLOCK = 1024;
-__global__ void __launch_bounds__(FR_COLS_BLOCK) k_fr_cols(const u32* src, u32* dst, const u32* __restrict__ tw, int lh_top, int d, int lk) {
+// Block b addresses an aligned block of 2^(lh_top+1) elements, so k vectors end to end are k times the grid.  COSET: as for k_fr_stage1.
+template <bool COSET>
+__global__ void __launch_bounds__(FR_COLS_BLOCK) k_fr_cols(const u32* src, u32* dst, const u32* __restrict__ tw, int lh_top, int d, int lk, const u32* __restrict__ cs, int log_n) {
   BLS_DYN_LDS(lds);
   const int T = 1 << (d + lk), K = 1 << lk;
   const int ls = lh_top - d + 1;
   const size_t lo = ((size_t)blockIdx.x & (((size_t)1 << (ls - lk)) - 1)) << lk;
   const size_t base = (((size_t)blockIdx.x >> (ls - lk)) << (lh_top + 1)) + lo;
   for (int e = threadIdx.x; e < T; e += blockDim.x) {
-    FrL v = frl_load(src + (base + ((size_t)(e >> lk) << ls) + (e & (K - 1))) * 8);
+    FrL v = frl_load_shifted<COSET>(src, base + ((size_t)(e >> lk) << ls) + (e & (K - 1)), cs, log_n);
 #pragma unroll
     for (int k = 0; k < 9; k++) lds[k * T + e] = v.l[k];
   }
@@ -397,6 +434,33 @@ __global__ void k_fr_ninv(u32* __restrict__ out, int log_n) {
   for (int i = 0; i < log_n; i++) r = fr_mul(r, h);
   for (int k = 0; k < 5; k++) r = fr_add(r, r);               // pre-scaled by 2^5 like the twiddles
   fr_store(out, r);
+}
+
+
+// ---- coset tables of blsgpu_fr_ntt_many: cs[j] = 2^5 g^j (forward) or 2^5 n^-1 g^-j (inverse), j < n = 2^log_n ---------------------------
+// the run-walk of k_fr_twiddles: a lane starts from base^(64 t) (one short exponentiation; the inverse direction one inversion of g
+// first) and walks 64 consecutive powers.  Entries are canonical, pre-scaled by 2^5 like the twiddles (see frl_mul).
+struct FrArg { u32 w[8]; };                       // a `Scalar` passed by value (the coset shift is a parameter, not data)
+__global__ void __launch_bounds__(256) k_fr_coset_table(u32* __restrict__ cs, FrArg g, int log_n, int inverse) {
+  const size_t n = (size_t)1 << log_n;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t j0 = t * FR_TW_RUN;
+  if (j0 >= n) return;
+  Fr b;
+  for (int i = 0; i < 8; i++) b.l[i] = g.w[i];
+  Fr cur;
+  if (inverse) {
+    b = fr_inv(b);
+    constexpr FrWords k = {BLS_FR_TWO_INV_W};      // n^-1 = (2^-1)^log_n, as k_fr_ninv
+    Fr h;
+    for (int i = 0; i < 8; i++) h.l[i] = k.w[i];
+    cur = fr_pow_u64(b, (u64)j0);
+    for (int i = 0; i < log_n; i++) cur = fr_mul(cur, h);
+  } else {
+    cur = fr_pow_u64(b, (u64)j0);
+  }
+  for (int k = 0; k < 5; k++) cur = fr_add(cur, cur);
+  for (int k = 0; k < FR_TW_RUN && j0 + k < n; k++) { fr_store(cs + (j0 + k) * 8, cur); cur = fr_mul(cur, b); }
 }
 
 }  // namespace bls

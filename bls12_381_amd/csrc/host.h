@@ -213,6 +213,10 @@ struct blsgpu_ctx {
   int fr_cols_ok = -1;                  // k_fr_cols usable on this device (144 KB of dynamic LDS granted); decided at the first transform
   hipEvent_t ev_fr[3] = {};             // twiddles forward / inverse, n^-1: recorded where the table was built, awaited by every user
                                         // (the caller may have switched streams with blsgpu_set_stream in between)
+  DevBuf fr_cs[2];                      // blsgpu_fr_ntt_many: coset tables 2^5 g^j (forward) / 2^5 n^-1 g^-j (inverse) of the last (g, log_n) used
+  int fr_cs_log[2] = {-1, -1};
+  uint64_t fr_cs_g[2][4] = {};
+  hipEvent_t ev_fr_cs[2] = {};          // as ev_fr
 };
 
 static inline KTimer* ktimer_of(blsgpu_ctx* c) { return &c->ktimer; }

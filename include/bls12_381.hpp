@@ -331,6 +331,16 @@ inline void fr_ntt(std::vector<FrLimbs>& v, bool inverse = false) {         // n
   int log_n = 0; while (((size_t)1 << log_n) < v.size()) log_n++;
   check(blsgpu_fr_ntt(Context::instance().handle(), v[0].data(), log_n, inverse ? 1 : 0), "fr_ntt");
 }
+// k transforms of v.size() / k scalars each in one call (vector i = elements [i n, (i+1) n)); coset: the Montgomery limbs of a non-zero
+// shift g -- the values on g * <w> (forward) and back (inverse) -- or nullptr for the plain transform
+inline void fr_ntt_many(std::vector<FrLimbs>& v, size_t k, bool inverse = false, const FrLimbs* coset = nullptr) {
+  if (k == 0 && v.empty()) return;
+  if (k == 0 || v.empty() || v.size() % k) throw std::invalid_argument("fr_ntt_many: the length must be k vectors of equal size");
+  const size_t n = v.size() / k;
+  if (n & (n - 1)) throw std::invalid_argument("fr_ntt_many: the vector length must be a power of two");
+  int log_n = 0; while (((size_t)1 << log_n) < n) log_n++;
+  check(blsgpu_fr_ntt_many(Context::instance().handle(), v[0].data(), log_n, k, inverse ? 1 : 0, coset ? coset->data() : nullptr), "fr_ntt_many");
+}
 
 // The same operations sharded over several GPUs of one node from this process (blsgpu_group: one context + one host thread per
 // listed device; partial results folded with `Sum` / `MillerLoopResult + MillerLoopResult`, src/g1.rs:161-171, src/pairings.rs:179-186)

@@ -504,6 +504,20 @@ int blsgpu_fr_from_bytes_wide_device(blsgpu_ctx* ctx, const void* d_bytes, size_
  * log_n in [0, 28]. */
 int blsgpu_fr_ntt(blsgpu_ctx* ctx, uint64_t* data, int log_n, int inverse);
 int blsgpu_fr_ntt_device(blsgpu_ctx* ctx, void* d_data, int log_n, int inverse);
+/* k independent transforms of 2^log_n scalars each in ONE call, in place; vector v occupies scalars [v * 2^log_n, (v+1) * 2^log_n)
+ * of data (the producer side of blsgpu_g{1,2}_msm_segments: 256 polynomials of 4096 coefficients are one call, not 256).
+ * coset == NULL: each vector exactly as blsgpu_fr_ntt (limb-identical results).  coset = g, the four Montgomery limbs of a non-zero
+ * canonical Scalar -- a HOST pointer in both forms: it is a parameter, not data -- e.g. the reference's GENERATOR = 7
+ * (scalar.rs:99-105, `MULTIPLICATIVE_GENERATOR` :708):
+ *   forward  y[m] = sum_j x[j] g^j w^(jm)            (the values of the polynomial x on the coset g * <w>)
+ *   inverse  x[j] = g^-j n^-1 sum_m y[m] w^(-jm)     (so inverse(g) after forward(g) is the identity)
+ * w as for blsgpu_fr_ntt.  The shift is fused into the transform's own passes (no separate multiplication pass); its power table is
+ * built on the device and cached per (g, log_n, direction).  Inputs and outputs are canonical.  log_n in [0, 28],
+ * k * 2^log_n <= 2^28, k == 0 is a no-op.  d_data must be 16-byte aligned (the kernels read 16-byte words).  The device form is
+ * asynchronous on the context's stream.  BLSGPU_ERR_ARG (nothing staged or launched): NULL data with k > 0, log_n or k * 2^log_n out
+ * of range, a coset whose limbs are all zero or not below r. */
+int blsgpu_fr_ntt_many(blsgpu_ctx* ctx, uint64_t* data, int log_n, size_t k, int inverse, const uint64_t* coset);
+int blsgpu_fr_ntt_many_device(blsgpu_ctx* ctx, void* d_data, int log_n, size_t k, int inverse, const uint64_t* coset);
 
 /* ---- hash-to-curve (the step in front of multi_miller_loop in bulk signature checks) ---- */
 /* `<G as HashToCurve<ExpandMsgXmd<Sha256>>>::hash_to_curve(msg, dst)` / `encode_to_curve` (encode_only != 0) for n
