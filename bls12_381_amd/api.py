@@ -630,6 +630,44 @@ class Context:
         """the same on k * 2^log_n scalars in device memory, in place, asynchronous on the context's stream (`coset` stays a host value)"""
         check(self.lib.blsgpu_fr_ntt_many_device(self.h, d_ptr, log_n, k, 1 if inverse else 0, _ptr(_coset_limbs(coset))), "fr_ntt_many_device")
 
+    def g_ntt_many(self, group, points, inverse=False):
+        """k independent radix-2 transforms over GROUP elements in one call (include/bls12_381_hip.h: Y[m] = sum_j [w^(jm)] P[j], the w of
+        fr_ntt; the inverse turns a monomial SRS into its Lagrange form).  `points` is a (k, n, 18 | 36) u64 array of projective wire
+        points, or a pair (xy, infinity) of (k, n, 12 | 24) affine coordinates and (k, n) flags, lifted here to Z = 1 / Z = 0; n a power
+        of two.  Every point must lie in the prime-order subgroup.  Returns a new (k, n, 18 | 36) array."""
+        w = 18 if group == 1 else 36
+        c = w // 3
+        if isinstance(points, tuple):
+            xy, inf = points
+            xy = np.asarray(xy, dtype=np.uint64)
+            if xy.ndim != 3 or xy.shape[2] != 2 * c:
+                raise ValueError("g_ntt_many: expected (k, n, %d) affine coordinates" % (2 * c))
+            flags = np.zeros(xy.shape[:2], dtype=bool) if inf is None else np.asarray(inf).astype(bool)
+            if flags.shape != xy.shape[:2]:
+                raise ValueError("g_ntt_many: the infinity flags must be a (k, n) array")
+            v = np.zeros(xy.shape[:2] + (w,), dtype=np.uint64)
+            v[:, :, :2 * c] = xy
+            v[:, :, 2 * c:2 * c + 6] = fp_to_limbs(1)
+            v[flags] = 0
+            v[flags, c:c + 6] = fp_to_limbs(1)                   # (0 : 1 : 0)
+        else:
+            v = np.array(points, dtype=np.uint64)
+            if v.ndim != 3 or v.shape[2] != w:
+                raise ValueError("g_ntt_many: expected a (k, n, %d) array" % w)
+        k, n = v.shape[0], v.shape[1]
+        if k and (n == 0 or n & (n - 1)):
+            raise ValueError("g_ntt_many: the vector length must be a power of two")
+        v = np.ascontiguousarray(v)
+        fn = self.lib.blsgpu_g1_ntt_many if group == 1 else self.lib.blsgpu_g2_ntt_many
+        check(fn(self.h, _ptr(v), max(n.bit_length() - 1, 0), k, 1 if inverse else 0), "g_ntt_many")
+        return v
+
+    def g_ntt_many_device(self, group, d_ptr, log_n, k, inverse=False):
+        """the same on k * 2^log_n projective wire points in device memory (16-byte aligned), in place, asynchronous on the context's stream:
+        mul_batch_device -> g_ntt_many_device -> batch_normalize_device -> bases_from_device needs no host copy"""
+        fn = self.lib.blsgpu_g1_ntt_many_device if group == 1 else self.lib.blsgpu_g2_ntt_many_device
+        check(fn(self.h, ctypes.c_void_p(d_ptr) if d_ptr else None, log_n, k, 1 if inverse else 0), "g_ntt_many_device")
+
     def fr_to_bytes(self, limbs, return_flags=False):
         """`Scalar::to_bytes` (scalar.rs:284-296) over (n, 4) u64 Montgomery limbs -> (n, 32) uint8; flags: limbs below r"""
         a = _u64(limbs, (-1, 4))

@@ -256,7 +256,8 @@ static int fr_ntt_check(blsgpu_ctx* c, const void* data, int log_n) {
   return BLSGPU_OK;
 }
 // the twiddle tables of (log_n, direction), built on first use and awaited by every user; fr_tw[dir] is reserved by the caller
-static int fr_twiddles_ready(blsgpu_ctx* c, int log_n, int dir) {
+// (declared in host.h: the group transforms of api_msm.hip read the same tables)
+int fr_twiddles_ready(blsgpu_ctx* c, int log_n, int dir) {
   hipStream_t st = c->stream;
   const size_t half = ((size_t)1 << log_n) >> 1;
   if (c->fr_tw_log[dir] != log_n) {
@@ -270,7 +271,7 @@ static int fr_twiddles_ready(blsgpu_ctx* c, int log_n, int dir) {
   return BLSGPU_OK;
 }
 // n^-1 (pre-scaled like the twiddles) in fr_ninv, likewise
-static int fr_ninv_ready(blsgpu_ctx* c, int log_n) {
+int fr_ninv_ready(blsgpu_ctx* c, int log_n) {
   hipStream_t st = c->stream;
   if (c->fr_ninv_log != log_n) {
     KLAUNCH(k_fr_ninv, dim3(1), dim3(64), 0, st, c->fr_ninv.as<u32>(), log_n); c->fr_ninv_log = log_n;

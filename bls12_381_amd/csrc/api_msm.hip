@@ -4,6 +4,7 @@
 #include "abi_kernels.hip.h"
 #include "mulbatch.hip.h"
 #include "msm_seg.hip.h"
+#include "gntt.hip.h"
 
 // ---------------------------------------------------------------------------------------------------
 // bases
@@ -849,6 +850,59 @@ extern "C" int blsgpu_g1_mul_batch_mont_device(blsgpu_ctx* c, const void* xy, co
   ScalarFormScope f(c, SCALAR_MONT); return mul_batch_device<FpPolicy>(c, xy, inf, s, n, out); }
 extern "C" int blsgpu_g2_mul_batch_mont_device(blsgpu_ctx* c, const void* xy, const void* inf, const void* s, size_t n, void* out) { CTX_CLAIM(c);
   ScalarFormScope f(c, SCALAR_MONT); return mul_batch_device<Fp2PairPolicy>(c, xy, inf, s, n, out); }
+
+// ---------------------------------------------------------------------------------------------------
+// group transforms (gntt.hip.h; gntt_plan.h decides the launches): k vectors of 2^log_n projective wire points, in place
+// ---------------------------------------------------------------------------------------------------
+// every argument check of both forms: before any staging, reservation or launch
+static int g_ntt_check(blsgpu_ctx* c, const void* xyz, int log_n, size_t k, bool device) {
+  if (!c || (k && !xyz)) return bad("g_ntt_many: NULL argument");
+  if (log_n < 0 || log_n > GNTT_MAX_LOG) return bad("g_ntt_many: log_n must be in [0, 24]");
+  if (k > (((size_t)1 << GNTT_MAX_LOG) >> log_n)) return bad("g_ntt_many: k * 2^log_n must not exceed 2^24");
+  if (device && ((uintptr_t)xyz & 15)) return bad("g_ntt_many_device: d_xyz must be 16-byte aligned");
+  return BLSGPU_OK;
+}
+template <class LaneS, class TeamS>
+static int g_ntt_many_device(blsgpu_ctx* c, void* d_xyz, int log_n, size_t k, int inverse) {
+  if (int rc = g_ntt_check(c, d_xyz, log_n, k, true)) return rc;
+  const GnPlan plan = gntt_plan_many(LaneS::GROUP, log_n, k, c->diag.gntt_team_max);
+  if (!plan.n_steps) return BLSGPU_OK;                 // k == 0 or log_n == 0: nothing to set up either
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const int dir = inverse ? 1 : 0;
+  // the tables are the Fr transform's own (api_aux.hip), cached per (log_n, direction); the points are transformed in place, so the
+  // call shares no scratch with an MSM in flight
+  if (c->fr_tw[dir].reserve(((size_t)1 << log_n) * 32) || c->fr_ninv.reserve(64)) { g_err = "hipMalloc(fr scratch) failed"; return BLSGPU_ERR_HIP; }
+  if (int rc = fr_twiddles_ready(c, log_n, dir)) return rc;
+  const u32* ninv = nullptr;
+  if (inverse) {
+    if (int rc = fr_ninv_ready(c, log_n)) return rc;
+    ninv = c->fr_ninv.as<u32>();
+  }
+  const u32* tw = c->fr_tw[dir].as<u32>();
+  u32* x = (u32*)d_xyz;
+  for (int i = 0; i < plan.n_steps; i++) {
+    const GnStep& s = plan.step[i];
+    if (s.kernel == GN_K_PERMUTE) KLAUNCH(k_gntt_permute<LaneS::IO::WW>, dim3(s.grid), dim3(s.block), s.lds, st, x, log_n, plan.total);
+    else if (s.shape == GN_TEAM) KLAUNCH(k_gntt_stage<TeamS>, dim3(s.grid), dim3(s.block), s.lds, st, x, tw, s.stage ? nullptr : ninv, s.stage, plan.butterflies);
+    else KLAUNCH(k_gntt_stage<LaneS>, dim3(s.grid), dim3(s.block), s.lds, st, x, tw, s.stage ? nullptr : ninv, s.stage, plan.butterflies);
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+template <class LaneS, class TeamS>
+static int g_ntt_many_host(blsgpu_ctx* c, uint64_t* xyz, int log_n, size_t k, int inverse) {
+  if (int rc = g_ntt_check(c, xyz, log_n, k, false)) return rc;
+  if (!k) return BLSGPU_OK;
+  HostCall h(c);
+  void* d = h.inout(c->io_a, xyz, (k << log_n) * 3 * LaneS::IO::WW * 4);
+  if (h.rc) return h.rc;
+  return h.finish(g_ntt_many_device<LaneS, TeamS>(c, d, log_n, k, inverse));
+}
+extern "C" int blsgpu_g1_ntt_many(blsgpu_ctx* c, uint64_t* xyz, int log_n, size_t k, int inverse) { CTX_CLAIM(c); return g_ntt_many_host<GnG1Lane, GnG1Team>(c, xyz, log_n, k, inverse); }
+extern "C" int blsgpu_g2_ntt_many(blsgpu_ctx* c, uint64_t* xyz, int log_n, size_t k, int inverse) { CTX_CLAIM(c); return g_ntt_many_host<GnG2Lane, GnG2Team>(c, xyz, log_n, k, inverse); }
+extern "C" int blsgpu_g1_ntt_many_device(blsgpu_ctx* c, void* d_xyz, int log_n, size_t k, int inverse) { CTX_CLAIM(c); return g_ntt_many_device<GnG1Lane, GnG1Team>(c, d_xyz, log_n, k, inverse); }
+extern "C" int blsgpu_g2_ntt_many_device(blsgpu_ctx* c, void* d_xyz, int log_n, size_t k, int inverse) { CTX_CLAIM(c); return g_ntt_many_device<GnG2Lane, GnG2Team>(c, d_xyz, log_n, k, inverse); }
 
 // ---------------------------------------------------------------------------------------------------
 // group helpers

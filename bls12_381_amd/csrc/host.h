@@ -2,7 +2,8 @@
 // per-kernel timing wrapper, and the declarations of the few functions that cross translation units.  No kernels here.
 //
 //   api_ctx.hip      contexts, streams, status, diagnostics, staged uploads, field / point self-test hooks
-//   api_msm.hip      resident bases, MSM, batched scalar multiplication, sums, batch_normalize        (msm.hip.h, mulbatch.hip.h)
+//   api_msm.hip      resident bases, MSM, batched scalar multiplication, sums, batch_normalize,       (msm.hip.h, mulbatch.hip.h,
+//                    group transforms                                                                   gntt.hip.h)
 //   api_pairing.hip  pairings, Miller loops, G2Prepared, final exponentiation, Gt, Fp6 / Fp12 hooks   (pairing / quad / prep / wide)
 //   api_aux.hip      Fr vectors and transform, hash-to-curve, point codecs, bulk BLS verification      (fr / h2c / codec)
 //   api_group.hip    device groups: one process driving several GPUs (host code only)
@@ -256,6 +257,8 @@ struct blsgpu_g2_prepared { int device = 0; size_t n = 0; u32* tab = nullptr; ui
 // ---- functions that cross translation units -------------------------------------------------------------------------------------
 int staged_upload(blsgpu_ctx* c, void* dst, const void* src, size_t bytes);      // api_ctx.hip
 void acc_harvest(blsgpu_ctx* c, bool wait);                                       // api_ctx.hip (MSM accumulation timings)
+int fr_twiddles_ready(blsgpu_ctx* c, int log_n, int dir);                        // api_aux.hip: the Fr twiddle table of (log_n, direction) in fr_tw[dir], which the caller reserved
+int fr_ninv_ready(blsgpu_ctx* c, int log_n);                                      // api_aux.hip: 2^5 n^-1 in fr_ninv, likewise
 
 // ---- host-pointer entry points ------------------------------------------------------------------------------------------------
 // Every host-pointer entry point is  check -> stage -> device core -> finish:  it runs the argument check of its operation, stages its

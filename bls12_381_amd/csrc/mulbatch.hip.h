@@ -85,20 +85,35 @@ k_mul_batch(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, const u
   MbIO<F>::save(acc.x, o); MbIO<F>::save(acc.y, o + WW); MbIO<F>::save(acc.z, o + 2 * WW);
 }
 
-// G1 fast path for points the caller vouches for (prime-order subgroup: blsgpu_set_assume_subgroup): the GLV split of the MSM
+// ---- the endomorphism ladders as device functions -----------------------------------------------------------------------------------
+// A ladder is written over the point operations `Ops` supplies: MbLaneOps is one point per lane (G1) or lane pair (G2,
+// pairlane.hip.h), the complete formulas of curve.hip.h; gntt.hip.h also runs the same ladders on a team of eight lanes
+// (team.hip.h).  The sequence of point operations does not depend on Ops, so every caller gets the same projective triple.
+template <class F> struct MbLaneOps {
+  DEV Proj<F> add(const Proj<F>& a, const Proj<F>& b) const { return pt_add<F>(a, b); }
+  DEV Proj<F> dbl(const Proj<F>& a) const { return pt_double<F>(a); }
+};
+// table [1..8] P: 4 doublings + 3 additions
+template <class F, class Ops>
+DEV void mb_table(const Proj<F>& p, Proj<F>* tab, const Ops& op) {
+  tab[0] = p;
+  tab[1] = op.dbl(p);
+  tab[2] = op.add(tab[1], p);
+  tab[3] = op.dbl(tab[1]);
+  tab[4] = op.add(tab[3], p);
+  tab[5] = op.dbl(tab[2]);
+  tab[6] = op.add(tab[5], p);
+  tab[7] = op.dbl(tab[3]);
+}
+
+// G1, points of the prime-order subgroup: the GLV split of the MSM
 // (msm.hip.h glv_split: k P = +-|k1| P -+ |k2| phi(P) with 127-bit halves, phi(X : Y : Z) = (BETA X : Y : Z), g1.rs:421-437) turns
 // the 64 windows into 32 with TWO additions each over ONE table -- the image of a table entry is one multiplication by BETA:
 // 128 doublings x 8 + 67 additions x 12 + 32 = 1 860 field multiplications against 2 852.  Outside the subgroup phi(P) is not
-// -[z^2] P, so unverified inputs keep the kernel above.
-__global__ void __launch_bounds__(256, 2)
-k_mul_batch_glv(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, const u32* __restrict__ scalars, u32* __restrict__ out, size_t n,
-                u32* __restrict__ status, int form) {
+// -[z^2] P.  s: the canonical scalar, eight words.
+template <class Ops>
+DEV Proj<FpPolicy> mb_ladder_glv(const u32* s, const Proj<FpPolicy>& p, const Ops& op) {
   typedef FpPolicy F;
-  constexpr int WW = 12;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  u32 s[8];
-  if (!scalar_load(scalars, i, form, s)) atomicOr(status, 1u);
   u32 h[2][4];
   glv_split(s, h[0], h[1]);
   const u32 flip[2] = {h[0][3] >> 31, h[1][3] >> 31};        // the whole term is subtracted
@@ -120,24 +135,12 @@ k_mul_batch_glv(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, con
     }
   }
   Proj<F> tab[8];
-  {
-    Proj<F> p;
-    p.x = MbIO<F>::load(xy + i * 2 * WW); p.y = MbIO<F>::load(xy + i * 2 * WW + WW);
-    p.z = (inf && inf[i]) ? F::zero() : F::one();
-    tab[0] = p;
-    tab[1] = pt_double<F>(p);
-    tab[2] = pt_add<F>(tab[1], p);
-    tab[3] = pt_double<F>(tab[1]);
-    tab[4] = pt_add<F>(tab[3], p);
-    tab[5] = pt_double<F>(tab[2]);
-    tab[6] = pt_add<F>(tab[5], p);
-    tab[7] = pt_double<F>(tab[3]);
-  }
+  mb_table<F>(p, tab, op);
   constexpr PLimbs kb = {BLS_BETA};
   Proj<F> acc = pt_identity<F>();
 #pragma nounroll
   for (int w = 31; w >= 0; w--) {
-    if (w != 31) { acc = pt_double<F>(acc); acc = pt_double<F>(acc); acc = pt_double<F>(acc); acc = pt_double<F>(acc); }
+    if (w != 31) { acc = op.dbl(acc); acc = op.dbl(acc); acc = op.dbl(acc); acc = op.dbl(acc); }
 #pragma unroll
     for (int j = 0; j < 2; j++) {
       const u32 d = (mag[j][w >> 3] >> ((w & 7) * 4)) & 15u;
@@ -146,26 +149,19 @@ k_mul_batch_glv(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, con
       if (!d) t = pt_identity<F>();
       if (j) t.x = F::st(mul(t.x, fe1_const(kb)));
       t.y = select(neg_d, F::st(neg(t.y)), t.y);
-      acc = pt_add<F>(acc, t);
+      acc = op.add(acc, t);
     }
   }
-  u32* o = out + i * 3 * WW;
-  MbIO<F>::save(acc.x, o); MbIO<F>::save(acc.y, o + WW); MbIO<F>::save(acc.z, o + 2 * WW);
+  return acc;
 }
 
-// G2 fast path for vouched points: the four-dimensional split of the MSM (msm.hip.h gls_split: k P = d0 P - d1 psi(P) + d2 psi^2(P) -
+// G2, points of the prime-order subgroup: the four-dimensional split of the MSM (msm.hip.h gls_split: k P = d0 P - d1 psi(P) + d2 psi^2(P) -
 // d3 psi^3(P) with |d_j| < 2^63, psi = the untwist-Frobenius-twist endomorphism of g2.rs:847-912) turns the 64 windows into 16 with FOUR
 // additions each over ONE table -- the image of a table entry under psi^j is two multiplications by constants and conjugations:
-// 64 doublings + 71 additions instead of 256 + 67.  One multiplication per lane pair (pairlane.hip.h), like k_mul_batch<Fp2PairPolicy>.
-__global__ void __launch_bounds__(256, 2)
-k_mul_batch_gls(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, const u32* __restrict__ scalars, u32* __restrict__ out, size_t n,
-                u32* __restrict__ status, int form) {
-  typedef Fp2PairPolicy F;
-  constexpr int WW = 24;
-  const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / 2;
-  if (i >= n) return;
-  u32 k[10];
-  if (!scalar_load(scalars, i, form, k)) atomicOr(status, 1u);
+// 64 doublings + 71 additions instead of 256 + 67.  F is Fp2PairPolicy (a lane pair per point) or Fp2Policy (whole elements per lane).
+// k: TEN words, the canonical scalar in k[0..7], clobbered.
+template <class F, class Ops>
+DEV Proj<F> mb_ladder_gls(u32* k, const Proj<F>& p, const Ops& op) {
   k[8] = 0; k[9] = 0;
   u64 dg[4]; u32 flip[4];
   gls_split(k, dg, flip);
@@ -189,23 +185,11 @@ k_mul_batch_gls(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, con
 #pragma unroll
   for (int j = 0; j < 4; j++) magp[j] = (u64)mag[j][0] | ((u64)mag[j][1] << 32);
   Proj<F> tab[8];
-  {
-    Proj<F> p;
-    p.x = MbIO<F>::load(xy + i * 2 * WW); p.y = MbIO<F>::load(xy + i * 2 * WW + WW);
-    p.z = (inf && inf[i]) ? F::zero() : F::one();
-    tab[0] = p;
-    tab[1] = pt_double<F>(p);
-    tab[2] = pt_add<F>(tab[1], p);
-    tab[3] = pt_double<F>(tab[1]);
-    tab[4] = pt_add<F>(tab[3], p);
-    tab[5] = pt_double<F>(tab[2]);
-    tab[6] = pt_add<F>(tab[5], p);
-    tab[7] = pt_double<F>(tab[3]);
-  }
+  mb_table<F>(p, tab, op);
   Proj<F> acc = pt_identity<F>();
 #pragma nounroll
   for (int w = 15; w >= 0; w--) {
-    if (w != 15) { acc = pt_double<F>(acc); acc = pt_double<F>(acc); acc = pt_double<F>(acc); acc = pt_double<F>(acc); }
+    if (w != 15) { acc = op.dbl(acc); acc = op.dbl(acc); acc = op.dbl(acc); acc = op.dbl(acc); }
 #pragma nounroll
     for (int j = 0; j < 4; j++) {
       const u32 d = (u32)(magp[j] >> (4 * w)) & 15u;
@@ -215,9 +199,45 @@ k_mul_batch_gls(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, con
       if (j & 1) t = pt_psi<F>(t);
       if (j & 2) t = pt_psi2<F>(t);
       t.y = select(neg_d, F::st(neg(t.y)), t.y);
-      acc = pt_add<F>(acc, t);
+      acc = op.add(acc, t);
     }
   }
+  return acc;
+}
+
+// G1 fast path for points the caller vouches for (prime-order subgroup: blsgpu_set_assume_subgroup): mb_ladder_glv, one
+// multiplication per lane.  Unverified inputs keep the kernel above.
+__global__ void __launch_bounds__(256, 2)
+k_mul_batch_glv(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, const u32* __restrict__ scalars, u32* __restrict__ out, size_t n,
+                u32* __restrict__ status, int form) {
+  typedef FpPolicy F;
+  constexpr int WW = 12;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 s[8];
+  if (!scalar_load(scalars, i, form, s)) atomicOr(status, 1u);
+  Proj<F> p;
+  p.x = MbIO<F>::load(xy + i * 2 * WW); p.y = MbIO<F>::load(xy + i * 2 * WW + WW);
+  p.z = (inf && inf[i]) ? F::zero() : F::one();
+  const Proj<F> acc = mb_ladder_glv(s, p, MbLaneOps<F>());
+  u32* o = out + i * 3 * WW;
+  MbIO<F>::save(acc.x, o); MbIO<F>::save(acc.y, o + WW); MbIO<F>::save(acc.z, o + 2 * WW);
+}
+
+// G2 fast path for vouched points: mb_ladder_gls, one multiplication per lane pair (pairlane.hip.h), like k_mul_batch<Fp2PairPolicy>.
+__global__ void __launch_bounds__(256, 2)
+k_mul_batch_gls(const u32* __restrict__ xy, const uint8_t* __restrict__ inf, const u32* __restrict__ scalars, u32* __restrict__ out, size_t n,
+                u32* __restrict__ status, int form) {
+  typedef Fp2PairPolicy F;
+  constexpr int WW = 24;
+  const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / 2;
+  if (i >= n) return;
+  u32 k[10];
+  if (!scalar_load(scalars, i, form, k)) atomicOr(status, 1u);
+  Proj<F> p;
+  p.x = MbIO<F>::load(xy + i * 2 * WW); p.y = MbIO<F>::load(xy + i * 2 * WW + WW);
+  p.z = (inf && inf[i]) ? F::zero() : F::one();
+  const Proj<F> acc = mb_ladder_gls<F>(k, p, MbLaneOps<F>());
   u32* o = out + i * 3 * WW;
   MbIO<F>::save(acc.x, o); MbIO<F>::save(acc.y, o + WW); MbIO<F>::save(acc.z, o + 2 * WW);
 }

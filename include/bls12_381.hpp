@@ -341,6 +341,35 @@ inline void fr_ntt_many(std::vector<FrLimbs>& v, size_t k, bool inverse = false,
   int log_n = 0; while (((size_t)1 << log_n) < n) log_n++;
   check(blsgpu_fr_ntt_many(Context::instance().handle(), v[0].data(), log_n, k, inverse ? 1 : 0, coset ? coset->data() : nullptr), "fr_ntt_many");
 }
+// The same transform over group elements: k vectors of p.size() / k points each in one call, in place (vector i = elements
+// [i n, (i+1) n)); Y[m] = sum_j [w^(jm)] P[j] with the w of fr_ntt, the inverse scaled by n^-1 (include/bls12_381_hip.h).  Every point
+// must lie in the prime-order subgroup.  The overloads on affine points lift them (Z = 1, the identity (0 : 1 : 0)) and return the result.
+template <int G> void g_ntt_many(std::vector<Projective<G>>& p, size_t k, bool inverse = false) {
+  if (k == 0 && p.empty()) return;
+  if (k == 0 || p.empty() || p.size() % k) throw std::invalid_argument("g_ntt_many: the length must be k vectors of equal size");
+  const size_t n = p.size() / k;
+  if (n & (n - 1)) throw std::invalid_argument("g_ntt_many: the vector length must be a power of two");
+  int log_n = 0; while (((size_t)1 << log_n) < n) log_n++;
+  constexpr int W = Projective<G>::W;
+  std::vector<uint64_t> xyz(p.size() * W);
+  for (size_t i = 0; i < p.size(); i++) std::memcpy(xyz.data() + i * W, p[i].xyz.data(), W * 8);
+  check((G == 1 ? blsgpu_g1_ntt_many : blsgpu_g2_ntt_many)(Context::instance().handle(), xyz.data(), log_n, k, inverse ? 1 : 0), "g_ntt_many");
+  for (size_t i = 0; i < p.size(); i++) std::memcpy(p[i].xyz.data(), xyz.data() + i * W, W * 8);
+}
+template <int G> std::vector<Projective<G>> g_ntt_many(const std::vector<Affine<G>>& a, size_t k, bool inverse = false) {
+  std::vector<Projective<G>> p(a.size());
+  for (size_t i = 0; i < a.size(); i++) {
+    if (a[i].infinity) { p[i] = Projective<G>::identity(); continue; }
+    std::memcpy(p[i].xyz.data(), a[i].xy.data(), Affine<G>::W * 8);
+    std::memcpy(p[i].xyz.data() + 2 * Projective<G>::W / 3, detail::kOne, 48);
+  }
+  g_ntt_many<G>(p, k, inverse);
+  return p;
+}
+inline void g1_ntt_many(std::vector<G1Projective>& p, size_t k, bool inverse = false) { g_ntt_many<1>(p, k, inverse); }
+inline void g2_ntt_many(std::vector<G2Projective>& p, size_t k, bool inverse = false) { g_ntt_many<2>(p, k, inverse); }
+inline std::vector<G1Projective> g1_ntt_many(const std::vector<G1Affine>& a, size_t k, bool inverse = false) { return g_ntt_many<1>(a, k, inverse); }
+inline std::vector<G2Projective> g2_ntt_many(const std::vector<G2Affine>& a, size_t k, bool inverse = false) { return g_ntt_many<2>(a, k, inverse); }
 
 // The same operations sharded over several GPUs of one node from this process (blsgpu_group: one context + one host thread per
 // listed device; partial results folded with `Sum` / `MillerLoopResult + MillerLoopResult`, src/g1.rs:161-171, src/pairings.rs:179-186)

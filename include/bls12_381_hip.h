@@ -518,6 +518,28 @@ int blsgpu_fr_ntt_device(blsgpu_ctx* ctx, void* d_data, int log_n, int inverse);
  * of range, a coset whose limbs are all zero or not below r. */
 int blsgpu_fr_ntt_many(blsgpu_ctx* ctx, uint64_t* data, int log_n, size_t k, int inverse, const uint64_t* coset);
 int blsgpu_fr_ntt_many_device(blsgpu_ctx* ctx, void* d_data, int log_n, size_t k, int inverse, const uint64_t* coset);
+/* The same radix-2 transform over GROUP elements: k vectors of 2^log_n G1 (G2) points each, laid end to end, in place, natural order in
+ * and out:
+ *   forward  Y[m] = sum_j [w^(jm)] P[j],   inverse  P[j] = [n^-1] sum_m [w^(-jm)] Y[m],   w as for blsgpu_fr_ntt
+ * so the transform of [s_j] G is [fr_ntt(s)_m] G, and inverse after forward is the identity on group elements.  Uses: a monomial SRS
+ * [tau^j] G into its Lagrange form (the inverse transform), the Toeplitz products of amortised KZG openings, key derivation over G2.
+ * Points are projective wire points X | Y | Z (18 u64 for G1, 36 for G2; an affine point is one with Z = 1, any record with Z = 0 is
+ * the identity): what blsgpu_g{1,2}_mul_batch writes and blsgpu_g{1,2}_batch_normalize reads, so mul_batch_device -> ntt_many_device
+ * -> batch_normalize_device -> bases_from_device is a chain without a host copy.  Results are group elements: the projective
+ * representative is not pinned, compare after affine conversion (as for mul_batch).
+ * PRECONDITION: every point lies in the prime-order subgroup -- outputs of the checked decoders, of mul_batch / MSM on such points, an
+ * SRS; the identity is allowed anywhere.  w^(jm) is a residue mod r, so the transform is only defined there, and the endomorphism
+ * splits are always used, whatever blsgpu_set_assume_subgroup says.  Results for points outside the subgroup are unspecified (as for
+ * the MSM under blsgpu_set_assume_subgroup).
+ * log_n in [0, 24], k * 2^log_n <= 2^24; k == 0 and log_n == 0 are no-ops (the records are left exactly as they are: a record with
+ * Z = 0 stays the identity it was).  d_xyz must be 16-byte aligned.  The device form is
+ * asynchronous on the context's stream and works in place: it shares no scratch with pipelined *_msm_device calls in flight.  The
+ * twiddle tables are the Fr transform's, built on the device and cached per (log_n, direction).  BLSGPU_ERR_ARG (nothing staged or
+ * launched): NULL points with k > 0, log_n or k * 2^log_n out of range, a misaligned d_xyz.  There is no coset form. */
+int blsgpu_g1_ntt_many(blsgpu_ctx* ctx, uint64_t* xyz, int log_n, size_t k, int inverse);
+int blsgpu_g2_ntt_many(blsgpu_ctx* ctx, uint64_t* xyz, int log_n, size_t k, int inverse);
+int blsgpu_g1_ntt_many_device(blsgpu_ctx* ctx, void* d_xyz, int log_n, size_t k, int inverse);
+int blsgpu_g2_ntt_many_device(blsgpu_ctx* ctx, void* d_xyz, int log_n, size_t k, int inverse);
 
 /* ---- hash-to-curve (the step in front of multi_miller_loop in bulk signature checks) ---- */
 /* `<G as HashToCurve<ExpandMsgXmd<Sha256>>>::hash_to_curve(msg, dst)` / `encode_to_curve` (encode_only != 0) for n

@@ -162,6 +162,10 @@ extern "C" {
     pub fn blsgpu_fr_ntt_device(ctx: *mut BlsgpuCtx, d_data: *mut c_void, log_n: c_int, inverse: c_int) -> c_int;
     pub fn blsgpu_fr_ntt_many(ctx: *mut BlsgpuCtx, data: *mut u64, log_n: c_int, k: usize, inverse: c_int, coset: *const u64) -> c_int;
     pub fn blsgpu_fr_ntt_many_device(ctx: *mut BlsgpuCtx, d_data: *mut c_void, log_n: c_int, k: usize, inverse: c_int, coset: *const u64) -> c_int;
+    pub fn blsgpu_g1_ntt_many(ctx: *mut BlsgpuCtx, xyz: *mut u64, log_n: c_int, k: usize, inverse: c_int) -> c_int;
+    pub fn blsgpu_g2_ntt_many(ctx: *mut BlsgpuCtx, xyz: *mut u64, log_n: c_int, k: usize, inverse: c_int) -> c_int;
+    pub fn blsgpu_g1_ntt_many_device(ctx: *mut BlsgpuCtx, d_xyz: *mut c_void, log_n: c_int, k: usize, inverse: c_int) -> c_int;
+    pub fn blsgpu_g2_ntt_many_device(ctx: *mut BlsgpuCtx, d_xyz: *mut c_void, log_n: c_int, k: usize, inverse: c_int) -> c_int;
     pub fn blsgpu_g1_hash_to_curve_batch(ctx: *mut BlsgpuCtx, msgs: *const u8, offsets: *const u64, n: usize, dst: *const u8, dst_len: usize, encode_only: c_int, out_xyz: *mut u64) -> c_int;
     pub fn blsgpu_g2_hash_to_curve_batch(ctx: *mut BlsgpuCtx, msgs: *const u8, offsets: *const u64, n: usize, dst: *const u8, dst_len: usize, encode_only: c_int, out_xyz: *mut u64) -> c_int;
     pub fn blsgpu_hash_to_curve_device(ctx: *mut BlsgpuCtx, group: c_int, d_msgs: *const c_void, d_offsets: *const c_void, n: usize, d_dst: *const c_void, dst_len: usize, encode_only: c_int, d_out_xyz: *mut c_void) -> c_int;

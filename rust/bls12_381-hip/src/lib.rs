@@ -13,6 +13,7 @@
 //!   multi_miller_loop         multi_miller_loop(&[(p_i, prepared q_i)])                 src/pairings.rs:554-603
 //!   final_exponentiation      MillerLoopResult::final_exponentiation                    src/pairings.rs:48-176
 //!   batch_normalize_g1        G1Projective::batch_normalize                             src/g1.rs:806-839
+//!   ntt_g1 / ntt_g2           the radix-2 group FFT a caller writes over `ROOT_OF_UNITY`                src/scalar.rs:193-205
 //!   multi_miller_loop_many    multi_miller_loop(terms_s).final_exponentiation() for every equation s    src/pairings.rs:554-603, 48-176
 //!   GpuGroup::*               the same operations sharded over the GPUs of the node (folds: `Sum`, `MillerLoopResult +`)
 //! Hot-path functions of the reference are infallible; here a HIP failure or a bad argument is an `Err(Error)` and the
@@ -136,6 +137,52 @@ pub fn mul_batch_g2(gpu: &Gpu, points: &[G2Affine], scalars: &[Scalar]) -> Resul
     let ((xy, inf), s) = (g2_wire(gpu, points)?, scalar_bytes(scalars));
     let (mut xyz, mut axy, mut ainf, mut enc) = (vec![0u64; n * 36], vec![0u64; n * 24], vec![0u8; n], vec![0u8; n * 192]);
     check(unsafe { ffi::blsgpu_g2_mul_batch(gpu.ctx, xy.as_ptr(), inf.as_ptr(), s.as_ptr(), n, xyz.as_mut_ptr()) })?;
+    check(unsafe { ffi::blsgpu_g2_batch_normalize(gpu.ctx, xyz.as_ptr(), n, axy.as_mut_ptr(), ainf.as_mut_ptr()) })?;
+    check(unsafe { ffi::blsgpu_g2_to_bytes_batch(gpu.ctx, axy.as_ptr(), ainf.as_ptr(), n, 0, enc.as_mut_ptr()) })?;
+    Ok(enc.chunks_exact(192).map(|c| {
+        let mut b = [0u8; 192]; b.copy_from_slice(c);
+        G2Projective::from(Option::<G2Affine>::from(G2Affine::from_uncompressed_unchecked(&b)).expect("libblsgpu returned an invalid G2 encoding"))
+    }).collect())
+}
+/// `Fp::one()` in Montgomery limbs (R mod p, src/fp.rs:83-90): the Z of an affine point lifted to a projective wire point
+const FP_ONE: [u64; 6] = [0x760900000002fffd, 0xebf4000bc40c0002, 0x5f48985753c758ba, 0x77ce585370525745, 0x5c071a97a256ec6d, 0x15f65ec3fa80e493];
+/// affine wire limbs + infinity bytes -> projective wire points X | Y | Z (Z = 1; the identity is (0 : 1 : 0)); w = limbs per coordinate
+fn lift_wire(xy: &[u64], inf: &[u8], w: usize) -> Vec<u64> {
+    let mut xyz = vec![0u64; inf.len() * 3 * w];
+    for (i, &f) in inf.iter().enumerate() {
+        let p = &mut xyz[i * 3 * w..(i + 1) * 3 * w];
+        if f != 0 { p[w..w + 6].copy_from_slice(&FP_ONE); continue; }
+        p[..2 * w].copy_from_slice(&xy[i * 2 * w..(i + 1) * 2 * w]);
+        p[2 * w..2 * w + 6].copy_from_slice(&FP_ONE);
+    }
+    xyz
+}
+/// Radix-2 transform over G1 elements, `k` vectors of `points.len() / k` points each (a power of two) in one call:
+/// `Y[m] = sum_j P[j] * w^(jm)` with `w = Scalar::ROOT_OF_UNITY^(2^(32 - log_n))` (src/scalar.rs:193-205), the inverse scaled by `n^-1` --
+/// what a caller writes as a group FFT over `G1Projective`, e.g. a monomial SRS into its Lagrange form.  Every point must lie in the
+/// prime-order subgroup, which every `G1Affine` the crate's checked constructors hand out does.
+pub fn ntt_g1(gpu: &Gpu, points: &[G1Affine], k: usize, inverse: bool) -> Result<Vec<G1Projective>, Error> {
+    let n = points.len();
+    assert!(k > 0 && n % k == 0 && (n / k).is_power_of_two());
+    let (xy, inf) = g1_wire(gpu, points)?;
+    let mut xyz = lift_wire(&xy, &inf, 6);
+    let (mut axy, mut ainf, mut enc) = (vec![0u64; n * 12], vec![0u8; n], vec![0u8; n * 96]);
+    check(unsafe { ffi::blsgpu_g1_ntt_many(gpu.ctx, xyz.as_mut_ptr(), (n / k).trailing_zeros() as c_int, k, inverse as c_int) })?;
+    check(unsafe { ffi::blsgpu_g1_batch_normalize(gpu.ctx, xyz.as_ptr(), n, axy.as_mut_ptr(), ainf.as_mut_ptr()) })?;
+    check(unsafe { ffi::blsgpu_g1_to_bytes_batch(gpu.ctx, axy.as_ptr(), ainf.as_ptr(), n, 0, enc.as_mut_ptr()) })?;
+    Ok(enc.chunks_exact(96).map(|c| {
+        let mut b = [0u8; 96]; b.copy_from_slice(c);
+        G1Projective::from(Option::<G1Affine>::from(G1Affine::from_uncompressed_unchecked(&b)).expect("libblsgpu returned an invalid G1 encoding"))
+    }).collect())
+}
+/// the same over G2
+pub fn ntt_g2(gpu: &Gpu, points: &[G2Affine], k: usize, inverse: bool) -> Result<Vec<G2Projective>, Error> {
+    let n = points.len();
+    assert!(k > 0 && n % k == 0 && (n / k).is_power_of_two());
+    let (xy, inf) = g2_wire(gpu, points)?;
+    let mut xyz = lift_wire(&xy, &inf, 12);
+    let (mut axy, mut ainf, mut enc) = (vec![0u64; n * 24], vec![0u8; n], vec![0u8; n * 192]);
+    check(unsafe { ffi::blsgpu_g2_ntt_many(gpu.ctx, xyz.as_mut_ptr(), (n / k).trailing_zeros() as c_int, k, inverse as c_int) })?;
     check(unsafe { ffi::blsgpu_g2_batch_normalize(gpu.ctx, xyz.as_ptr(), n, axy.as_mut_ptr(), ainf.as_mut_ptr()) })?;
     check(unsafe { ffi::blsgpu_g2_to_bytes_batch(gpu.ctx, axy.as_ptr(), ainf.as_ptr(), n, 0, enc.as_mut_ptr()) })?;
     Ok(enc.chunks_exact(192).map(|c| {
