@@ -68,6 +68,10 @@ SIGNATURES = {
     "blsgpu_fr_ntt_device": (c_int, [c_vp, c_vp, c_int, c_int]),
     "blsgpu_fr_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int, c_vp]),
     "blsgpu_fr_ntt_many_device": (c_int, [c_vp, c_vp, c_int, c_sz, c_int, c_vp]),
+    "blsgpu_fr_scan_many": (c_int, [c_vp, c_int, c_int, c_vp, c_sz, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_scan_many_device": (c_int, [c_vp, c_int, c_int, c_vp, c_sz, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_batch_invert": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_batch_invert_device": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
     "blsgpu_g1_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),
     "blsgpu_g2_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),
     "blsgpu_g1_ntt_many_device": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),

@@ -62,6 +62,7 @@ def _flags(f, n):
     return f
 
 
+FR_SCAN_SUM, FR_SCAN_PRODUCT, FR_SCAN_HORNER = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_SCAN_*
 FR_GENERATOR = 7                          # scalar.rs:99-105 GENERATOR (`MULTIPLICATIVE_GENERATOR` :708): the usual coset shift
 
 
@@ -76,6 +77,24 @@ def _coset_limbs(coset):
         v = (g << 256) % R_ORDER
         return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
     return _u64(coset, (4,)).copy()
+
+
+def _point_limbs(points, k):
+    """k Python ints in [0, r) | a (k, 4) array of Montgomery limbs -> (k, 4) Montgomery limbs (np.uint64), converted as _coset_limbs does"""
+    if isinstance(points, (int, np.integer)):
+        points = [points]
+    if isinstance(points, (list, tuple)) and all(isinstance(p, (int, np.integer)) for p in points):
+        if len(points) != k:
+            raise ValueError("fr_scan: one point per row")
+        out = np.zeros((k, 4), dtype=np.uint64)
+        for i, p in enumerate(points):
+            z = int(p)
+            if not 0 <= z < R_ORDER:
+                raise ValueError("fr_scan: an integer point must be in [0, r)")
+            v = (z << 256) % R_ORDER
+            out[i] = [(v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(4)]
+        return out
+    return _u64(points, (k, 4)).copy()
 
 
 _R_WORDS = np.frombuffer(R_ORDER.to_bytes(32, "little"), dtype="<u8")
@@ -599,6 +618,10 @@ class Context:
         check(self.lib.blsgpu_fr_op(self.h, op, _ptr(a), _ptr(b), a.shape[0], _ptr(out), _ptr(flags)), "fr_op")
         return (out, flags) if return_flags else out
 
+    def fr_op_device(self, op, d_a, d_b, n, d_out, d_flags=None):
+        """fr_op on n scalars in device memory (d_b: None for the unary ops), asynchronous on the context's stream"""
+        check(self.lib.blsgpu_fr_op_device(self.h, int(op), d_a, d_b, n, d_out, d_flags), "fr_op_device")
+
     def fr_ntt(self, values, inverse=False):
         """radix-2 transform of 2^k Scalars ((n, 4) u64 Montgomery limbs), natural order in and out; see
         include/bls12_381_hip.h for the definition."""
@@ -629,6 +652,48 @@ class Context:
     def fr_ntt_many_device(self, d_ptr, log_n, k, inverse=False, coset=None):
         """the same on k * 2^log_n scalars in device memory, in place, asynchronous on the context's stream (`coset` stays a host value)"""
         check(self.lib.blsgpu_fr_ntt_many_device(self.h, d_ptr, log_n, k, 1 if inverse else 0, _ptr(_coset_limbs(coset))), "fr_ntt_many_device")
+
+    def fr_scan(self, op, values, points=None, exclusive=False):
+        """recurrences along k rows in one call (include/bls12_381_hip.h): `values` is a (k, len, 4) u64 array of Montgomery limbs (a
+        (len, 4) array is k = 1), op FR_SCAN_SUM / FR_SCAN_PRODUCT (inclusive, or exclusive) or FR_SCAN_HORNER: row v = the coefficients
+        of p_v, points[v] = z (Python ints in [0, r) or a (k, 4) array of Montgomery limbs) -> out[v][0] = p_v(z), out[v][1:] = the
+        quotient (p_v(X) - p_v(z)) / (X - z).  Returns a new array of the same shape."""
+        v = np.ascontiguousarray(np.array(values, dtype=np.uint64))
+        one = v.ndim == 2
+        if one:
+            v = v.reshape((1,) + v.shape)
+        if v.ndim != 3 or v.shape[2] != 4:
+            raise ValueError("fr_scan: expected a (k, len, 4) or (len, 4) array")
+        if op not in (FR_SCAN_SUM, FR_SCAN_PRODUCT, FR_SCAN_HORNER):
+            raise ValueError("fr_scan: unknown op")
+        k, n = v.shape[0], v.shape[1]
+        pts = None
+        if op == FR_SCAN_HORNER:
+            if exclusive:
+                raise ValueError("fr_scan: exclusive is not defined for HORNER")
+            if points is None:
+                raise ValueError("fr_scan: HORNER needs one point per row")
+            pts = _point_limbs(points, k)
+        out = np.zeros_like(v)
+        check(self.lib.blsgpu_fr_scan_many(self.h, int(op), 1 if exclusive else 0, _ptr(v), n, k, _ptr(pts), _ptr(out)), "fr_scan")
+        return out[0] if one else out
+
+    def fr_scan_device(self, op, d_in, length, k, d_out, d_points=None, exclusive=False):
+        """the same on k * length scalars in device memory (d_points: k scalars in device memory for HORNER), d_out == d_in allowed,
+        asynchronous on the context's stream"""
+        check(self.lib.blsgpu_fr_scan_many_device(self.h, int(op), 1 if exclusive else 0, d_in, length, k, d_points, d_out), "fr_scan_device")
+
+    def fr_batch_invert(self, values, return_flags=False):
+        """element-wise inverses of an (n, 4) u64 array of Montgomery limbs by Montgomery's trick: limb-identical to fr_op(4, ...), 0 for a
+        zero; return_flags also returns the `is_some` bytes (0 where the input was zero)"""
+        a = _u64(values, (-1, 4))
+        out = np.zeros_like(a)
+        flags = np.ones(a.shape[0], dtype=np.uint8)
+        check(self.lib.blsgpu_fr_batch_invert(self.h, _ptr(a), a.shape[0], _ptr(out), _ptr(flags)), "fr_batch_invert")
+        return (out, flags) if return_flags else out
+
+    def fr_batch_invert_device(self, d_in, n, d_out, d_flags=None):
+        check(self.lib.blsgpu_fr_batch_invert_device(self.h, d_in, n, d_out, d_flags), "fr_batch_invert_device")
 
     def g_ntt_many(self, group, points, inverse=False):
         """k independent radix-2 transforms over GROUP elements in one call (include/bls12_381_hip.h: Y[m] = sum_j [w^(jm)] P[j], the w of

@@ -3,6 +3,7 @@
 #include "host.h"
 #include "fr.hip.h"
 #include "fr_plan.h"
+#include "fr_scan.hip.h"
 #include "h2c.hip.h"
 #include "expand_kernels.hip.h"
 #include "codec.hip.h"
@@ -444,6 +445,129 @@ extern "C" int blsgpu_fr_ntt_many(blsgpu_ctx* c, uint64_t* data, int log_n, size
   void* d = h.inout(c->io_a, data, (k << log_n) * 32);
   if (h.rc) return h.rc;
   return h.finish(blsgpu_fr_ntt_many_device(c, d, log_n, k, inverse, coset));
+}
+
+// ---- recurrences along a vector: segmented scans and batch inversion (fr_scan.hip.h; fr_scan_plan.h decides the launches) -----------------
+// every argument check of both forms, before anything is staged, reserved or launched.  *work: there is something to do.
+static bool frs_ranges_clash(const void* a, const void* b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x != y && x < y + bytes && y < x + bytes;
+}
+static int fr_scan_check(blsgpu_ctx* c, int op, int exclusive, const void* in, size_t len, size_t k, const void* points, const void* out, bool device, bool* work) {
+  *work = false;
+  if (!c) return bad("fr_scan_many: NULL context");
+  if (op < BLSGPU_FR_SCAN_SUM || op > BLSGPU_FR_SCAN_HORNER) return bad("fr_scan_many: unknown op");
+  if (op == BLSGPU_FR_SCAN_HORNER && exclusive) return bad("fr_scan_many: exclusive is not defined for HORNER");
+  if (len && k > FRS_MAX_TOTAL / len) return bad("fr_scan_many: k * len must not exceed 2^28");
+  if (!len || !k) return BLSGPU_OK;
+  if (!in || !out) return bad("fr_scan_many: NULL data pointer");
+  if (op == BLSGPU_FR_SCAN_HORNER && !points) return bad("fr_scan_many: HORNER needs points (k scalars)");
+  if (device && ((((uintptr_t)in | (uintptr_t)out) & 15) || (op == BLSGPU_FR_SCAN_HORNER && ((uintptr_t)points & 15))))
+    return bad("fr_scan_many_device: device pointers must be 16-byte aligned");
+  if (frs_ranges_clash(in, out, len * k * 32)) return bad("fr_scan_many: in and out overlap partially (out == in is the in-place form)");
+  *work = true;
+  return BLSGPU_OK;
+}
+// more than 64 KB of dynamic LDS per workgroup has to be asked for: once per context (four cheap calls)
+static int frs_lds_probe(blsgpu_ctx* c) {
+  if (c->frs_lds_ready) return BLSGPU_OK;
+  const int want = (int)frs_lds_bytes(FrScanShape());
+  HIPCHK(hipFuncSetAttribute((const void*)k_frs_tile<FRS_SUM>, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+  HIPCHK(hipFuncSetAttribute((const void*)k_frs_tile<FRS_PRODUCT>, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+  HIPCHK(hipFuncSetAttribute((const void*)k_frs_tile<FRS_HORNER>, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+  HIPCHK(hipFuncSetAttribute((const void*)k_frs_invert, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+  c->frs_lds_ready = true;
+  return BLSGPU_OK;
+}
+template <int OP>
+static int fr_scan_launch(blsgpu_ctx* c, const FrScanPlan& plan, int exclusive, const u32* in, size_t len, size_t k, const u32* points, u32* out) {
+  hipStream_t st = c->stream;
+  const unsigned chunk = FrScanShape().chunk;
+  u32* buf[4] = {c->frs_agg[0].as<u32>(), c->frs_agg[1].as<u32>(), c->frs_carry[0].as<u32>(), c->frs_carry[1].as<u32>()};
+  for (int i = 0; i < plan.n_steps; i++) {
+    const FrScanStep& s = plan.step[i];
+    u32* src = s.src >= 0 ? buf[s.src] : nullptr;
+    u32* dst = s.dst >= 0 ? buf[s.dst] : nullptr;
+    u32* carry = s.carry >= 0 ? buf[s.carry] : nullptr;
+    switch (s.kernel) {
+      case FRS_K_SINGLE: case FRS_K_REDUCE: case FRS_K_SCAN:
+        KLAUNCH(k_frs_tile<OP>, dim3(s.grid), dim3(s.block), s.lds, st, s.kernel, exclusive, in, out, points, len, k, chunk, dst, (const u32*)carry, c->frs_lane.as<u32>());
+        break;
+      default:
+        KLAUNCH(k_frs_agg<OP>, dim3(s.grid), dim3(s.block), s.lds, st, s.kernel, (const u32*)src, s.items, chunk, s.kernel == FRS_K_AGG_REDUCE ? dst : (u32*)nullptr,
+                (const u32*)carry, s.kernel == FRS_K_AGG_SCAN ? dst : (u32*)nullptr);
+        break;
+    }
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_scan_many_device(blsgpu_ctx* c, int op, int exclusive, const void* d_in, size_t len, size_t k, const void* d_points, void* d_out) { CTX_CLAIM(c);
+  bool work;
+  if (int rc = fr_scan_check(c, op, exclusive, d_in, len, k, d_points, d_out, true, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = frs_lds_probe(c)) return rc;
+  const FrScanPlan plan = fr_scan_plan(len, k);
+  if (plan.n_steps < 0) return bad("fr_scan_many: k * len must not exceed 2^28");
+  const size_t rec = (size_t)frs_rec_words(op) * 4;
+  if (c->frs_agg[0].reserve(plan.recs[FRS_BUF_AGG0] * rec) || c->frs_agg[1].reserve(plan.recs[FRS_BUF_AGG1] * rec) ||
+      c->frs_carry[0].reserve(plan.recs[FRS_BUF_CARRY0] * 32) || c->frs_carry[1].reserve(plan.recs[FRS_BUF_CARRY1] * 32) ||
+      c->frs_lane.reserve(plan.recs[FRS_BUF_LANE] * rec)) {
+    g_err = "hipMalloc(fr scan scratch) failed"; return BLSGPU_ERR_HIP;
+  }
+  const u32* in = (const u32*)d_in; const u32* pts = (const u32*)d_points; u32* out = (u32*)d_out;
+  const int ex = exclusive ? 1 : 0;
+  if (op == BLSGPU_FR_SCAN_SUM) return fr_scan_launch<FRS_SUM>(c, plan, ex, in, len, k, pts, out);
+  if (op == BLSGPU_FR_SCAN_PRODUCT) return fr_scan_launch<FRS_PRODUCT>(c, plan, ex, in, len, k, pts, out);
+  return fr_scan_launch<FRS_HORNER>(c, plan, 0, in, len, k, pts, out);
+}
+extern "C" int blsgpu_fr_scan_many(blsgpu_ctx* c, int op, int exclusive, const uint64_t* values, size_t len, size_t k, const uint64_t* points, uint64_t* out) { CTX_CLAIM(c);
+  bool work;
+  if (int rc = fr_scan_check(c, op, exclusive, values, len, k, points, out, false, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HostCall h(c);
+  void* di = h.in(c->io_a, values, len * k * 32);
+  void* dp = h.in(c->io_b, op == BLSGPU_FR_SCAN_HORNER ? points : nullptr, k * 32);
+  void* o = h.out(c->io_out, out, len * k * 32);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_scan_many_device(c, op, exclusive, di, len, k, dp, o));
+}
+static int fr_batch_invert_check(blsgpu_ctx* c, const void* in, size_t n, const void* out, bool device, bool* work) {
+  *work = false;
+  if (!c) return bad("fr_batch_invert: NULL context");
+  if (n > FRS_MAX_TOTAL) return bad("fr_batch_invert: n must not exceed 2^28");
+  if (!n) return BLSGPU_OK;
+  if (!in || !out) return bad("fr_batch_invert: NULL data pointer");
+  if (device && (((uintptr_t)in | (uintptr_t)out) & 15)) return bad("fr_batch_invert_device: device pointers must be 16-byte aligned");
+  if (frs_ranges_clash(in, out, n * 32)) return bad("fr_batch_invert: in and out overlap partially (out == in is the in-place form)");
+  *work = true;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_batch_invert_device(blsgpu_ctx* c, const void* d_in, size_t n, void* d_out, void* d_nonzero_flags) { CTX_CLAIM(c);
+  bool work;
+  if (int rc = fr_batch_invert_check(c, d_in, n, d_out, true, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = frs_lds_probe(c)) return rc;
+  const FrScanPlan plan = fr_invert_plan(n);
+  for (int i = 0; i < plan.n_steps; i++) {
+    const FrScanStep& s = plan.step[i];
+    KLAUNCH(k_frs_invert, dim3(s.grid), dim3(s.block), s.lds, c->stream, (const u32*)d_in, (u32*)d_out, (uint8_t*)d_nonzero_flags, n, (unsigned)FrScanShape().chunk);
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_batch_invert(blsgpu_ctx* c, const uint64_t* values, size_t n, uint64_t* out, uint8_t* nonzero_flags) { CTX_CLAIM(c);
+  bool work;
+  if (int rc = fr_batch_invert_check(c, values, n, out, false, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HostCall h(c);
+  void* di = h.in(c->io_a, values, n * 32);
+  void* o = h.out(c->io_out, out, n * 32);
+  void* f = nonzero_flags ? h.out(c->flags_a, nonzero_flags, n) : nullptr;
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_batch_invert_device(c, di, n, o, f));
 }
 
 // ---------------------------------------------------------------------------------------------------

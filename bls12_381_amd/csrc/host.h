@@ -218,6 +218,8 @@ struct blsgpu_ctx {
   int fr_cs_log[2] = {-1, -1};
   uint64_t fr_cs_g[2][4] = {};
   hipEvent_t ev_fr_cs[2] = {};          // as ev_fr
+  DevBuf frs_agg[2], frs_carry[2], frs_lane;      // blsgpu_fr_scan_many: aggregate records of the tiles / of groups of tiles, their exclusive scans, the lanes' prefixes (fr_scan_plan.h)
+  bool frs_lds_ready = false;           // the scan kernels' dynamic LDS (more than the 64 KB a kernel gets unasked) has been granted on this device
 };
 
 static inline KTimer* ktimer_of(blsgpu_ctx* c) { return &c->ktimer; }

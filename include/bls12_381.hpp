@@ -341,6 +341,25 @@ inline void fr_ntt_many(std::vector<FrLimbs>& v, size_t k, bool inverse = false,
   int log_n = 0; while (((size_t)1 << log_n) < n) log_n++;
   check(blsgpu_fr_ntt_many(Context::instance().handle(), v[0].data(), log_n, k, inverse ? 1 : 0, coset ? coset->data() : nullptr), "fr_ntt_many");
 }
+// Recurrences along k rows of v.size() / k scalars each in one call (include/bls12_381_hip.h): running sums / products (inclusive, or
+// exclusive), or Horner rows -- row i = the coefficients of p_i, points[i] = z: out row = p_i(z), then the quotient (p_i(X) - p_i(z)) / (X - z)
+enum class FrScan { Sum = 0, Product = 1, Horner = 2 };
+inline std::vector<FrLimbs> fr_scan(FrScan op, const std::vector<FrLimbs>& v, size_t k, const std::vector<FrLimbs>& points = {}, bool exclusive = false) {
+  std::vector<FrLimbs> out(v.size());
+  if (v.empty()) return out;
+  if (k == 0 || v.size() % k) throw std::invalid_argument("fr_scan: the length must be k rows of equal size");
+  if (op == FrScan::Horner && (points.size() != k || exclusive)) throw std::invalid_argument("fr_scan: HORNER takes one point per row and no exclusive form");
+  check(blsgpu_fr_scan_many(Context::instance().handle(), (int)op, exclusive ? 1 : 0, v[0].data(), v.size() / k, k, points.empty() ? nullptr : points[0].data(), out[0].data()), "fr_scan");
+  return out;
+}
+// element-wise inverses by Montgomery's trick: limb-identical to fr_op(FrOp::Invert, ...), 0 for a zero (nonzero, if given, gets the flags)
+inline std::vector<FrLimbs> fr_batch_invert(const std::vector<FrLimbs>& v, std::vector<uint8_t>* nonzero = nullptr) {
+  std::vector<FrLimbs> out(v.size());
+  if (nonzero) nonzero->assign(v.size(), 1);
+  if (v.empty()) return out;
+  check(blsgpu_fr_batch_invert(Context::instance().handle(), v[0].data(), v.size(), out[0].data(), nonzero ? nonzero->data() : nullptr), "fr_batch_invert");
+  return out;
+}
 // The same transform over group elements: k vectors of p.size() / k points each in one call, in place (vector i = elements
 // [i n, (i+1) n)); Y[m] = sum_j [w^(jm)] P[j] with the w of fr_ntt, the inverse scaled by n^-1 (include/bls12_381_hip.h).  Every point
 // must lie in the prime-order subgroup.  The overloads on affine points lift them (Z = 1, the identity (0 : 1 : 0)) and return the result.

@@ -518,6 +518,30 @@ int blsgpu_fr_ntt_device(blsgpu_ctx* ctx, void* d_data, int log_n, int inverse);
  * of range, a coset whose limbs are all zero or not below r. */
 int blsgpu_fr_ntt_many(blsgpu_ctx* ctx, uint64_t* data, int log_n, size_t k, int inverse, const uint64_t* coset);
 int blsgpu_fr_ntt_many_device(blsgpu_ctx* ctx, void* d_data, int log_n, size_t k, int inverse, const uint64_t* coset);
+/* Recurrences ALONG a vector: k independent rows of `len` scalars each (any len > 0, not only a power of two), laid end to end; row v
+ * occupies scalars [v * len, (v+1) * len).  One call scans all rows:
+ *   SUM      out[v][i] = sum_{j<=i} in[v][j]            exclusive: the sum over j < i, out[v][0] = 0
+ *   PRODUCT  out[v][i] = prod_{j<=i} in[v][j]           exclusive: the product over j < i, out[v][0] = 1 (a zero zeroes the rest of ITS row)
+ *   HORNER   out[v][len-1] = in[v][len-1],  out[v][i] = in[v][i] + points[v] * out[v][i+1]      (exclusive must be 0)
+ * For HORNER in[v][i] is the coefficient of X^i of p_v, z = points[v] the row's own point (k scalars: data, so a device pointer in the
+ * device form): out[v][0] = p_v(z), and out[v][1 .. len) are the coefficients of X^0 .. X^(len-2) of (p_v(X) - p_v(z)) / (X - z), the
+ * quotient of a KZG opening.  `points` is ignored for SUM and PRODUCT.  Inputs and outputs are canonical Montgomery limbs.
+ * k * len <= 2^28; k == 0 and len == 0 are no-ops.  Device pointers must be 16-byte aligned.  out == in (exactly) is the in-place form;
+ * any other overlap is refused.  The device form is asynchronous on the context's stream; its scratch is the context's own (about 10
+ * bytes per element for a call of more than 2048 elements) and is not shared with pipelined *_msm_device calls in flight.  BLSGPU_ERR_ARG (nothing staged or launched): an unknown op, exclusive with
+ * HORNER, k * len out of range (64-bit overflow included), NULL in / out with work to do, NULL points for HORNER, a misaligned device
+ * pointer, a partial overlap. */
+#define BLSGPU_FR_SCAN_SUM     0
+#define BLSGPU_FR_SCAN_PRODUCT 1
+#define BLSGPU_FR_SCAN_HORNER  2
+int blsgpu_fr_scan_many(blsgpu_ctx* ctx, int op, int exclusive, const uint64_t* values, size_t len, size_t k, const uint64_t* points, uint64_t* out);
+int blsgpu_fr_scan_many_device(blsgpu_ctx* ctx, int op, int exclusive, const void* d_in, size_t len, size_t k, const void* d_points, void* d_out);
+/* out[i] = in[i]^-1 for a whole vector by Montgomery's trick (about three products per element and one inversion per tile of 2048,
+ * against an exponentiation per element for blsgpu_fr_op op 4, whose results these equal limb for limb).  A zero gives 0 and
+ * nonzero_flags[i] = 0 (1 elsewhere; nonzero_flags may be NULL) and affects no other element.  n <= 2^28, n == 0 is a no-op; alignment,
+ * out == in, asynchrony and refusals as for blsgpu_fr_scan_many. */
+int blsgpu_fr_batch_invert(blsgpu_ctx* ctx, const uint64_t* values, size_t n, uint64_t* out, uint8_t* nonzero_flags);
+int blsgpu_fr_batch_invert_device(blsgpu_ctx* ctx, const void* d_in, size_t n, void* d_out, void* d_nonzero_flags);
 /* The same radix-2 transform over GROUP elements: k vectors of 2^log_n G1 (G2) points each, laid end to end, in place, natural order in
  * and out:
  *   forward  Y[m] = sum_j [w^(jm)] P[j],   inverse  P[j] = [n^-1] sum_m [w^(-jm)] Y[m],   w as for blsgpu_fr_ntt

@@ -162,6 +162,10 @@ extern "C" {
     pub fn blsgpu_fr_ntt_device(ctx: *mut BlsgpuCtx, d_data: *mut c_void, log_n: c_int, inverse: c_int) -> c_int;
     pub fn blsgpu_fr_ntt_many(ctx: *mut BlsgpuCtx, data: *mut u64, log_n: c_int, k: usize, inverse: c_int, coset: *const u64) -> c_int;
     pub fn blsgpu_fr_ntt_many_device(ctx: *mut BlsgpuCtx, d_data: *mut c_void, log_n: c_int, k: usize, inverse: c_int, coset: *const u64) -> c_int;
+    pub fn blsgpu_fr_scan_many(ctx: *mut BlsgpuCtx, op: c_int, exclusive: c_int, values: *const u64, len: usize, k: usize, points: *const u64, out: *mut u64) -> c_int;
+    pub fn blsgpu_fr_scan_many_device(ctx: *mut BlsgpuCtx, op: c_int, exclusive: c_int, d_in: *const c_void, len: usize, k: usize, d_points: *const c_void, d_out: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_batch_invert(ctx: *mut BlsgpuCtx, values: *const u64, n: usize, out: *mut u64, nonzero_flags: *mut u8) -> c_int;
+    pub fn blsgpu_fr_batch_invert_device(ctx: *mut BlsgpuCtx, d_in: *const c_void, n: usize, d_out: *mut c_void, d_nonzero_flags: *mut c_void) -> c_int;
     pub fn blsgpu_g1_ntt_many(ctx: *mut BlsgpuCtx, xyz: *mut u64, log_n: c_int, k: usize, inverse: c_int) -> c_int;
     pub fn blsgpu_g2_ntt_many(ctx: *mut BlsgpuCtx, xyz: *mut u64, log_n: c_int, k: usize, inverse: c_int) -> c_int;
     pub fn blsgpu_g1_ntt_many_device(ctx: *mut BlsgpuCtx, d_xyz: *mut c_void, log_n: c_int, k: usize, inverse: c_int) -> c_int;

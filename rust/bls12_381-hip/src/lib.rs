@@ -190,6 +190,48 @@ pub fn ntt_g2(gpu: &Gpu, points: &[G2Affine], k: usize, inverse: bool) -> Result
         G2Projective::from(Option::<G2Affine>::from(G2Affine::from_uncompressed_unchecked(&b)).expect("libblsgpu returned an invalid G2 encoding"))
     }).collect())
 }
+/// `Scalar`s -> the four Montgomery limbs each that the Fr entry points take (`Scalar::to_bytes`, src/scalar.rs:284-296, converted on the GPU)
+fn scalar_limbs(gpu: &Gpu, scalars: &[Scalar]) -> Result<Vec<u64>, Error> {
+    let (bytes, mut limbs) = (scalar_bytes(scalars), vec![0u64; scalars.len() * 4]);
+    check(unsafe { ffi::blsgpu_fr_from_bytes(gpu.ctx, bytes.as_ptr(), scalars.len(), limbs.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(limbs)
+}
+fn limbs_scalars(gpu: &Gpu, limbs: &[u64]) -> Result<Vec<Scalar>, Error> {
+    let n = limbs.len() / 4;
+    let mut bytes = vec![0u8; n * 32];
+    check(unsafe { ffi::blsgpu_fr_to_bytes(gpu.ctx, limbs.as_ptr(), n, bytes.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(bytes.chunks_exact(32).map(|c| {
+        let mut b = [0u8; 32]; b.copy_from_slice(c);
+        Option::<Scalar>::from(Scalar::from_bytes(&b)).expect("libblsgpu returned a non-canonical Scalar")
+    }).collect())
+}
+/// The recurrences of `blsgpu_fr_scan_many` over `k` rows of `values.len() / k` scalars each, in one call.
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum FrScan { Sum = 0, Product = 1, Horner = 2 }
+/// `Sum` / `Product`: running sums / products along each row (`exclusive`: of the elements before each position, starting from 0 / 1).
+/// `Horner`: row v holds the coefficients of p_v (index i = X^i), `points[v]` = z; the result row is p_v(z) followed by the coefficients of
+/// the quotient (p_v(X) - p_v(z)) / (X - z) -- what a caller writes as a loop `h = c[i] + z * h` from the top coefficient down.
+pub fn fr_scan(gpu: &Gpu, op: FrScan, values: &[Scalar], k: usize, points: &[Scalar], exclusive: bool) -> Result<Vec<Scalar>, Error> {
+    if values.is_empty() { return Ok(Vec::new()); }
+    assert!(k > 0 && values.len() % k == 0);
+    assert!(op != FrScan::Horner || (points.len() == k && !exclusive));
+    let input = scalar_limbs(gpu, values)?;
+    let pts = if op == FrScan::Horner { scalar_limbs(gpu, points)? } else { Vec::new() };
+    let mut out = vec![0u64; input.len()];
+    check(unsafe {
+        ffi::blsgpu_fr_scan_many(gpu.ctx, op as c_int, exclusive as c_int, input.as_ptr(), values.len() / k, k,
+                                 if pts.is_empty() { std::ptr::null() } else { pts.as_ptr() }, out.as_mut_ptr())
+    })?;
+    limbs_scalars(gpu, &out)
+}
+/// Drop-in for `values.iter().map(|v| v.invert())` (src/scalar.rs:573-628) by Montgomery's trick: `None` where the input is zero.
+pub fn fr_batch_invert(gpu: &Gpu, values: &[Scalar]) -> Result<Vec<Option<Scalar>>, Error> {
+    if values.is_empty() { return Ok(Vec::new()); }
+    let input = scalar_limbs(gpu, values)?;
+    let (mut out, mut flags) = (vec![0u64; input.len()], vec![0u8; values.len()]);
+    check(unsafe { ffi::blsgpu_fr_batch_invert(gpu.ctx, input.as_ptr(), values.len(), out.as_mut_ptr(), flags.as_mut_ptr()) })?;
+    Ok(limbs_scalars(gpu, &out)?.into_iter().zip(flags).map(|(s, f)| if f != 0 { Some(s) } else { None }).collect())
+}
 fn split72(flat: Vec<u64>) -> Vec<GtLimbs> {
     flat.chunks_exact(72).map(|c| { let mut a = [0u64; 72]; a.copy_from_slice(c); GtLimbs(a) }).collect()
 }

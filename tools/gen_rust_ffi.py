@@ -58,8 +58,15 @@ def parse_header(path=HEADER):
     return out
 
 
-def rust_source():
-    decls = parse_header()
+# strict and reserved keywords of Rust (2021): a C parameter of that name is written as a raw identifier
+RUST_KEYWORDS = frozenset("""as break const continue crate else enum extern false fn for if impl in let loop match mod move mut pub ref return self Self
+static struct super trait true type unsafe use where while async await dyn abstract become box do final macro override priv typeof unsized
+virtual yield try""".split())
+
+
+def rust_source(decls=None):
+    """the Rust file for the header's declarations (or for `decls`, a list of (name, return type, [(C type, parameter name)]))"""
+    decls = parse_header() if decls is None else decls
     lines = ["//! `extern \"C\"` declarations of libblsgpu.so -- GENERATED from include/bls12_381_hip.h by tools/gen_rust_ffi.py; do not edit.",
              "//! One entry per symbol of the C ABI; the header documents each one and cites the reference lines it replaces.",
              "#![allow(non_camel_case_types, dead_code)]",
@@ -86,7 +93,7 @@ def rust_source():
              "#[link(name = \"blsgpu\")]",
              "extern \"C\" {"]
     for name, ret, ps in decls:
-        args = ", ".join("%s: %s" % ("r#type" if n == "type" else n, C_TO_RUST[t]) for t, n in ps)
+        args = ", ".join("%s: %s" % ("r#" + n if n in RUST_KEYWORDS else n, C_TO_RUST[t]) for t, n in ps)
         r = "" if ret == "void" else " -> " + C_TO_RUST[ret]
         lines.append("    pub fn %s(%s)%s;" % (name, args, r))
     lines.append("}")
