@@ -72,6 +72,14 @@ SIGNATURES = {
     "blsgpu_fr_scan_many_device": (c_int, [c_vp, c_int, c_int, c_vp, c_sz, c_sz, c_vp, c_vp]),
     "blsgpu_fr_batch_invert": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
     "blsgpu_fr_batch_invert_device": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_matrix_upload": (c_int, [c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "blsgpu_fr_matrix_from_device": (c_int, [c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "blsgpu_fr_matrix_rows": (c_sz, [c_vp]),
+    "blsgpu_fr_matrix_cols": (c_sz, [c_vp]),
+    "blsgpu_fr_matrix_nnz": (c_sz, [c_vp]),
+    "blsgpu_fr_matrix_free": (None, [c_vp]),
+    "blsgpu_fr_spmv": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_fr_spmv_device": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),
     "blsgpu_g1_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),
     "blsgpu_g2_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),
     "blsgpu_g1_ntt_many_device": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),

@@ -173,6 +173,40 @@ class ResidentBases:
             pass
 
 
+class FrMatrix:
+    """A CSR matrix over Fr resident on the device (`blsgpu_fr_matrix`): validated and planned once by Context.fr_matrix, multiplied
+    many times by Context.fr_spmv."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def _size(self, fn):
+        return int(fn(self.handle)) if self.handle else 0
+
+    @property
+    def rows(self):
+        return self._size(self.ctx.lib.blsgpu_fr_matrix_rows)
+
+    @property
+    def cols(self):
+        return self._size(self.ctx.lib.blsgpu_fr_matrix_cols)
+
+    @property
+    def nnz(self):
+        return self._size(self.ctx.lib.blsgpu_fr_matrix_nnz)
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_fr_matrix_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PreparedG2Table:
     """m `G2Prepared` values resident on the device (`blsgpu_g2_prepared`): the 68 line-coefficient triples of each point
     (pairings.rs:487-546), named by index in the `*_prepared` Miller loops."""
@@ -694,6 +728,47 @@ class Context:
 
     def fr_batch_invert_device(self, d_in, n, d_out, d_flags=None):
         check(self.lib.blsgpu_fr_batch_invert_device(self.h, d_in, n, d_out, d_flags), "fr_batch_invert_device")
+
+    def fr_matrix(self, row_ptr, col, val, n_cols):
+        """a CSR matrix made resident (include/bls12_381_hip.h: blsgpu_fr_matrix_upload): row_ptr has n_rows + 1 entries from 0 to
+        nnz = len(col), non-decreasing; col[p] < n_cols; val is nnz Python ints in [0, r) or an (nnz, 4) u64 array of Montgomery limbs
+        (accepted as fr_scan's points are).  Columns inside a row may repeat (they add) and come in any order; rows may be empty.  The
+        whole structure is validated here, once; a bad matrix raises.  Returns an FrMatrix (.rows, .cols, .nnz, .close())."""
+        rp = np.ascontiguousarray(row_ptr, dtype=np.uint32).reshape(-1)
+        cl = np.ascontiguousarray(col, dtype=np.uint32).reshape(-1)
+        if rp.shape[0] < 1:
+            raise ValueError("fr_matrix: row_ptr needs n_rows + 1 entries")
+        if int(rp[-1]) != cl.shape[0]:
+            raise ValueError("fr_matrix: row_ptr[n_rows] must equal the number of non-zeros len(col)")
+        vl = _point_limbs(list(val) if isinstance(val, (list, tuple)) else val, cl.shape[0]) if cl.shape[0] else np.zeros((0, 4), dtype=np.uint64)
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_matrix_upload(self.h, rp.shape[0] - 1, int(n_cols), _ptr(rp), _ptr(cl), _ptr(vl), ctypes.byref(h)), "fr_matrix")
+        return FrMatrix(self, h)
+
+    def fr_matrix_from_device(self, d_row_ptr, d_col, d_val, n_rows, n_cols):
+        """the same from arrays already in device memory (u32 row_ptr / col, four u64 limbs per value; d_val 16-byte aligned): validated by a
+        kernel, copied into the handle's own buffers -- the caller's are free again on return"""
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_matrix_from_device(self.h, int(n_rows), int(n_cols), d_row_ptr, d_col, d_val, ctypes.byref(h)), "fr_matrix_from_device")
+        return FrMatrix(self, h)
+
+    def fr_spmv(self, m, x):
+        """out[v][i] = sum_p val[p] x[v][col[p]] over row i's entries: x is a (k, n_cols, 4) u64 array of Montgomery limbs ((n_cols, 4) is
+        k = 1) -> a new (k, n_rows, 4) (or (n_rows, 4)) array.  Stack A, B and C into one matrix of 3n rows to apply all three in one call."""
+        v = np.ascontiguousarray(np.array(x, dtype=np.uint64))
+        one = v.ndim == 2
+        if one:
+            v = v.reshape((1,) + v.shape)
+        if v.ndim != 3 or v.shape[2] != 4 or v.shape[1] != m.cols:
+            raise ValueError("fr_spmv: expected a (k, n_cols, 4) or (n_cols, 4) array")
+        out = np.zeros((v.shape[0], m.rows, 4), dtype=np.uint64)
+        check(self.lib.blsgpu_fr_spmv(self.h, m.handle, _ptr(v), v.shape[0], _ptr(out)), "fr_spmv")
+        return out[0] if one else out
+
+    def fr_spmv_device(self, m, d_x, k, d_out):
+        """the same on k * n_cols scalars in device memory -> k * n_rows scalars at d_out (no overlap with d_x), asynchronous on the
+        context's stream"""
+        check(self.lib.blsgpu_fr_spmv_device(self.h, m.handle, d_x, k, d_out), "fr_spmv_device")
 
     def g_ntt_many(self, group, points, inverse=False):
         """k independent radix-2 transforms over GROUP elements in one call (include/bls12_381_hip.h: Y[m] = sum_j [w^(jm)] P[j], the w of

@@ -4,6 +4,7 @@
 #include "fr.hip.h"
 #include "fr_plan.h"
 #include "fr_scan.hip.h"
+#include "fr_spmv.hip.h"
 #include "h2c.hip.h"
 #include "expand_kernels.hip.h"
 #include "codec.hip.h"
@@ -568,6 +569,201 @@ extern "C" int blsgpu_fr_batch_invert(blsgpu_ctx* c, const uint64_t* values, siz
   void* f = nonzero_flags ? h.out(c->flags_a, nonzero_flags, n) : nullptr;
   if (h.rc) return h.rc;
   return h.finish(blsgpu_fr_batch_invert_device(c, di, n, o, f));
+}
+
+// ---- sparse matrix-vector products: a resident CSR matrix times k vectors (fr_spmv.hip.h; fr_spmv_plan.h decides the launches) ------------
+// The whole structure is checked ONCE, before a handle exists: the product kernels gather x[col] and index out[row] on trust.
+// `what` names the first offender.  Returns true for a valid matrix.
+static bool frm_validate_host(size_t n_rows, size_t n_cols, const uint32_t* row_ptr, const uint32_t* col, const uint32_t* val_words, std::string* what) {
+  char buf[160];
+  if (row_ptr[0] != 0) { *what = "fr_matrix: row_ptr[0] must be 0"; return false; }
+  for (size_t i = 0; i < n_rows; i++)
+    if (row_ptr[i] > row_ptr[i + 1]) { snprintf(buf, sizeof buf, "fr_matrix: row_ptr decreases at row %zu", i); *what = buf; return false; }
+  const size_t nnz = row_ptr[n_rows];
+  if (nnz > FRSP_MAX) { *what = "fr_matrix: row_ptr[n_rows] (the number of non-zeros) must not exceed 2^28"; return false; }
+  if (nnz && (!col || !val_words)) { *what = "fr_matrix: NULL col / val with non-zeros to read"; return false; }
+  for (size_t p = 0; p < nnz; p++)
+    if (col[p] >= n_cols) { snprintf(buf, sizeof buf, "fr_matrix: col[%zu] = %u is not below n_cols", p, (unsigned)col[p]); *what = buf; return false; }
+  for (size_t p = 0; p < nnz; p++) {
+    const uint32_t* w = val_words + p * 8;
+    bool lt = false;
+    for (int i = 7; i >= 0; i--) { if (w[i] != FR_MOD_C.w[i]) { lt = w[i] < FR_MOD_C.w[i]; break; } }
+    if (!lt) { snprintf(buf, sizeof buf, "fr_matrix: val[%zu] is not a canonical Scalar (limbs >= r)", p); *what = buf; return false; }
+  }
+  return true;
+}
+static void frm_drop(blsgpu_fr_matrix* m) {
+  if (!m) return;
+  if (m->row_ptr) hipFree(m->row_ptr);
+  if (m->col) hipFree(m->col);
+  if (m->val) hipFree(m->val);
+  if (m->tile_row) hipFree(m->tile_row);
+  if (m->flag) hipFree(m->flag);
+  delete m;
+}
+static int frm_sizes_check(blsgpu_ctx* c, size_t n_rows, size_t n_cols, const void* row_ptr, blsgpu_fr_matrix** out) {
+  if (out) *out = nullptr;
+  if (!c || !out || !row_ptr) return bad("fr_matrix: NULL argument");
+  if (n_rows > FRSP_MAX || n_cols > FRSP_MAX) return bad("fr_matrix: n_rows and n_cols must not exceed 2^28");
+  return BLSGPU_OK;
+}
+static int frm_alloc(blsgpu_ctx* c, blsgpu_fr_matrix* m) {
+  const size_t tiles = frsp_tiles(m->nnz);
+  HIPCHK(hipMalloc((void**)&m->row_ptr, (m->n_rows + 1) * 4));
+  HIPCHK(hipMalloc((void**)&m->col, (m->nnz ? m->nnz : 1) * 4));
+  HIPCHK(hipMalloc((void**)&m->val, (m->nnz ? m->nnz : 1) * 32));
+  HIPCHK(hipMalloc((void**)&m->tile_row, (tiles + 1) * 4));
+  HIPCHK(hipMalloc((void**)&m->flag, 16));
+  HIPCHK(hipMemsetAsync(m->flag, 0, 16, c->stream));
+  return BLSGPU_OK;
+}
+// the resident form of a validated matrix whose row_ptr / col / val are already in m's own buffers: fold 2^5 into the values, find the
+// tiles' first rows, note whether a row is empty.  Synchronises (upload is a setup call).
+static int frm_prepare(blsgpu_ctx* c, blsgpu_fr_matrix* m) {
+  const size_t tiles = frsp_tiles(m->nnz);
+  size_t span = m->nnz > m->n_rows ? m->nnz : m->n_rows;
+  if (tiles + 1 > span) span = tiles + 1;
+  if (m->n_rows) {
+    KLAUNCH(k_frsp_prepare, dim3(nblk(span, 256)), dim3(256), 0, c->stream, (const u32*)m->row_ptr, (const u32*)m->val, m->val, m->tile_row, m->flag, m->n_rows, m->nnz, tiles,
+            (unsigned)(FrSpmvShape().block * FrSpmvShape().chunk));
+    LAUNCHCHK();
+  }
+  u32 flag[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(flag, m->flag, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  m->has_empty = flag[1] != 0;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_matrix_upload(blsgpu_ctx* c, size_t n_rows, size_t n_cols, const uint32_t* row_ptr, const uint32_t* col, const uint64_t* val, blsgpu_fr_matrix** out) { CTX_CLAIM(c);
+  if (int rc = frm_sizes_check(c, n_rows, n_cols, row_ptr, out)) return rc;
+  std::string what;
+  if (!frm_validate_host(n_rows, n_cols, row_ptr, col, (const uint32_t*)val, &what)) { g_err = what; return BLSGPU_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  blsgpu_fr_matrix* m = new blsgpu_fr_matrix();
+  m->device = c->device; m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = row_ptr[n_rows];
+  int rc = frm_alloc(c, m);
+  if (!rc) rc = staged_upload(c, m->row_ptr, row_ptr, (n_rows + 1) * 4);
+  if (!rc && m->nnz) rc = staged_upload(c, m->col, col, m->nnz * 4);
+  if (!rc && m->nnz) rc = staged_upload(c, m->val, val, m->nnz * 32);
+  if (!rc) rc = frm_prepare(c, m);
+  if (rc) { (void)hipStreamSynchronize(c->stream); frm_drop(m); return rc; }
+  *out = m;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_matrix_from_device(blsgpu_ctx* c, size_t n_rows, size_t n_cols, const void* d_row_ptr, const void* d_col, const void* d_val, blsgpu_fr_matrix** out) { CTX_CLAIM(c);
+  if (int rc = frm_sizes_check(c, n_rows, n_cols, d_row_ptr, out)) return rc;
+  if ((((uintptr_t)d_row_ptr | (uintptr_t)d_col) & 3) || ((uintptr_t)d_val & 15)) return bad("fr_matrix_from_device: d_val must be 16-byte aligned, d_row_ptr and d_col 4-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  u32 ends[2] = {0, 0};                          // row_ptr[0], row_ptr[n_rows]: the latter IS the number of non-zeros
+  HIPCHK(hipMemcpyAsync(&ends[0], d_row_ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&ends[1], (const u32*)d_row_ptr + n_rows, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (ends[0] != 0) return bad("fr_matrix: row_ptr[0] must be 0");
+  const size_t nnz = ends[1];
+  if (nnz > FRSP_MAX) return bad("fr_matrix: row_ptr[n_rows] (the number of non-zeros) must not exceed 2^28");
+  if (nnz && (!d_col || !d_val)) return bad("fr_matrix: NULL col / val with non-zeros to read");
+  blsgpu_fr_matrix* m = new blsgpu_fr_matrix();
+  m->device = c->device; m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
+  auto build = [&]() -> int {
+    if (int rc = frm_alloc(c, m)) return rc;
+    const size_t span = nnz > n_rows ? nnz : n_rows;
+    u32 flag = 0;
+    if (span) {
+      KLAUNCH(k_frsp_validate, dim3(nblk(span, 256)), dim3(256), 0, c->stream, (const u32*)d_row_ptr, (const u32*)d_col, (const u32*)d_val, n_rows, n_cols, nnz, m->flag);
+      LAUNCHCHK();
+      HIPCHK(hipMemcpyAsync(&flag, m->flag, 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (flag) {                                  // refused: fetch the arrays to NAME the first offender (the slow path of a call that fails anyway)
+      std::vector<uint32_t> rp(n_rows + 1), cl(nnz), vl(nnz * 8);
+      HIPCHK(hipMemcpy(rp.data(), d_row_ptr, (n_rows + 1) * 4, hipMemcpyDeviceToHost));
+      if (nnz) { HIPCHK(hipMemcpy(cl.data(), d_col, nnz * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(vl.data(), d_val, nnz * 32, hipMemcpyDeviceToHost)); }
+      std::string what;
+      if (frm_validate_host(n_rows, n_cols, rp.data(), cl.data(), vl.data(), &what)) what = "fr_matrix: the matrix did not pass the device check";
+      g_err = what;
+      return BLSGPU_ERR_ARG;
+    }
+    HIPCHK(hipMemcpyAsync(m->row_ptr, d_row_ptr, (n_rows + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (nnz) {
+      HIPCHK(hipMemcpyAsync(m->col, d_col, nnz * 4, hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(m->val, d_val, nnz * 32, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return frm_prepare(c, m);
+  };
+  if (int rc = build()) { (void)hipStreamSynchronize(c->stream); frm_drop(m); return rc; }
+  *out = m;
+  return BLSGPU_OK;
+}
+extern "C" size_t blsgpu_fr_matrix_rows(const blsgpu_fr_matrix* m) { return m ? m->n_rows : 0; }
+extern "C" size_t blsgpu_fr_matrix_cols(const blsgpu_fr_matrix* m) { return m ? m->n_cols : 0; }
+extern "C" size_t blsgpu_fr_matrix_nnz(const blsgpu_fr_matrix* m) { return m ? m->nnz : 0; }
+extern "C" void blsgpu_fr_matrix_free(blsgpu_fr_matrix* m) {
+  if (!m) return;
+  hipSetDevice(m->device);
+  hipDeviceSynchronize();                  // an asynchronous product may still be reading the matrix
+  frm_drop(m);
+}
+// every argument check of both product forms, before anything is staged, reserved or launched.  *work: there is something to do.
+static int fr_spmv_check(blsgpu_ctx* c, const blsgpu_fr_matrix* m, const void* x, size_t k, const void* out, bool device, bool* work) {
+  *work = false;
+  if (!c) return bad("fr_spmv: NULL context");
+  if (!m) return bad("fr_spmv: NULL matrix");
+  if (m->device != c->device) return bad("fr_spmv: the matrix lives on another device than the context");
+  const size_t big = m->n_rows > m->n_cols ? m->n_rows : m->n_cols;
+  if (big && k > FRSP_MAX / big) return bad("fr_spmv: k * max(n_rows, n_cols) must not exceed 2^28");
+  if (!k || !m->n_rows) return BLSGPU_OK;
+  if (!out || (m->n_cols && !x)) return bad("fr_spmv: NULL x / out with work to do");
+  if (device && (((uintptr_t)x | (uintptr_t)out) & 15)) return bad("fr_spmv_device: device pointers must be 16-byte aligned");
+  const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out;
+  if (xa < oa + k * m->n_rows * 32 && oa < xa + k * m->n_cols * 32) return bad("fr_spmv: out overlaps x (the gather would race with the stores)");
+  *work = true;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_spmv_device(blsgpu_ctx* c, const blsgpu_fr_matrix* m, const void* d_x, size_t k, void* d_out) { CTX_CLAIM(c);
+  bool work;
+  if (int rc = fr_spmv_check(c, m, d_x, k, d_out, true, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const FrSpmvShape shape;
+  if (!c->frsp_lds_ready) {                // more than 64 KB of dynamic LDS per workgroup has to be asked for: once per context
+    HIPCHK(hipFuncSetAttribute((const void*)k_frsp_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)frsp_lds_bytes(shape)));
+    c->frsp_lds_ready = true;
+  }
+  const FrSpmvPlan plan = fr_spmv_plan(m->n_rows, m->nnz, k, m->has_empty, shape);
+  if (c->frsp_head.reserve(plan.rec_scalars * 32) || c->frsp_tail.reserve(plan.rec_scalars * 32) || c->frsp_meta.reserve(plan.meta_words * 4)) {
+    g_err = "hipMalloc(fr spmv scratch) failed"; return BLSGPU_ERR_HIP;
+  }
+  hipStream_t st = c->stream;
+  const u32* x = (const u32*)d_x; u32* out = (u32*)d_out;
+  for (int i = 0; i < plan.n_steps; i++) {
+    const FrSpmvStep& s = plan.step[i];
+    switch (s.kernel) {
+      case FRSP_K_FILL:
+        HIPCHK(hipMemsetAsync(out, 0, s.items * 32, st));
+        break;
+      case FRSP_K_TILE:
+        KLAUNCH(k_frsp_tile, dim3(s.grid), dim3(s.block), s.lds, st, (const u32*)m->row_ptr, (const u32*)m->col, (const u32*)m->val, (const u32*)m->tile_row, m->n_rows, m->n_cols, m->nnz,
+                x, out, k, (unsigned)shape.chunk, c->frsp_head.as<u32>(), c->frsp_tail.as<u32>(), c->frsp_meta.as<u32>());
+        break;
+      default:
+        KLAUNCH(k_frsp_fixup, dim3(s.grid), dim3(s.block), s.lds, st, (const u32*)m->row_ptr, (const u32*)c->frsp_head.as<u32>(), (const u32*)c->frsp_tail.as<u32>(),
+                (const u32*)c->frsp_meta.as<u32>(), s.items, m->n_rows, k, (unsigned)plan.tile, out);
+        break;
+    }
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_spmv(blsgpu_ctx* c, const blsgpu_fr_matrix* m, const uint64_t* x, size_t k, uint64_t* out) { CTX_CLAIM(c);
+  bool work;
+  if (int rc = fr_spmv_check(c, m, x, k, out, false, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HostCall h(c);
+  void* dx = h.in(c->io_a, x, k * m->n_cols * 32);
+  void* o = h.out(c->io_out, out, k * m->n_rows * 32);
+  if (h.rc) return h.rc;
+  if (!dx) { if (!h.reserve(c->io_a, 16)) return h.rc; dx = c->io_a.p; }      // n_cols == 0: nothing is gathered, but the device form wants a pointer
+  return h.finish(blsgpu_fr_spmv_device(c, m, dx, k, o));
 }
 
 // ---------------------------------------------------------------------------------------------------

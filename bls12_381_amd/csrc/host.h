@@ -219,6 +219,8 @@ struct blsgpu_ctx {
   uint64_t fr_cs_g[2][4] = {};
   hipEvent_t ev_fr_cs[2] = {};          // as ev_fr
   DevBuf frs_agg[2], frs_carry[2], frs_lane;      // blsgpu_fr_scan_many: aggregate records of the tiles / of groups of tiles, their exclusive scans, the lanes' prefixes (fr_scan_plan.h)
+  DevBuf frsp_head, frsp_tail, frsp_meta;         // blsgpu_fr_spmv: the HEAD / TAIL sums and the META word of every tile (fr_spmv_plan.h)
+  bool frsp_lds_ready = false;          // ... and its tile kernel's dynamic LDS
   bool frs_lds_ready = false;           // the scan kernels' dynamic LDS (more than the 64 KB a kernel gets unasked) has been granted on this device
 };
 
@@ -255,6 +257,16 @@ struct ScalarFormScope {
 
 // G2Prepared resident on the device (api_pairing.hip; the bulk verification of api_aux.hip keeps one)
 struct blsgpu_g2_prepared { int device = 0; size_t n = 0; u32* tab = nullptr; uint8_t* inf = nullptr; hipEvent_t ev_ready = nullptr; };
+
+// a CSR matrix over Fr resident on the device (api_aux.hip: blsgpu_fr_matrix_upload / _from_device; fr_spmv.hip.h)
+struct blsgpu_fr_matrix {
+  int device = 0; size_t n_rows = 0, n_cols = 0, nnz = 0;
+  u32* row_ptr = nullptr; u32* col = nullptr;      // the caller's arrays, validated
+  u32* val = nullptr;                              // 2^5 val: the factor the lazy product of fr.hip.h leaves behind is folded in once
+  u32* tile_row = nullptr;                         // the row of every tile's first entry (+ one closing word)
+  u32* flag = nullptr;                             // [0] the validation kernel's verdict, [1] a row is empty
+  bool has_empty = false;                          // a row without entries: the product zeroes its output first
+};
 
 // ---- functions that cross translation units -------------------------------------------------------------------------------------
 int staged_upload(blsgpu_ctx* c, void* dst, const void* src, size_t bytes);      // api_ctx.hip

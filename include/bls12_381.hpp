@@ -360,6 +360,35 @@ inline std::vector<FrLimbs> fr_batch_invert(const std::vector<FrLimbs>& v, std::
   check(blsgpu_fr_batch_invert(Context::instance().handle(), v[0].data(), v.size(), out[0].data(), nonzero ? nonzero->data() : nullptr), "fr_batch_invert");
   return out;
 }
+// A CSR matrix over Fr resident on the device (blsgpu_fr_matrix): validated and planned once, multiplied many times.  row_ptr has
+// n_rows + 1 entries from 0 to nnz = col.size() = val.size(); col[p] < n_cols; repeated columns inside a row add; rows may be empty.
+class FrMatrix {
+ public:
+  FrMatrix(const std::vector<uint32_t>& row_ptr, const std::vector<uint32_t>& col, const std::vector<FrLimbs>& val, size_t n_cols) {
+    if (row_ptr.empty() || col.size() != val.size() || row_ptr.back() != col.size()) throw std::invalid_argument("FrMatrix: row_ptr must run from 0 to col.size() == val.size()");
+    check(blsgpu_fr_matrix_upload(Context::instance().handle(), row_ptr.size() - 1, n_cols, row_ptr.data(), col.data(), val.empty() ? nullptr : val[0].data(), &m_), "fr_matrix_upload");
+  }
+  ~FrMatrix() { blsgpu_fr_matrix_free(m_); }
+  FrMatrix(const FrMatrix&) = delete;
+  FrMatrix& operator=(const FrMatrix&) = delete;
+  FrMatrix(FrMatrix&& o) noexcept : m_(o.m_) { o.m_ = nullptr; }
+  size_t rows() const { return blsgpu_fr_matrix_rows(m_); }
+  size_t cols() const { return blsgpu_fr_matrix_cols(m_); }
+  size_t nnz() const { return blsgpu_fr_matrix_nnz(m_); }
+  const blsgpu_fr_matrix* handle() const { return m_; }
+ private:
+  blsgpu_fr_matrix* m_ = nullptr;
+};
+// out[v][i] = sum over row i's entries of val[p] * x[v][col[p]] for k = x.size() / m.cols() right-hand sides laid end to end; stack A, B and
+// C into one matrix of 3n rows to apply all three in one call
+inline std::vector<FrLimbs> fr_spmv(const FrMatrix& m, const std::vector<FrLimbs>& x) {
+  if (m.cols() == 0 || x.size() % m.cols()) throw std::invalid_argument("fr_spmv: x must be k vectors of m.cols() scalars");
+  const size_t k = x.size() / m.cols();
+  std::vector<FrLimbs> out(k * m.rows());
+  if (out.empty()) return out;
+  check(blsgpu_fr_spmv(Context::instance().handle(), m.handle(), x[0].data(), k, out[0].data()), "fr_spmv");
+  return out;
+}
 // The same transform over group elements: k vectors of p.size() / k points each in one call, in place (vector i = elements
 // [i n, (i+1) n)); Y[m] = sum_j [w^(jm)] P[j] with the w of fr_ntt, the inverse scaled by n^-1 (include/bls12_381_hip.h).  Every point
 // must lie in the prime-order subgroup.  The overloads on affine points lift them (Z = 1, the identity (0 : 1 : 0)) and return the result.

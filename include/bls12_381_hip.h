@@ -542,6 +542,37 @@ int blsgpu_fr_scan_many_device(blsgpu_ctx* ctx, int op, int exclusive, const voi
  * out == in, asynchrony and refusals as for blsgpu_fr_scan_many. */
 int blsgpu_fr_batch_invert(blsgpu_ctx* ctx, const uint64_t* values, size_t n, uint64_t* out, uint8_t* nonzero_flags);
 int blsgpu_fr_batch_invert_device(blsgpu_ctx* ctx, const void* d_in, size_t n, void* d_out, void* d_nonzero_flags);
+/* Sparse matrix-vector products over Fr: the step a = A z, b = B z, c = C z in front of a Groth16 / Marlin / PLONK-style prover's
+ * transforms -- each output a short linear combination of gathered witness entries with fixed per-circuit coefficients.  The matrix is
+ * fixed per circuit and reused for every proof, exactly as an SRS is, so it is a resident handle like blsgpu_bases: upload, validate
+ * and plan once, multiply many times.  To apply A, B and C in one call, stack their rows into ONE matrix of 3n rows.
+ * Format: CSR.  row_ptr has n_rows + 1 entries, row_ptr[0] = 0, non-decreasing; row_ptr[n_rows] IS the number of non-zeros nnz, and
+ * col / val hold that many entries (the caller's promise, as every array length is): col[p] < n_cols, val[p] = the four canonical
+ * Montgomery limbs of a `Scalar`.  Columns inside a row may come in any order and may repeat (repeats add); rows may be empty.
+ * n_rows, n_cols, nnz <= 2^28.  The handle keeps its own device copy: the caller's arrays are free again when the call returns.
+ * Validation happens here, once, before a handle exists (the products gather on trust and never re-validate): row_ptr's first entry and
+ * order, nnz's range, every col, every val below r -- on the host for the host form, by a kernel for the device form (upload is a setup
+ * call and synchronises the context's stream).  A bad matrix is BLSGPU_ERR_ARG, *out stays NULL, and blsgpu_last_error names the first
+ * offending row or position.  d_val must be 16-byte aligned.  blsgpu_fr_matrix_free follows the rules of blsgpu_bases_free (it waits for
+ * the device; NULL is allowed). */
+typedef struct blsgpu_fr_matrix blsgpu_fr_matrix;
+int blsgpu_fr_matrix_upload(blsgpu_ctx* ctx, size_t n_rows, size_t n_cols, const uint32_t* row_ptr, const uint32_t* col, const uint64_t* val, blsgpu_fr_matrix** out);
+int blsgpu_fr_matrix_from_device(blsgpu_ctx* ctx, size_t n_rows, size_t n_cols, const void* d_row_ptr, const void* d_col, const void* d_val, blsgpu_fr_matrix** out);
+size_t blsgpu_fr_matrix_rows(const blsgpu_fr_matrix* m);
+size_t blsgpu_fr_matrix_cols(const blsgpu_fr_matrix* m);
+size_t blsgpu_fr_matrix_nnz(const blsgpu_fr_matrix* m);
+void blsgpu_fr_matrix_free(blsgpu_fr_matrix* m);
+/* out[v][i] = sum_{p in [row_ptr[i], row_ptr[i+1])} val[p] * x[v][col[p]]  for k right-hand sides laid end to end: x is k x n_cols and
+ * out is k x n_rows scalars (the layout of blsgpu_fr_ntt_many), built on `Scalar`'s mul / add (scalar.rs:452-503, :435-449; the
+ * reference crate has no such operation).  x canonical is a precondition; out is canonical, an empty row gives 0, nnz == 0 writes
+ * zeros.  The non-zeros, not the rows, are tiled, so a few rows of 10^5 entries among millions of short ones cost nothing extra; the
+ * matrix is read once for all k vectors; results are limb-identical from run to run (no atomics).  k * max(n_rows, n_cols) <= 2^28;
+ * k == 0 and n_rows == 0 are no-ops.  Device pointers must be 16-byte aligned.  The device form is asynchronous on the context's
+ * stream; its scratch (64 bytes per 2048 non-zeros and vector) is its own and is not shared with pipelined *_msm_device calls in
+ * flight.  BLSGPU_ERR_ARG (nothing staged or launched): a NULL matrix, NULL x / out with work to do, k * n out of range (64-bit
+ * overflow included), a misaligned device pointer, ANY overlap of the out range with the x range (the gather would race). */
+int blsgpu_fr_spmv(blsgpu_ctx* ctx, const blsgpu_fr_matrix* m, const uint64_t* x, size_t k, uint64_t* out);
+int blsgpu_fr_spmv_device(blsgpu_ctx* ctx, const blsgpu_fr_matrix* m, const void* d_x, size_t k, void* d_out);
 /* The same radix-2 transform over GROUP elements: k vectors of 2^log_n G1 (G2) points each, laid end to end, in place, natural order in
  * and out:
  *   forward  Y[m] = sum_j [w^(jm)] P[j],   inverse  P[j] = [n^-1] sum_m [w^(-jm)] Y[m],   w as for blsgpu_fr_ntt

@@ -166,6 +166,14 @@ extern "C" {
     pub fn blsgpu_fr_scan_many_device(ctx: *mut BlsgpuCtx, op: c_int, exclusive: c_int, d_in: *const c_void, len: usize, k: usize, d_points: *const c_void, d_out: *mut c_void) -> c_int;
     pub fn blsgpu_fr_batch_invert(ctx: *mut BlsgpuCtx, values: *const u64, n: usize, out: *mut u64, nonzero_flags: *mut u8) -> c_int;
     pub fn blsgpu_fr_batch_invert_device(ctx: *mut BlsgpuCtx, d_in: *const c_void, n: usize, d_out: *mut c_void, d_nonzero_flags: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_matrix_upload(ctx: *mut BlsgpuCtx, n_rows: usize, n_cols: usize, row_ptr: *const u32, col: *const u32, val: *const u64, out: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_matrix_from_device(ctx: *mut BlsgpuCtx, n_rows: usize, n_cols: usize, d_row_ptr: *const c_void, d_col: *const c_void, d_val: *const c_void, out: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_matrix_rows(m: *const c_void) -> usize;
+    pub fn blsgpu_fr_matrix_cols(m: *const c_void) -> usize;
+    pub fn blsgpu_fr_matrix_nnz(m: *const c_void) -> usize;
+    pub fn blsgpu_fr_matrix_free(m: *mut c_void);
+    pub fn blsgpu_fr_spmv(ctx: *mut BlsgpuCtx, m: *const c_void, x: *const u64, k: usize, out: *mut u64) -> c_int;
+    pub fn blsgpu_fr_spmv_device(ctx: *mut BlsgpuCtx, m: *const c_void, d_x: *const c_void, k: usize, d_out: *mut c_void) -> c_int;
     pub fn blsgpu_g1_ntt_many(ctx: *mut BlsgpuCtx, xyz: *mut u64, log_n: c_int, k: usize, inverse: c_int) -> c_int;
     pub fn blsgpu_g2_ntt_many(ctx: *mut BlsgpuCtx, xyz: *mut u64, log_n: c_int, k: usize, inverse: c_int) -> c_int;
     pub fn blsgpu_g1_ntt_many_device(ctx: *mut BlsgpuCtx, d_xyz: *mut c_void, log_n: c_int, k: usize, inverse: c_int) -> c_int;

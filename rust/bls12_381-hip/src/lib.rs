@@ -23,7 +23,7 @@
 pub mod ffi;
 
 use bls12_381::{G1Affine, G1Projective, G2Affine, G2Projective, Scalar};
-use core::ffi::{c_int, CStr};
+use core::ffi::{c_int, c_void, CStr};
 use group::Curve;
 
 /// Error of a library call: the status code and `blsgpu_last_error()`.
@@ -231,6 +231,40 @@ pub fn fr_batch_invert(gpu: &Gpu, values: &[Scalar]) -> Result<Vec<Option<Scalar
     let (mut out, mut flags) = (vec![0u64; input.len()], vec![0u8; values.len()]);
     check(unsafe { ffi::blsgpu_fr_batch_invert(gpu.ctx, input.as_ptr(), values.len(), out.as_mut_ptr(), flags.as_mut_ptr()) })?;
     Ok(limbs_scalars(gpu, &out)?.into_iter().zip(flags).map(|(s, f)| if f != 0 { Some(s) } else { None }).collect())
+}
+/// A CSR matrix over `Scalar` resident on the GPU (`blsgpu_fr_matrix`): a circuit's constraint matrices, uploaded, validated and planned
+/// once and multiplied with every proof's witness.  The FFI layer sees the handle as an untyped pointer; this is its type.
+pub struct FrMatrix { handle: *mut c_void, rows: usize, cols: usize }
+impl FrMatrix {
+    /// `row_ptr` has `n_rows + 1` entries from 0 to `col.len() == val.len()`, non-decreasing; `col[p] < n_cols`.  Columns inside a row may
+    /// repeat (they add) and come in any order; rows may be empty.  A malformed matrix is an `Err` naming the first offending row or position.
+    pub fn new(gpu: &Gpu, row_ptr: &[u32], col: &[u32], val: &[Scalar], n_cols: usize) -> Result<FrMatrix, Error> {
+        assert!(!row_ptr.is_empty() && col.len() == val.len() && *row_ptr.last().unwrap() as usize == col.len());
+        let limbs = scalar_limbs(gpu, val)?;
+        let mut handle: *mut c_void = std::ptr::null_mut();
+        check(unsafe {
+            ffi::blsgpu_fr_matrix_upload(gpu.ctx, row_ptr.len() - 1, n_cols, row_ptr.as_ptr(), col.as_ptr(), limbs.as_ptr(),
+                                         &mut handle as *mut *mut c_void as *mut c_void)
+        })?;
+        Ok(FrMatrix { handle, rows: row_ptr.len() - 1, cols: n_cols })
+    }
+    pub fn rows(&self) -> usize { self.rows }
+    pub fn cols(&self) -> usize { self.cols }
+    pub fn nnz(&self) -> usize { unsafe { ffi::blsgpu_fr_matrix_nnz(self.handle as *const c_void) } }
+}
+impl Drop for FrMatrix {
+    fn drop(&mut self) { unsafe { ffi::blsgpu_fr_matrix_free(self.handle) } }
+}
+/// `out[v][i] = sum over row i's entries of val[p] * x[v][col[p]]` for `k = x.len() / m.cols()` right-hand sides laid end to end -- what a
+/// caller writes as `a = A z, b = B z, c = C z` row by row; stack A, B and C into one matrix of `3n` rows to apply all three in one call.
+pub fn fr_spmv(gpu: &Gpu, m: &FrMatrix, x: &[Scalar]) -> Result<Vec<Scalar>, Error> {
+    assert!(m.cols > 0 && x.len() % m.cols == 0);
+    let k = x.len() / m.cols;
+    if k == 0 || m.rows == 0 { return Ok(Vec::new()); }
+    let input = scalar_limbs(gpu, x)?;
+    let mut out = vec![0u64; k * m.rows * 4];
+    check(unsafe { ffi::blsgpu_fr_spmv(gpu.ctx, m.handle as *const c_void, input.as_ptr(), k, out.as_mut_ptr()) })?;
+    limbs_scalars(gpu, &out)
 }
 fn split72(flat: Vec<u64>) -> Vec<GtLimbs> {
     flat.chunks_exact(72).map(|c| { let mut a = [0u64; 72]; a.copy_from_slice(c); GtLimbs(a) }).collect()
