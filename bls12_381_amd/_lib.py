@@ -80,6 +80,20 @@ SIGNATURES = {
     "blsgpu_fr_matrix_free": (None, [c_vp]),
     "blsgpu_fr_spmv": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),
     "blsgpu_fr_spmv_device": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_fr_mle_fold": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_mle_fold_device": (c_int, [c_vp, c_vp, c_sz, c_int, c_sz, c_vp, c_vp, c_sz]),
+    "blsgpu_fr_eq_table": (c_int, [c_vp, c_vp, c_int, c_vp]),
+    "blsgpu_fr_eq_table_device": (c_int, [c_vp, c_vp, c_int, c_vp]),
+    "blsgpu_fr_mle_eval": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_mle_eval_device": (c_int, [c_vp, c_vp, c_sz, c_int, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_sumcheck_round_device": (c_int, [c_vp, c_vp, c_sz, c_int, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "blsgpu_fr_sumcheck_begin": (c_int, [c_vp, c_vp, c_int, c_sz, c_sz, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "blsgpu_fr_sumcheck_begin_device": (c_int, [c_vp, c_vp, c_sz, c_int, c_sz, c_sz, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "blsgpu_fr_sumcheck_vars_left": (c_int, [c_vp]),
+    "blsgpu_fr_sumcheck_degree": (c_int, [c_vp]),
+    "blsgpu_fr_sumcheck_round": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "blsgpu_fr_sumcheck_finish": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "blsgpu_fr_sumcheck_free": (None, [c_vp]),
     "blsgpu_g1_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),
     "blsgpu_g2_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),
     "blsgpu_g1_ntt_many_device": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),

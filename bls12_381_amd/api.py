@@ -207,6 +207,71 @@ class FrMatrix:
             pass
 
 
+def _term_program(terms):
+    """[(coefficient as a Python int in [0, r) or four Montgomery limbs, [table indices]), ...] -> (n_terms, term_ptr u32, term_tab u8, coef (n, 4) u64):
+    the term program of include/bls12_381_hip.h (the library validates it)"""
+    terms = list(terms)
+    ptr, tab = [0], []
+    coef = np.zeros((max(len(terms), 1), 4), dtype=np.uint64)
+    for t, (c, idx) in enumerate(terms):
+        idx = [int(i) for i in idx]
+        if any(not 0 <= i < 256 for i in idx):
+            raise ValueError("fr_sumcheck: a table index is out of range")
+        tab += idx
+        ptr.append(len(tab))
+        coef[t] = _point_limbs(c if isinstance(c, (int, np.integer)) else np.asarray(c), 1)[0]
+    return len(terms), np.array(ptr, dtype=np.uint32), np.array(tab if tab else [0], dtype=np.uint8), coef
+
+
+def fr_limbs_to_int(limbs):
+    """four Montgomery limbs of a canonical Scalar -> the Python int it stands for"""
+    v = 0
+    for i, w in enumerate(np.asarray(limbs, dtype=np.uint64).reshape(-1)[:4]):
+        v |= int(w) << (64 * i)
+    return v * pow(1 << 256, -1, R_ORDER) % R_ORDER
+
+
+class FrSumcheck:
+    """A sumcheck in progress (`blsgpu_fr_sumcheck`): the tables live in device memory of the handle's own and are consumed by the rounds.
+    Order: round() -> evaluations, round(r_1) ..., while vars_left > 1, then finish(r_m) -> the k values f_j(point)."""
+
+    def __init__(self, ctx, handle, k):
+        self.ctx, self.handle, self.k = ctx, handle, k
+
+    @property
+    def vars_left(self):
+        return int(self.ctx.lib.blsgpu_fr_sumcheck_vars_left(self.handle)) if self.handle else 0
+
+    @property
+    def degree(self):
+        return int(self.ctx.lib.blsgpu_fr_sumcheck_degree(self.handle)) if self.handle else 0
+
+    def round(self, r_prev=None):
+        """the round polynomial's values at 0 .. degree as a (degree + 1, 4) array of Montgomery limbs; r_prev: None in the first round,
+        afterwards the previous round's challenge (a Python int in [0, r) or four Montgomery limbs), which is folded in first"""
+        out = np.zeros((self.degree + 1, 4), dtype=np.uint64)
+        r = None if r_prev is None else _point_limbs(r_prev, 1)
+        check(self.ctx.lib.blsgpu_fr_sumcheck_round(self.ctx.h, self.handle, _ptr(r), _ptr(out)), "fr_sumcheck_round")
+        return out
+
+    def finish(self, r):
+        """binds the last variable at r; returns the (k, 4) values f_j(point), point[b] = the challenge of round m - b"""
+        out = np.zeros((self.k, 4), dtype=np.uint64)
+        check(self.ctx.lib.blsgpu_fr_sumcheck_finish(self.ctx.h, self.handle, _ptr(_point_limbs(r, 1)), _ptr(out)), "fr_sumcheck_finish")
+        return out
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_fr_sumcheck_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PreparedG2Table:
     """m `G2Prepared` values resident on the device (`blsgpu_g2_prepared`): the 68 line-coefficient triples of each point
     (pairings.rs:487-546), named by index in the `*_prepared` Miller loops."""
@@ -769,6 +834,107 @@ class Context:
         """the same on k * n_cols scalars in device memory -> k * n_rows scalars at d_out (no overlap with d_x), asynchronous on the
         context's stream"""
         check(self.lib.blsgpu_fr_spmv_device(self.h, m.handle, d_x, k, d_out), "fr_spmv_device")
+
+    @staticmethod
+    def _mle_tables(values, what):
+        """(k, 2^m, 4) or (2^m, 4) Montgomery limbs -> (array (k, 2^m, 4), m, was a single table)"""
+        v = np.ascontiguousarray(np.array(values, dtype=np.uint64))
+        one = v.ndim == 2
+        if one:
+            v = v.reshape((1,) + v.shape)
+        if v.ndim != 3 or v.shape[2] != 4:
+            raise ValueError(what + ": expected a (k, 2^m, 4) or (2^m, 4) array")
+        n = v.shape[1]
+        if v.shape[0] and (n == 0 or n & (n - 1)):
+            raise ValueError(what + ": the table length must be a power of two")
+        return v, max(n.bit_length() - 1, 0), one
+
+    def fr_mle_fold(self, tables, r):
+        """binds the TOP variable of k multilinear tables at r (include/bls12_381_hip.h): `tables` is a (k, 2^m, 4) u64 array of
+        Montgomery limbs ((2^m, 4) is k = 1), m >= 1, r a Python int in [0, r) or four Montgomery limbs -> a new (k, 2^(m-1), 4) array,
+        out[j][i] = f_j[i] + r (f_j[i + 2^(m-1)] - f_j[i])"""
+        v, m, one = self._mle_tables(tables, "fr_mle_fold")
+        out = np.zeros((v.shape[0], v.shape[1] // 2, 4), dtype=np.uint64)
+        check(self.lib.blsgpu_fr_mle_fold(self.h, _ptr(v), m, v.shape[0], _ptr(_point_limbs(r, 1)), _ptr(out)), "fr_mle_fold")
+        return out[0] if one else out
+
+    def fr_mle_fold_device(self, d_in, pitch_in, m, k, d_r, d_out, pitch_out):
+        """the same on k tables of 2^m scalars in device memory, table j at j * pitch scalars; d_r: one scalar in device memory;
+        d_out == d_in with equal pitches folds in place; asynchronous on the context's stream"""
+        check(self.lib.blsgpu_fr_mle_fold_device(self.h, d_in, pitch_in, m, k, d_r, d_out, pitch_out), "fr_mle_fold_device")
+
+    def fr_eq_table(self, point):
+        """the table eq(point)[i] = prod_b (bit b of i ? point[b] : 1 - point[b]) as a (2^m, 4) array of Montgomery limbs; point: m Python
+        ints in [0, r) or an (m, 4) array of Montgomery limbs (m = 0: the table [1])"""
+        m = len(point)
+        pts = _point_limbs(list(point) if isinstance(point, (list, tuple)) else point, m) if m else None
+        out = np.zeros((1 << m, 4), dtype=np.uint64)
+        check(self.lib.blsgpu_fr_eq_table(self.h, _ptr(pts), m, _ptr(out)), "fr_eq_table")
+        return out
+
+    def fr_eq_table_device(self, d_point, m, d_out):
+        """the same from m scalars in device memory into 2^m scalars at d_out, asynchronous on the context's stream"""
+        check(self.lib.blsgpu_fr_eq_table_device(self.h, d_point, m, d_out), "fr_eq_table_device")
+
+    def fr_mle_eval(self, tables, point):
+        """f_j(point) for k multilinear tables ((k, 2^m, 4) or (2^m, 4) Montgomery limbs), point[b] the value of x_b (m Python ints or an
+        (m, 4) array) -> (k, 4) (or (4,)) Montgomery limbs"""
+        v, m, one = self._mle_tables(tables, "fr_mle_eval")
+        if len(point) != m:
+            raise ValueError("fr_mle_eval: the point needs one coordinate per variable")
+        pts = _point_limbs(list(point) if isinstance(point, (list, tuple)) else point, m) if m else None
+        out = np.zeros((v.shape[0], 4), dtype=np.uint64)
+        check(self.lib.blsgpu_fr_mle_eval(self.h, _ptr(v), m, v.shape[0], _ptr(pts), _ptr(out)), "fr_mle_eval")
+        return out[0] if one else out
+
+    def fr_mle_eval_device(self, d_tables, pitch, m, k, d_point, d_out):
+        """the same on tables in device memory (not written) -> k scalars at d_out, asynchronous on the context's stream"""
+        check(self.lib.blsgpu_fr_mle_eval_device(self.h, d_tables, pitch, m, k, d_point, d_out), "fr_mle_eval_device")
+
+    def fr_sumcheck_round_device(self, d_tables, pitch, m, k, terms, d_evals, d_r_prev=None):
+        """one round polynomial of sum_x sum_t coef_t prod_e f_e(x) over k tables in device memory: terms is a list of
+        (coefficient, [table indices]); d_evals receives degree + 1 scalars.  With d_r_prev (one scalar in device memory) the tables are
+        first folded at it IN PLACE and the evaluations are those of the folded tables (include/bls12_381_hip.h).  Asynchronous."""
+        n, ptr, tab, coef = _term_program(terms)
+        check(self.lib.blsgpu_fr_sumcheck_round_device(self.h, d_tables, pitch, m, k, n, _ptr(ptr), _ptr(tab), _ptr(coef), d_r_prev, d_evals), "fr_sumcheck_round_device")
+
+    def fr_sumcheck(self, tables, terms):
+        """begins a sumcheck over k tables ((k, 2^m, 4) Montgomery limbs, copied to the device) and the summand
+        sum_t coef_t prod_e f_e: terms is a list of (coefficient as a Python int in [0, r) or four Montgomery limbs, [table indices]).
+        Returns an FrSumcheck (.round(r_prev=None), .finish(r), .vars_left, .degree, .close())."""
+        v, m, _ = self._mle_tables(tables, "fr_sumcheck")
+        n, ptr, tab, coef = _term_program(terms)
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_sumcheck_begin(self.h, _ptr(v), m, v.shape[0], n, _ptr(ptr), _ptr(tab), _ptr(coef), ctypes.byref(h)), "fr_sumcheck")
+        return FrSumcheck(self, h, v.shape[0])
+
+    def fr_sumcheck_device(self, d_tables, pitch, m, k, terms):
+        """the same from k tables of 2^m scalars in device memory, table j at j * pitch scalars (copied: the caller's stay as they are)"""
+        n, ptr, tab, coef = _term_program(terms)
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_sumcheck_begin_device(self.h, d_tables, pitch, m, k, n, _ptr(ptr), _ptr(tab), _ptr(coef), ctypes.byref(h)), "fr_sumcheck_device")
+        return FrSumcheck(self, h, k)
+
+    def fr_sumcheck_prove(self, tables, terms, challenge):
+        """drives every round of a sumcheck: challenge(round_index, evals_as_ints) -> int is called with round_index = 1 .. m and that
+        round's evaluations at 0 .. degree as Python ints, and returns the round's challenge.  Returns (round_evals, point, values):
+        the list of per-round evaluation lists, the point with point[b] the value of x_b, and the (k, 4) Montgomery limbs f_j(point)."""
+        return self._sumcheck_drive(self.fr_sumcheck(tables, terms), challenge)
+
+    @staticmethod
+    def _sumcheck_drive(sc, challenge):
+        try:
+            m = sc.vars_left
+            rounds, chal, r = [], [], None
+            for s in range(1, m + 1):
+                ev = [fr_limbs_to_int(e) for e in sc.round(r)]
+                rounds.append(ev)
+                r = int(challenge(s, ev)) % R_ORDER
+                chal.append(r)
+            values = sc.finish(r)
+            return rounds, chal[::-1], values
+        finally:
+            sc.close()
 
     def g_ntt_many(self, group, points, inverse=False):
         """k independent radix-2 transforms over GROUP elements in one call (include/bls12_381_hip.h: Y[m] = sum_j [w^(jm)] P[j], the w of

@@ -5,6 +5,7 @@
 #include "fr_plan.h"
 #include "fr_scan.hip.h"
 #include "fr_spmv.hip.h"
+#include "fr_mle.hip.h"
 #include "h2c.hip.h"
 #include "expand_kernels.hip.h"
 #include "codec.hip.h"
@@ -764,6 +765,284 @@ extern "C" int blsgpu_fr_spmv(blsgpu_ctx* c, const blsgpu_fr_matrix* m, const ui
   if (h.rc) return h.rc;
   if (!dx) { if (!h.reserve(c->io_a, 16)) return h.rc; dx = c->io_a.p; }      // n_cols == 0: nothing is gathered, but the device form wants a pointer
   return h.finish(blsgpu_fr_spmv_device(c, m, dx, k, o));
+}
+
+// ---- multilinear tables: folds, eq tables, evaluation, sumcheck rounds (fr_mle.hip.h; fr_mle_plan.h decides the launches) -----------------
+// the footprint (k - 1) * pitch + len scalars of k tables; false when it does not fit 2^28 (64-bit overflow included)
+static bool frmle_footprint(size_t k, size_t pitch, size_t len, size_t* scalars) {
+  *scalars = 0;
+  if (!k) return true;
+  if (k > FRM_MAX_TOTAL || pitch > FRM_MAX_TOTAL || len > FRM_MAX_TOTAL) return false;
+  const size_t f = (k - 1) * pitch + len;           // both factors <= 2^28: no overflow
+  *scalars = f;
+  return f <= FRM_MAX_TOTAL;
+}
+static bool frmle_overlap(const void* a, size_t a_scalars, const void* b, size_t b_scalars) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + b_scalars * 32 && y < x + a_scalars * 32;
+}
+// more than 64 KB of dynamic LDS per workgroup has to be asked for: once per context
+static int frmle_lds_probe(blsgpu_ctx* c) {
+  if (c->frm_lds_ready) return BLSGPU_OK;
+  const int want = (int)frm_round_lds_bytes(FrMleShape(), FRM_MAX_K);
+  HIPCHK(hipFuncSetAttribute((const void*)k_frm_round<false>, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+  HIPCHK(hipFuncSetAttribute((const void*)k_frm_round<true>, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+  c->frm_lds_ready = true;
+  return BLSGPU_OK;
+}
+// walks a plan: in / out are the caller's buffers with the caller's pitches, r the call's own challenge, point the challenges of an eval
+static int frmle_launch(blsgpu_ctx* c, const FrMlePlan& plan, const u32* in, size_t pitch_in, u32* out, size_t pitch_out, const u32* r, const u32* point, size_t k,
+                        const FrmProg* prog) {
+  hipStream_t st = c->stream;
+  const FrMleShape shape;
+  u32* buf[4] = {const_cast<u32*>(in), out, c->frm_scratch.as<u32>(), c->frm_rec.as<u32>()};
+  for (int i = 0; i < plan.n_steps; i++) {
+    const FrMleStep& s = plan.step[i];
+    u32* src = s.src >= 0 ? buf[s.src] : nullptr;
+    u32* dst = s.dst >= 0 ? buf[s.dst] : nullptr;
+    const size_t pi = s.pitch_in ? s.pitch_in : pitch_in, po = s.pitch_out ? s.pitch_out : pitch_out;
+    switch (s.kernel) {
+      case FRM_K_FOLD:
+        KLAUNCH(k_frm_fold, dim3(s.grid), dim3(s.block), s.lds, st, (const u32*)src, pi, dst, po, s.m - 1, s.items, s.var >= 0 ? point + (size_t)s.var * 8 : r);
+        break;
+      case FRM_K_EQ:
+        KLAUNCH(k_frm_eq, dim3(s.grid), dim3(s.block), s.lds, st, point, s.m, frm_eq_lo(s.m, shape), dst);
+        break;
+      case FRM_K_COPY:
+        HIPCHK(hipMemcpy2DAsync(dst, po * 32, src, pi * 32, 32, s.items, hipMemcpyDeviceToDevice, st));
+        break;
+      case FRM_K_ROUND:
+        KLAUNCH(k_frm_round<false>, dim3(s.grid), dim3(s.block), s.lds, st, src, pi, s.items, (unsigned)k, (unsigned)shape.chunk, *prog, (const u32*)nullptr, dst);
+        break;
+      case FRM_K_ROUND_FUSED:
+        KLAUNCH(k_frm_round<true>, dim3(s.grid), dim3(s.block), s.lds, st, src, pi, s.items, (unsigned)k, (unsigned)shape.chunk, *prog, r, dst);
+        break;
+      default:
+        KLAUNCH(k_frm_round_finish, dim3(s.grid), dim3(s.block), s.lds, st, (const u32*)src, s.items, prog->deg + 1, dst);
+        break;
+    }
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+// every argument check of both fold forms, before anything is staged, reserved or launched.  *work: there is something to do.
+static int fr_mle_fold_check(blsgpu_ctx* c, const void* in, size_t pitch_in, int m, size_t k, const void* r, const void* out, size_t pitch_out, bool device, bool* work) {
+  *work = false;
+  if (!c) return bad("fr_mle_fold: NULL context");
+  if (m < 1 || m > FRM_MAX_M) return bad("fr_mle_fold: m must be in [1, 28]");
+  const size_t n = (size_t)1 << m, h = n >> 1;
+  if (pitch_in < n || pitch_out < h) return bad("fr_mle_fold: a pitch is smaller than its table (pitch_in >= 2^m, pitch_out >= 2^(m-1))");
+  size_t fin, fout;
+  if (!frmle_footprint(k, pitch_in, n, &fin) || !frmle_footprint(k, pitch_out, h, &fout)) return bad("fr_mle_fold: (k - 1) * pitch + 2^m must not exceed 2^28");
+  if (!k) return BLSGPU_OK;
+  if (!in || !out || !r) return bad("fr_mle_fold: NULL tables / r / out with work to do");
+  if (device && (((uintptr_t)in | (uintptr_t)out | (uintptr_t)r) & 15)) return bad("fr_mle_fold_device: device pointers must be 16-byte aligned");
+  if (!(in == out && pitch_in == pitch_out) && frmle_overlap(in, fin, out, fout))
+    return bad("fr_mle_fold: in and out overlap (d_out == d_in with equal pitches is the in-place form)");
+  if (device && (frmle_overlap(r, 1, out, fout))) return bad("fr_mle_fold: the challenge lies inside the output");
+  *work = true;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_mle_fold_device(blsgpu_ctx* c, const void* d_in, size_t pitch_in, int m, size_t k, const void* d_r, void* d_out, size_t pitch_out) { CTX_CLAIM(c);
+  bool work;
+  if (int rc = fr_mle_fold_check(c, d_in, pitch_in, m, k, d_r, d_out, pitch_out, true, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  return frmle_launch(c, fr_mle_fold_plan(m, k), (const u32*)d_in, pitch_in, (u32*)d_out, pitch_out, (const u32*)d_r, nullptr, k, nullptr);
+}
+extern "C" int blsgpu_fr_mle_fold(blsgpu_ctx* c, const uint64_t* tables, int m, size_t k, const uint64_t* r, uint64_t* out) { CTX_CLAIM(c);
+  bool work;
+  const size_t n = m >= 1 && m <= FRM_MAX_M ? (size_t)1 << m : 2;
+  if (int rc = fr_mle_fold_check(c, tables, n, m, k, r, out, n / 2, false, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HostCall h(c);
+  void* di = h.in(c->io_a, tables, k * n * 32);
+  void* dr = h.in(c->io_b, r, 32);
+  void* o = h.out(c->io_out, out, k * (n / 2) * 32);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_mle_fold_device(c, di, n, m, k, dr, o, n / 2));
+}
+static int fr_eq_table_check(blsgpu_ctx* c, const void* point, int m, const void* out, bool device) {
+  if (!c) return bad("fr_eq_table: NULL context");
+  if (m < 0 || m > FRM_MAX_M) return bad("fr_eq_table: m must be in [0, 28]");
+  if (!out || (m && !point)) return bad("fr_eq_table: NULL point / out");
+  if (device && (((uintptr_t)point | (uintptr_t)out) & 15)) return bad("fr_eq_table_device: device pointers must be 16-byte aligned");
+  if (device && m && frmle_overlap(point, (size_t)m, out, (size_t)1 << m)) return bad("fr_eq_table: the point lies inside the output");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_eq_table_device(blsgpu_ctx* c, const void* d_point, int m, void* d_out) { CTX_CLAIM(c);
+  if (int rc = fr_eq_table_check(c, d_point, m, d_out, true)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  return frmle_launch(c, fr_eq_table_plan(m), nullptr, 0, (u32*)d_out, 0, nullptr, (const u32*)d_point, 1, nullptr);
+}
+extern "C" int blsgpu_fr_eq_table(blsgpu_ctx* c, const uint64_t* point, int m, uint64_t* out) { CTX_CLAIM(c);
+  if (int rc = fr_eq_table_check(c, point, m, out, false)) return rc;
+  HostCall h(c);
+  void* dp = h.in(c->io_a, m ? point : nullptr, (size_t)m * 32);
+  void* o = h.out(c->io_out, out, ((size_t)1 << m) * 32);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_eq_table_device(c, dp, m, o));
+}
+static int fr_mle_eval_check(blsgpu_ctx* c, const void* tables, size_t pitch, int m, size_t k, const void* point, const void* out, bool device, bool* work) {
+  *work = false;
+  if (!c) return bad("fr_mle_eval: NULL context");
+  if (m < 0 || m > FRM_MAX_M) return bad("fr_mle_eval: m must be in [0, 28]");
+  const size_t n = (size_t)1 << m;
+  if (pitch < n) return bad("fr_mle_eval: pitch is smaller than a table (pitch >= 2^m)");
+  size_t foot;
+  if (!frmle_footprint(k, pitch, n, &foot)) return bad("fr_mle_eval: (k - 1) * pitch + 2^m must not exceed 2^28");
+  if (!k) return BLSGPU_OK;
+  if (!tables || !out || (m && !point)) return bad("fr_mle_eval: NULL tables / point / out with work to do");
+  if (device && (((uintptr_t)tables | (uintptr_t)out | (uintptr_t)point) & 15)) return bad("fr_mle_eval_device: device pointers must be 16-byte aligned");
+  if (device && frmle_overlap(tables, foot, out, k)) return bad("fr_mle_eval: out overlaps the tables (they are not written)");
+  if (device && m && frmle_overlap(point, (size_t)m, out, k)) return bad("fr_mle_eval: out overlaps the point");
+  *work = true;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_mle_eval_device(blsgpu_ctx* c, const void* d_tables, size_t pitch, int m, size_t k, const void* d_point, void* d_out) { CTX_CLAIM(c);
+  bool work;
+  if (int rc = fr_mle_eval_check(c, d_tables, pitch, m, k, d_point, d_out, true, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const FrMlePlan plan = fr_mle_eval_plan(m, k);
+  if (c->frm_scratch.reserve(plan.scratch * 32)) { g_err = "hipMalloc(fr mle scratch) failed"; return BLSGPU_ERR_HIP; }
+  return frmle_launch(c, plan, (const u32*)d_tables, pitch, (u32*)d_out, 1, nullptr, (const u32*)d_point, k, nullptr);
+}
+extern "C" int blsgpu_fr_mle_eval(blsgpu_ctx* c, const uint64_t* tables, int m, size_t k, const uint64_t* point, uint64_t* out) { CTX_CLAIM(c);
+  bool work;
+  const size_t n = m >= 0 && m <= FRM_MAX_M ? (size_t)1 << m : 1;
+  if (int rc = fr_mle_eval_check(c, tables, n, m, k, point, out, false, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HostCall h(c);
+  void* dt = h.in(c->io_a, tables, k * n * 32);
+  void* dp = h.in(c->io_b, m ? point : nullptr, (size_t)m * 32);
+  void* o = h.out(c->io_out, out, k * 32);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_mle_eval_device(c, dt, n, m, k, dp, o));
+}
+// every argument check of a round, before anything is reserved or launched; *prog: the kernels' form of the program
+static int fr_sumcheck_round_check(blsgpu_ctx* c, const void* tables, size_t pitch, int m, size_t k, size_t n_terms, const uint32_t* term_ptr, const uint8_t* term_tab,
+                                   const uint64_t* coef, const void* r_prev, const void* evals, FrmProg* prog) {
+  if (!c) return bad("fr_sumcheck_round: NULL context");
+  if (const char* why = frm_prog_build(k, n_terms, term_ptr, term_tab, coef, prog)) return bad(why);
+  if (m > FRM_MAX_M || m < (r_prev ? 2 : 1)) return bad(r_prev ? "fr_sumcheck_round: m must be in [2, 28] when a challenge is folded in first" : "fr_sumcheck_round: m must be in [1, 28]");
+  const size_t n = (size_t)1 << m;
+  if (pitch < n) return bad("fr_sumcheck_round: pitch is smaller than a table (pitch >= 2^m)");
+  size_t foot;
+  if (!frmle_footprint(k, pitch, n, &foot)) return bad("fr_sumcheck_round: (k - 1) * pitch + 2^m must not exceed 2^28");
+  if (!tables || !evals) return bad("fr_sumcheck_round: NULL tables / evals");
+  if (((uintptr_t)tables | (uintptr_t)evals | (uintptr_t)r_prev) & 15) return bad("fr_sumcheck_round_device: device pointers must be 16-byte aligned");
+  if (frmle_overlap(tables, foot, evals, prog->deg + 1)) return bad("fr_sumcheck_round: evals overlaps the tables");
+  if (r_prev && frmle_overlap(tables, foot, r_prev, 1)) return bad("fr_sumcheck_round: the challenge lies inside the tables, which the fold writes");
+  if (r_prev && frmle_overlap(evals, prog->deg + 1, r_prev, 1)) return bad("fr_sumcheck_round: the challenge lies inside evals");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_sumcheck_round_device(blsgpu_ctx* c, void* d_tables, size_t pitch, int m, size_t k, size_t n_terms, const uint32_t* term_ptr, const uint8_t* term_tab,
+                                               const uint64_t* coef, const void* d_r_prev, void* d_evals) { CTX_CLAIM(c);
+  FrmProg prog;
+  if (int rc = fr_sumcheck_round_check(c, d_tables, pitch, m, k, n_terms, term_ptr, term_tab, coef, d_r_prev, d_evals, &prog)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = frmle_lds_probe(c)) return rc;
+  const FrMlePlan plan = fr_sumcheck_round_plan(m, k, (int)prog.deg, d_r_prev != nullptr);
+  if (plan.n_steps < 0) return bad("fr_sumcheck_round: the shape is out of range");
+  if (c->frm_rec.reserve(plan.recs * (prog.deg + 1) * 32)) { g_err = "hipMalloc(fr sumcheck records) failed"; return BLSGPU_ERR_HIP; }
+  return frmle_launch(c, plan, (const u32*)d_tables, pitch, (u32*)d_evals, 0, (const u32*)d_r_prev, nullptr, k, &prog);
+}
+
+// the handle: its own copy of the tables (the rounds consume them), the program validated once
+static void frsc_drop(blsgpu_fr_sumcheck* s) {
+  if (!s) return;
+  if (s->tables) hipFree(s->tables);
+  if (s->small) hipFree(s->small);
+  delete s;
+}
+static int frsc_check(blsgpu_ctx* c, const void* tables, size_t pitch, int m, size_t k, size_t n_terms, const uint32_t* term_ptr, const uint8_t* term_tab, const uint64_t* coef,
+                      blsgpu_fr_sumcheck** out, bool device, FrmProg* prog) {
+  if (out) *out = nullptr;
+  if (!c || !out) return bad("fr_sumcheck_begin: NULL context / out");
+  if (const char* why = frm_prog_build(k, n_terms, term_ptr, term_tab, coef, prog)) return bad(why);
+  if (m < 1 || m > FRM_MAX_M) return bad("fr_sumcheck_begin: m must be in [1, 28]");
+  const size_t n = (size_t)1 << m;
+  if (pitch < n) return bad("fr_sumcheck_begin: pitch is smaller than a table (pitch >= 2^m)");
+  size_t foot;
+  if (!frmle_footprint(k, pitch, n, &foot) || k * n > FRM_MAX_TOTAL) return bad("fr_sumcheck_begin: (k - 1) * pitch + 2^m and k * 2^m must not exceed 2^28");
+  if (!tables) return bad("fr_sumcheck_begin: NULL tables");
+  if (device && ((uintptr_t)tables & 15)) return bad("fr_sumcheck_begin_device: device pointers must be 16-byte aligned");
+  return BLSGPU_OK;
+}
+static int frsc_make(blsgpu_ctx* c, int m, size_t k, size_t n_terms, const uint32_t* term_ptr, const uint8_t* term_tab, const uint64_t* coef, const FrmProg& prog,
+                     blsgpu_fr_sumcheck** out) {
+  blsgpu_fr_sumcheck* s = new blsgpu_fr_sumcheck();
+  s->device = c->device; s->m = m; s->k = k; s->pitch = (size_t)1 << m; s->vars_left = m; s->deg = (int)prog.deg; s->n_terms = n_terms;
+  memcpy(s->term_ptr, term_ptr, (n_terms + 1) * 4);
+  memcpy(s->term_tab, term_tab, term_ptr[n_terms]);
+  memcpy(s->coef, coef, n_terms * 32);
+  if (hipMalloc((void**)&s->tables, k * s->pitch * 32) != hipSuccess || hipMalloc((void**)&s->small, (1 + FRM_MAX_EVALS) * 32) != hipSuccess) {
+    (void)hipGetLastError(); frsc_drop(s); g_err = "hipMalloc(fr sumcheck tables) failed"; return BLSGPU_ERR_HIP;
+  }
+  *out = s;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_sumcheck_begin(blsgpu_ctx* c, const uint64_t* tables, int m, size_t k, size_t n_terms, const uint32_t* term_ptr, const uint8_t* term_tab,
+                                        const uint64_t* coef, blsgpu_fr_sumcheck** out) { CTX_CLAIM(c);
+  FrmProg prog;
+  if (int rc = frsc_check(c, tables, m >= 1 && m <= FRM_MAX_M ? (size_t)1 << m : 0, m, k, n_terms, term_ptr, term_tab, coef, out, false, &prog)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  blsgpu_fr_sumcheck* s = nullptr;
+  if (int rc = frsc_make(c, m, k, n_terms, term_ptr, term_tab, coef, prog, &s)) return rc;
+  int rc = staged_upload(c, s->tables, tables, k * s->pitch * 32);
+  if (rc) { (void)hipStreamSynchronize(c->stream); frsc_drop(s); return rc; }
+  *out = s;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_sumcheck_begin_device(blsgpu_ctx* c, const void* d_tables, size_t pitch, int m, size_t k, size_t n_terms, const uint32_t* term_ptr,
+                                               const uint8_t* term_tab, const uint64_t* coef, blsgpu_fr_sumcheck** out) { CTX_CLAIM(c);
+  FrmProg prog;
+  if (int rc = frsc_check(c, d_tables, pitch, m, k, n_terms, term_ptr, term_tab, coef, out, true, &prog)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  blsgpu_fr_sumcheck* s = nullptr;
+  if (int rc = frsc_make(c, m, k, n_terms, term_ptr, term_tab, coef, prog, &s)) return rc;
+  hipError_t e = hipMemcpy2DAsync(s->tables, s->pitch * 32, d_tables, pitch * 32, s->pitch * 32, k, hipMemcpyDeviceToDevice, c->stream);
+  if (e != hipSuccess) { frsc_drop(s); return fail("hipMemcpy2DAsync(fr sumcheck tables)", e, __LINE__); }
+  *out = s;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_sumcheck_vars_left(const blsgpu_fr_sumcheck* s) { return s ? s->vars_left : 0; }
+extern "C" int blsgpu_fr_sumcheck_degree(const blsgpu_fr_sumcheck* s) { return s ? s->deg : 0; }
+extern "C" int blsgpu_fr_sumcheck_round(blsgpu_ctx* c, blsgpu_fr_sumcheck* s, const uint64_t* r_prev, uint64_t* evals) { CTX_CLAIM(c);
+  if (!c || !s || !evals) return bad("fr_sumcheck_round: NULL context / handle / evals");
+  if (s->device != c->device) return bad("fr_sumcheck_round: the handle lives on another device than the context");
+  if (!s->vars_left) return bad("fr_sumcheck_round: the sumcheck is finished");
+  if (!s->started && r_prev) return bad("fr_sumcheck_round: the first round takes no challenge (r_prev must be NULL)");
+  if (s->started && !r_prev) return bad("fr_sumcheck_round: every round after the first needs the previous round's challenge");
+  if (s->started && s->vars_left == 1) return bad("fr_sumcheck_round: one variable is left: blsgpu_fr_sumcheck_finish takes the last challenge");
+  HIPCHK(hipSetDevice(c->device));
+  if (r_prev) HIPCHK(hipMemcpyAsync(s->small, r_prev, 32, hipMemcpyHostToDevice, c->stream));
+  if (int rc = blsgpu_fr_sumcheck_round_device(c, s->tables, s->pitch, s->vars_left, s->k, s->n_terms, s->term_ptr, s->term_tab, s->coef, r_prev ? s->small : nullptr, s->small + 8))
+    return rc;
+  HIPCHK(hipMemcpyAsync(evals, s->small + 8, (size_t)(s->deg + 1) * 32, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (r_prev) s->vars_left--;
+  s->started = true;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_sumcheck_finish(blsgpu_ctx* c, blsgpu_fr_sumcheck* s, const uint64_t* r_last, uint64_t* values) { CTX_CLAIM(c);
+  if (!c || !s || !r_last || !values) return bad("fr_sumcheck_finish: NULL context / handle / r_last / values");
+  if (s->device != c->device) return bad("fr_sumcheck_finish: the handle lives on another device than the context");
+  if (!s->started || s->vars_left != 1) return bad("fr_sumcheck_finish: rounds are left (finish takes the LAST challenge, when one variable is left)");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(s->small, r_last, 32, hipMemcpyHostToDevice, c->stream));
+  if (int rc = blsgpu_fr_mle_fold_device(c, s->tables, s->pitch, 1, s->k, s->small, s->tables, s->pitch)) return rc;
+  HIPCHK(hipMemcpy2DAsync(values, 32, s->tables, s->pitch * 32, 32, s->k, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  s->vars_left = 0;
+  return BLSGPU_OK;
+}
+extern "C" void blsgpu_fr_sumcheck_free(blsgpu_fr_sumcheck* s) {
+  if (!s) return;
+  hipSetDevice(s->device);
+  hipDeviceSynchronize();                  // work queued on a stream may still use the tables
+  frsc_drop(s);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -222,6 +222,8 @@ struct blsgpu_ctx {
   DevBuf frsp_head, frsp_tail, frsp_meta;         // blsgpu_fr_spmv: the HEAD / TAIL sums and the META word of every tile (fr_spmv_plan.h)
   bool frsp_lds_ready = false;          // ... and its tile kernel's dynamic LDS
   bool frs_lds_ready = false;           // the scan kernels' dynamic LDS (more than the 64 KB a kernel gets unasked) has been granted on this device
+  DevBuf frm_rec, frm_scratch;          // blsgpu_fr_sumcheck_round_device: one record per tile; blsgpu_fr_mle_eval_device: the folded copy of the tables (fr_mle_plan.h)
+  bool frm_lds_ready = false;           // ... and the round kernels' dynamic LDS
 };
 
 static inline KTimer* ktimer_of(blsgpu_ctx* c) { return &c->ktimer; }
@@ -266,6 +268,21 @@ struct blsgpu_fr_matrix {
   u32* tile_row = nullptr;                         // the row of every tile's first entry (+ one closing word)
   u32* flag = nullptr;                             // [0] the validation kernel's verdict, [1] a row is empty
   bool has_empty = false;                          // a row without entries: the product zeroes its output first
+};
+
+// a sumcheck in progress (api_aux.hip: blsgpu_fr_sumcheck_begin*; fr_mle.hip.h): its own copy of the tables, which the rounds consume,
+// and the term program as the caller gave it (validated once at begin; the round entry point it is passed to builds the kernels' form)
+struct blsgpu_fr_sumcheck {
+  int device = 0; int m = 0; size_t k = 0, pitch = 0;
+  int vars_left = 0;                               // 0: finished
+  bool started = false;                            // the first round has run
+  int deg = 0;
+  size_t n_terms = 0;
+  uint32_t term_ptr[9] = {};
+  uint8_t term_tab[48] = {};
+  uint64_t coef[32] = {};
+  u32* tables = nullptr;                           // k * pitch scalars
+  u32* small = nullptr;                            // the challenge (8 words), then deg + 1 evaluations
 };
 
 // ---- functions that cross translation units -------------------------------------------------------------------------------------

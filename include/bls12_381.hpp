@@ -389,6 +389,75 @@ inline std::vector<FrLimbs> fr_spmv(const FrMatrix& m, const std::vector<FrLimbs
   check(blsgpu_fr_spmv(Context::instance().handle(), m.handle(), x[0].data(), k, out[0].data()), "fr_spmv");
   return out;
 }
+// Multilinear tables (include/bls12_381_hip.h): k tables of t.size() / k = 2^m scalars each, laid end to end; entry i is the value at the
+// point whose coordinate x_b is bit b of i.  fr_mle_fold binds the top variable at r (k x 2^(m-1) out), fr_eq_table is
+// eq(point)[i] = prod_b (bit b of i ? point[b] : 1 - point[b]), fr_mle_eval gives f_j(point) with point[b] the value of x_b.
+inline int fr_mle_log(size_t n, const char* what) {
+  if (n == 0 || (n & (n - 1))) throw std::invalid_argument(std::string(what) + ": the table length must be a power of two");
+  int m = 0; while (((size_t)1 << m) < n) m++;
+  return m;
+}
+inline std::vector<FrLimbs> fr_mle_fold(const std::vector<FrLimbs>& t, size_t k, const FrLimbs& r) {
+  if (t.empty()) return {};
+  if (k == 0 || t.size() % k) throw std::invalid_argument("fr_mle_fold: the length must be k tables of equal size");
+  const int m = fr_mle_log(t.size() / k, "fr_mle_fold");
+  std::vector<FrLimbs> out(t.size() / 2);
+  check(blsgpu_fr_mle_fold(Context::instance().handle(), t[0].data(), m, k, r.data(), out.empty() ? nullptr : out[0].data()), "fr_mle_fold");
+  return out;
+}
+inline std::vector<FrLimbs> fr_eq_table(const std::vector<FrLimbs>& point) {
+  std::vector<FrLimbs> out((size_t)1 << point.size());
+  check(blsgpu_fr_eq_table(Context::instance().handle(), point.empty() ? nullptr : point[0].data(), (int)point.size(), out[0].data()), "fr_eq_table");
+  return out;
+}
+inline std::vector<FrLimbs> fr_mle_eval(const std::vector<FrLimbs>& t, size_t k, const std::vector<FrLimbs>& point) {
+  std::vector<FrLimbs> out(k);
+  if (k == 0) return out;
+  if (t.empty() || t.size() % k || fr_mle_log(t.size() / k, "fr_mle_eval") != (int)point.size()) throw std::invalid_argument("fr_mle_eval: k tables of 2^point.size() scalars");
+  check(blsgpu_fr_mle_eval(Context::instance().handle(), t[0].data(), (int)point.size(), k, point.empty() ? nullptr : point[0].data(), out[0].data()), "fr_mle_eval");
+  return out;
+}
+// One term of a sumcheck's summand: coef * prod_e f_{tables[e]} (1 to 6 factors; an index may repeat)
+struct FrTerm { FrLimbs coef; std::vector<uint8_t> tables; };
+// A sumcheck over sum_x sum_t coef_t prod_e f_e(x) as a resident handle (blsgpu_fr_sumcheck): the k tables are copied to the device
+// and consumed by the rounds.  round() gives the round polynomial's values at 0 .. degree(); order: round(), round(&r_1), ... while
+// vars_left() > 1, then finish(r_m), which returns f_j at the point p_b = r_(m-b).
+class FrSumcheck {
+ public:
+  FrSumcheck(const std::vector<FrLimbs>& t, size_t k, const std::vector<FrTerm>& terms) : k_(k) {
+    if (t.empty() || k == 0 || t.size() % k) throw std::invalid_argument("FrSumcheck: the length must be k tables of equal size");
+    const int m = fr_mle_log(t.size() / k, "FrSumcheck");
+    std::vector<uint32_t> ptr{0};
+    std::vector<uint8_t> tab;
+    std::vector<FrLimbs> coef;
+    for (const FrTerm& term : terms) {
+      tab.insert(tab.end(), term.tables.begin(), term.tables.end());
+      ptr.push_back((uint32_t)tab.size());
+      coef.push_back(term.coef);
+    }
+    check(blsgpu_fr_sumcheck_begin(Context::instance().handle(), t[0].data(), m, k, terms.size(), ptr.data(), tab.data(), coef.empty() ? nullptr : coef[0].data(), &s_), "fr_sumcheck_begin");
+  }
+  ~FrSumcheck() { blsgpu_fr_sumcheck_free(s_); }
+  FrSumcheck(const FrSumcheck&) = delete;
+  FrSumcheck& operator=(const FrSumcheck&) = delete;
+  FrSumcheck(FrSumcheck&& o) noexcept : s_(o.s_), k_(o.k_) { o.s_ = nullptr; }
+  int vars_left() const { return blsgpu_fr_sumcheck_vars_left(s_); }
+  int degree() const { return blsgpu_fr_sumcheck_degree(s_); }
+  std::vector<FrLimbs> round(const FrLimbs* r_prev = nullptr) {
+    std::vector<FrLimbs> evals((size_t)degree() + 1);
+    check(blsgpu_fr_sumcheck_round(Context::instance().handle(), s_, r_prev ? r_prev->data() : nullptr, evals[0].data()), "fr_sumcheck_round");
+    return evals;
+  }
+  std::vector<FrLimbs> finish(const FrLimbs& r_last) {
+    std::vector<FrLimbs> values(k_);
+    check(blsgpu_fr_sumcheck_finish(Context::instance().handle(), s_, r_last.data(), values[0].data()), "fr_sumcheck_finish");
+    return values;
+  }
+  blsgpu_fr_sumcheck* handle() const { return s_; }
+ private:
+  blsgpu_fr_sumcheck* s_ = nullptr;
+  size_t k_ = 0;
+};
 // The same transform over group elements: k vectors of p.size() / k points each in one call, in place (vector i = elements
 // [i n, (i+1) n)); Y[m] = sum_j [w^(jm)] P[j] with the w of fr_ntt, the inverse scaled by n^-1 (include/bls12_381_hip.h).  Every point
 // must lie in the prime-order subgroup.  The overloads on affine points lift them (Z = 1, the identity (0 : 1 : 0)) and return the result.

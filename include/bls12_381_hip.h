@@ -573,6 +573,62 @@ void blsgpu_fr_matrix_free(blsgpu_fr_matrix* m);
  * overflow included), a misaligned device pointer, ANY overlap of the out range with the x range (the gather would race). */
 int blsgpu_fr_spmv(blsgpu_ctx* ctx, const blsgpu_fr_matrix* m, const uint64_t* x, size_t k, uint64_t* out);
 int blsgpu_fr_spmv_device(blsgpu_ctx* ctx, const blsgpu_fr_matrix* m, const void* d_x, size_t k, void* d_out);
+/* Multilinear polynomials: a table of 2^m scalars is the values of a multilinear polynomial f on the hypercube, entry i the value at the
+ * point whose coordinate x_b is bit b of i -- what a Spartan / HyperPlonk / GKR-style prover holds after blsgpu_fr_spmv_device where a
+ * univariate prover would transform.  k tables are addressed as table j at j * pitch scalars behind the base pointer, pitch >= 2^m (the
+ * host forms are packed: pitch = 2^m).  With h = 2^(m-1):
+ *   fold      out[j][i] = f_j[i] + r * (f_j[i + h] - f_j[i]),  i < h:  f_j with the TOP variable bound, x_(m-1) = r (m - 1 variables left)
+ *   eq table  out[i] = prod_{b<m} (bit b of i ? p_b : 1 - p_b),  so that  f(p) = sum_i f[i] * eq(p)[i]
+ *   eval      out[j] = f_j(point), point[b] the value of x_b: m folds, the first into the context's scratch; the tables are not written
+ * built on `Scalar`'s mul / add / sub (scalar.rs:452-503, :435-449, :414-432; the reference crate has none of these operations).
+ * Canonical inputs are a precondition (not validated); outputs are canonical, and limb-identical from run to run (no atomics, no
+ * workgroup waits for another one).  fold: m in [1, 28]; d_r is ONE scalar in device memory; d_out == d_in with pitch_out == pitch_in is
+ * the in-place form (row j's result lies in the first half of row j's slot), any other overlap of the two footprints
+ * (k - 1) * pitch + length is refused; the host form returns packed k x 2^(m-1).  eq table: m in [0, 28], m == 0 writes the Scalar one.
+ * eval: m in [0, 28], m == 0 copies.  (k - 1) * pitch + 2^m <= 2^28 (64-bit overflow checked); k == 0 is a no-op.  Device pointers
+ * must be 16-byte aligned.  The device forms are asynchronous on the context's stream; scratch is the context's own and is not shared
+ * with pipelined *_msm_device calls in flight.  BLSGPU_ERR_ARG (nothing staged or launched): a NULL pointer with work to do, m, k or a
+ * pitch out of range, a misaligned device pointer, an overlap. */
+int blsgpu_fr_mle_fold(blsgpu_ctx* ctx, const uint64_t* tables, int m, size_t k, const uint64_t r[4], uint64_t* out);
+int blsgpu_fr_mle_fold_device(blsgpu_ctx* ctx, const void* d_in, size_t pitch_in, int m, size_t k, const void* d_r, void* d_out, size_t pitch_out);
+int blsgpu_fr_eq_table(blsgpu_ctx* ctx, const uint64_t* point, int m, uint64_t* out);
+int blsgpu_fr_eq_table_device(blsgpu_ctx* ctx, const void* d_point, int m, void* d_out);
+int blsgpu_fr_mle_eval(blsgpu_ctx* ctx, const uint64_t* tables, int m, size_t k, const uint64_t* point, uint64_t* out);
+int blsgpu_fr_mle_eval_device(blsgpu_ctx* ctx, const void* d_tables, size_t pitch, int m, size_t k, const void* d_point, void* d_out);
+/* One round polynomial of a sumcheck over  P(x) = sum_t coef_t * prod_{e in term t} f_{term_tab[e]}(x)  (Scalar mul / add / sub as above).
+ * The term program is a parameter in HOST memory in both forms, as `coset` is: n_terms in [1, 8]; term_ptr holds n_terms + 1 words,
+ * term_ptr[0] = 0, strictly increasing, 1 to 6 factors per term; term_tab holds table indices < k (a repeated index is a square); coef
+ * holds n_terms x 4 canonical Montgomery limbs (zero allowed); k in [1, 8].  D = the longest term.  For t = 0 .. D
+ *   evals[t] = sum_{i<h} sum_t' coef_t' * prod_e ((1 - t) * f_e[i] + t * f_e[i + h])
+ * i.e. the values at 0 .. D of the polynomial the prover sends when it binds x_(m-1); a term shorter than D is evaluated as it is.
+ * d_r_prev == NULL: the tables as they are, m in [1, 28], nothing is written but d_evals (D + 1 scalars).  d_r_prev != NULL (one scalar
+ * in device memory): FIRST every table is folded at *d_r_prev in place, pitch kept (row j's 2^(m-1) results in the first half of its
+ * slot, the second half is left as it was), and the evaluations are those of the folded tables of m - 1 variables; m in [2, 28].  This
+ * is the form a prover runs in rounds 2 .. m: one pass reads every table once, writes half of it and leaves the next round's
+ * polynomial.  Round s = 1 .. m binds x_(m-s); with challenges r_1 .. r_m the tables end at the point p_b = r_(m-b).
+ * Asynchronous on the context's stream; pitch, footprint, alignment, canonical inputs, determinism and refusals as above, and
+ * BLSGPU_ERR_ARG for k == 0, a bad program, d_evals or d_r_prev inside the tables. */
+int blsgpu_fr_sumcheck_round_device(blsgpu_ctx* ctx, void* d_tables, size_t pitch, int m, size_t k, size_t n_terms, const uint32_t* term_ptr, const uint8_t* term_tab,
+                                    const uint64_t* coef, const void* d_r_prev, void* d_evals);
+/* A whole sumcheck as a resident handle, like blsgpu_fr_matrix and blsgpu_bases: begin copies the k tables of m in [1, 28] variables into
+ * device memory of its own (the rounds consume them; the caller's are free again on return; k * 2^m <= 2^28) and validates the program
+ * once.  round and finish are thin host code over blsgpu_fr_sumcheck_round_device and blsgpu_fr_mle_fold_device that also copy the
+ * D + 1 evaluations (finish: the k values f_j(point)) back to HOST memory and synchronise the context's stream: an interactive prover
+ * derives its next challenge from them.  Order: round(NULL), then round(r_1) .. round(r_(m-1)) while vars_left > 1, then finish(r_m);
+ * for m = 1 round(NULL), finish(r_1).  Challenges are four canonical Montgomery limbs in host memory.  Any other order -- a NULL
+ * challenge after the first round, a challenge in the first round, round when one variable is left, finish before that, anything after
+ * finish -- is BLSGPU_ERR_ARG and leaves the handle as it was.  vars_left counts the unbound variables (m after begin, 0 after finish);
+ * degree is D.  blsgpu_fr_sumcheck_free follows the rules of blsgpu_fr_matrix_free (it waits for the device; NULL is allowed). */
+typedef struct blsgpu_fr_sumcheck blsgpu_fr_sumcheck;
+int blsgpu_fr_sumcheck_begin(blsgpu_ctx* ctx, const uint64_t* tables, int m, size_t k, size_t n_terms, const uint32_t* term_ptr, const uint8_t* term_tab, const uint64_t* coef,
+                             blsgpu_fr_sumcheck** out);
+int blsgpu_fr_sumcheck_begin_device(blsgpu_ctx* ctx, const void* d_tables, size_t pitch, int m, size_t k, size_t n_terms, const uint32_t* term_ptr, const uint8_t* term_tab,
+                                    const uint64_t* coef, blsgpu_fr_sumcheck** out);
+int blsgpu_fr_sumcheck_vars_left(const blsgpu_fr_sumcheck* s);
+int blsgpu_fr_sumcheck_degree(const blsgpu_fr_sumcheck* s);
+int blsgpu_fr_sumcheck_round(blsgpu_ctx* ctx, blsgpu_fr_sumcheck* s, const uint64_t* r_prev, uint64_t* evals);
+int blsgpu_fr_sumcheck_finish(blsgpu_ctx* ctx, blsgpu_fr_sumcheck* s, const uint64_t* r_last, uint64_t* values);
+void blsgpu_fr_sumcheck_free(blsgpu_fr_sumcheck* s);
 /* The same radix-2 transform over GROUP elements: k vectors of 2^log_n G1 (G2) points each, laid end to end, in place, natural order in
  * and out:
  *   forward  Y[m] = sum_j [w^(jm)] P[j],   inverse  P[j] = [n^-1] sum_m [w^(-jm)] Y[m],   w as for blsgpu_fr_ntt

@@ -174,6 +174,20 @@ extern "C" {
     pub fn blsgpu_fr_matrix_free(m: *mut c_void);
     pub fn blsgpu_fr_spmv(ctx: *mut BlsgpuCtx, m: *const c_void, x: *const u64, k: usize, out: *mut u64) -> c_int;
     pub fn blsgpu_fr_spmv_device(ctx: *mut BlsgpuCtx, m: *const c_void, d_x: *const c_void, k: usize, d_out: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_mle_fold(ctx: *mut BlsgpuCtx, tables: *const u64, m: c_int, k: usize, r: *const u64, out: *mut u64) -> c_int;
+    pub fn blsgpu_fr_mle_fold_device(ctx: *mut BlsgpuCtx, d_in: *const c_void, pitch_in: usize, m: c_int, k: usize, d_r: *const c_void, d_out: *mut c_void, pitch_out: usize) -> c_int;
+    pub fn blsgpu_fr_eq_table(ctx: *mut BlsgpuCtx, point: *const u64, m: c_int, out: *mut u64) -> c_int;
+    pub fn blsgpu_fr_eq_table_device(ctx: *mut BlsgpuCtx, d_point: *const c_void, m: c_int, d_out: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_mle_eval(ctx: *mut BlsgpuCtx, tables: *const u64, m: c_int, k: usize, point: *const u64, out: *mut u64) -> c_int;
+    pub fn blsgpu_fr_mle_eval_device(ctx: *mut BlsgpuCtx, d_tables: *const c_void, pitch: usize, m: c_int, k: usize, d_point: *const c_void, d_out: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_sumcheck_round_device(ctx: *mut BlsgpuCtx, d_tables: *mut c_void, pitch: usize, m: c_int, k: usize, n_terms: usize, term_ptr: *const u32, term_tab: *const u8, coef: *const u64, d_r_prev: *const c_void, d_evals: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_sumcheck_begin(ctx: *mut BlsgpuCtx, tables: *const u64, m: c_int, k: usize, n_terms: usize, term_ptr: *const u32, term_tab: *const u8, coef: *const u64, out: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_sumcheck_begin_device(ctx: *mut BlsgpuCtx, d_tables: *const c_void, pitch: usize, m: c_int, k: usize, n_terms: usize, term_ptr: *const u32, term_tab: *const u8, coef: *const u64, out: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_sumcheck_vars_left(s: *const c_void) -> c_int;
+    pub fn blsgpu_fr_sumcheck_degree(s: *const c_void) -> c_int;
+    pub fn blsgpu_fr_sumcheck_round(ctx: *mut BlsgpuCtx, s: *mut c_void, r_prev: *const u64, evals: *mut u64) -> c_int;
+    pub fn blsgpu_fr_sumcheck_finish(ctx: *mut BlsgpuCtx, s: *mut c_void, r_last: *const u64, values: *mut u64) -> c_int;
+    pub fn blsgpu_fr_sumcheck_free(s: *mut c_void);
     pub fn blsgpu_g1_ntt_many(ctx: *mut BlsgpuCtx, xyz: *mut u64, log_n: c_int, k: usize, inverse: c_int) -> c_int;
     pub fn blsgpu_g2_ntt_many(ctx: *mut BlsgpuCtx, xyz: *mut u64, log_n: c_int, k: usize, inverse: c_int) -> c_int;
     pub fn blsgpu_g1_ntt_many_device(ctx: *mut BlsgpuCtx, d_xyz: *mut c_void, log_n: c_int, k: usize, inverse: c_int) -> c_int;

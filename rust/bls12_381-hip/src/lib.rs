@@ -266,6 +266,74 @@ pub fn fr_spmv(gpu: &Gpu, m: &FrMatrix, x: &[Scalar]) -> Result<Vec<Scalar>, Err
     check(unsafe { ffi::blsgpu_fr_spmv(gpu.ctx, m.handle as *const c_void, input.as_ptr(), k, out.as_mut_ptr()) })?;
     limbs_scalars(gpu, &out)
 }
+/// Binds the TOP variable of `k = tables.len() / 2^m` multilinear tables laid end to end (entry `i` is the value at the point whose
+/// coordinate `x_b` is bit `b` of `i`): `out[j][i] = f_j[i] + r * (f_j[i + 2^(m-1)] - f_j[i])`, `k * 2^(m-1)` scalars.
+pub fn fr_mle_fold(gpu: &Gpu, tables: &[Scalar], m: u32, r: &Scalar) -> Result<Vec<Scalar>, Error> {
+    assert!(m >= 1 && tables.len() % (1usize << m) == 0);
+    let k = tables.len() >> m;
+    if k == 0 { return Ok(Vec::new()); }
+    let (input, rl) = (scalar_limbs(gpu, tables)?, scalar_limbs(gpu, std::slice::from_ref(r))?);
+    let mut out = vec![0u64; tables.len() / 2 * 4];
+    check(unsafe { ffi::blsgpu_fr_mle_fold(gpu.ctx, input.as_ptr(), m as c_int, k, rl.as_ptr(), out.as_mut_ptr()) })?;
+    limbs_scalars(gpu, &out)
+}
+/// `eq(point)[i] = prod_b (bit b of i ? point[b] : 1 - point[b])`, `2^point.len()` scalars: `f(point) = sum_i f[i] * eq(point)[i]`.
+pub fn fr_eq_table(gpu: &Gpu, point: &[Scalar]) -> Result<Vec<Scalar>, Error> {
+    let pl = scalar_limbs(gpu, point)?;
+    let mut out = vec![0u64; 4usize << point.len()];
+    check(unsafe { ffi::blsgpu_fr_eq_table(gpu.ctx, if point.is_empty() { std::ptr::null() } else { pl.as_ptr() }, point.len() as c_int, out.as_mut_ptr()) })?;
+    limbs_scalars(gpu, &out)
+}
+/// `f_j(point)` for `k = tables.len() / 2^point.len()` multilinear tables, `point[b]` the value of `x_b`.
+pub fn fr_mle_eval(gpu: &Gpu, tables: &[Scalar], point: &[Scalar]) -> Result<Vec<Scalar>, Error> {
+    let m = point.len();
+    assert!(tables.len() % (1usize << m) == 0);
+    let k = tables.len() >> m;
+    if k == 0 { return Ok(Vec::new()); }
+    let (input, pl) = (scalar_limbs(gpu, tables)?, scalar_limbs(gpu, point)?);
+    let mut out = vec![0u64; k * 4];
+    check(unsafe { ffi::blsgpu_fr_mle_eval(gpu.ctx, input.as_ptr(), m as c_int, k, if m == 0 { std::ptr::null() } else { pl.as_ptr() }, out.as_mut_ptr()) })?;
+    limbs_scalars(gpu, &out)
+}
+/// A sumcheck over `sum_x sum_t coef_t * prod_e f_{tables[e]}(x)` resident on the GPU (`blsgpu_fr_sumcheck`): the tables are copied to the
+/// device and consumed by the rounds.  The FFI layer sees the handle as an untyped pointer; this is its type.  Order: `round(None)`,
+/// `round(Some(&r_1))` ... while `vars_left() > 1`, then `finish(&r_m)`, which returns `f_j` at the point `p_b = r_(m-b)`.
+pub struct FrSumcheck<'a> { gpu: &'a Gpu, handle: *mut c_void, k: usize }
+impl<'a> FrSumcheck<'a> {
+    /// `terms`: (coefficient, table indices) with 1 to 6 indices below `k` each (an index may repeat), at most 8 terms and 8 tables.
+    pub fn new(gpu: &'a Gpu, tables: &[Scalar], m: u32, terms: &[(Scalar, Vec<u8>)]) -> Result<FrSumcheck<'a>, Error> {
+        assert!(m >= 1 && !tables.is_empty() && tables.len() % (1usize << m) == 0);
+        let k = tables.len() >> m;
+        let input = scalar_limbs(gpu, tables)?;
+        let coef = scalar_limbs(gpu, &terms.iter().map(|t| t.0).collect::<Vec<Scalar>>())?;
+        let (mut ptr, mut tab) = (vec![0u32], Vec::<u8>::new());
+        for t in terms { tab.extend_from_slice(&t.1); ptr.push(tab.len() as u32); }
+        let mut handle: *mut c_void = std::ptr::null_mut();
+        check(unsafe {
+            ffi::blsgpu_fr_sumcheck_begin(gpu.ctx, input.as_ptr(), m as c_int, k, terms.len(), ptr.as_ptr(), tab.as_ptr(), coef.as_ptr(),
+                                          &mut handle as *mut *mut c_void as *mut c_void)
+        })?;
+        Ok(FrSumcheck { gpu, handle, k })
+    }
+    pub fn vars_left(&self) -> usize { unsafe { ffi::blsgpu_fr_sumcheck_vars_left(self.handle as *const c_void) as usize } }
+    pub fn degree(&self) -> usize { unsafe { ffi::blsgpu_fr_sumcheck_degree(self.handle as *const c_void) as usize } }
+    /// The round polynomial's values at `0 ..= degree()`; `r_prev` is `None` in the first round only.
+    pub fn round(&mut self, r_prev: Option<&Scalar>) -> Result<Vec<Scalar>, Error> {
+        let rl = match r_prev { Some(r) => scalar_limbs(self.gpu, std::slice::from_ref(r))?, None => Vec::new() };
+        let mut out = vec![0u64; (self.degree() + 1) * 4];
+        check(unsafe { ffi::blsgpu_fr_sumcheck_round(self.gpu.ctx, self.handle, if r_prev.is_some() { rl.as_ptr() } else { std::ptr::null() }, out.as_mut_ptr()) })?;
+        limbs_scalars(self.gpu, &out)
+    }
+    pub fn finish(&mut self, r_last: &Scalar) -> Result<Vec<Scalar>, Error> {
+        let rl = scalar_limbs(self.gpu, std::slice::from_ref(r_last))?;
+        let mut out = vec![0u64; self.k * 4];
+        check(unsafe { ffi::blsgpu_fr_sumcheck_finish(self.gpu.ctx, self.handle, rl.as_ptr(), out.as_mut_ptr()) })?;
+        limbs_scalars(self.gpu, &out)
+    }
+}
+impl<'a> Drop for FrSumcheck<'a> {
+    fn drop(&mut self) { unsafe { ffi::blsgpu_fr_sumcheck_free(self.handle) } }
+}
 fn split72(flat: Vec<u64>) -> Vec<GtLimbs> {
     flat.chunks_exact(72).map(|c| { let mut a = [0u64; 72]; a.copy_from_slice(c); GtLimbs(a) }).collect()
 }
