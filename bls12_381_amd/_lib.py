@@ -72,6 +72,10 @@ SIGNATURES = {
     "blsgpu_fr_scan_many_device": (c_int, [c_vp, c_int, c_int, c_vp, c_sz, c_sz, c_vp, c_vp]),
     "blsgpu_fr_batch_invert": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
     "blsgpu_fr_batch_invert_device": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_bary_eval_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_int, c_vp]),
+    "blsgpu_fr_bary_eval_many_device": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_int, c_vp]),
+    "blsgpu_fr_bary_open_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_int, c_vp, c_vp]),
+    "blsgpu_fr_bary_open_many_device": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_int, c_vp, c_vp]),
     "blsgpu_fr_matrix_upload": (c_int, [c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
     "blsgpu_fr_matrix_from_device": (c_int, [c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
     "blsgpu_fr_matrix_rows": (c_sz, [c_vp]),

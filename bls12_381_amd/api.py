@@ -63,6 +63,7 @@ def _flags(f, n):
 
 
 FR_SCAN_SUM, FR_SCAN_PRODUCT, FR_SCAN_HORNER = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_SCAN_*
+FR_ORDER_NATURAL, FR_ORDER_BITREV = 0, 1                    # include/bls12_381_hip.h: BLSGPU_FR_ORDER_*
 FR_GENERATOR = 7                          # scalar.rs:99-105 GENERATOR (`MULTIPLICATIVE_GENERATOR` :708): the usual coset shift
 
 
@@ -79,18 +80,18 @@ def _coset_limbs(coset):
     return _u64(coset, (4,)).copy()
 
 
-def _point_limbs(points, k):
+def _point_limbs(points, k, what="fr_scan"):
     """k Python ints in [0, r) | a (k, 4) array of Montgomery limbs -> (k, 4) Montgomery limbs (np.uint64), converted as _coset_limbs does"""
     if isinstance(points, (int, np.integer)):
         points = [points]
     if isinstance(points, (list, tuple)) and all(isinstance(p, (int, np.integer)) for p in points):
         if len(points) != k:
-            raise ValueError("fr_scan: one point per row")
+            raise ValueError("%s: one point per row" % what)
         out = np.zeros((k, 4), dtype=np.uint64)
         for i, p in enumerate(points):
             z = int(p)
             if not 0 <= z < R_ORDER:
-                raise ValueError("fr_scan: an integer point must be in [0, r)")
+                raise ValueError("%s: an integer point must be in [0, r)" % what)
             v = (z << 256) % R_ORDER
             out[i] = [(v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(4)]
         return out
@@ -793,6 +794,45 @@ class Context:
 
     def fr_batch_invert_device(self, d_in, n, d_out, d_flags=None):
         check(self.lib.blsgpu_fr_batch_invert_device(self.h, d_in, n, d_out, d_flags), "fr_batch_invert_device")
+
+    def _fr_bary_args(self, what, evals, points):
+        v = np.ascontiguousarray(np.array(evals, dtype=np.uint64))
+        one = v.ndim == 2
+        if one:
+            v = v.reshape((1,) + v.shape)
+        if v.ndim != 3 or v.shape[2] != 4:
+            raise ValueError("%s: expected a (k, n, 4) or (n, 4) array" % what)
+        k, n = v.shape[0], v.shape[1]
+        if n == 0 or n & (n - 1):
+            raise ValueError("%s: the row length must be a power of two" % what)
+        return v, one, k, n.bit_length() - 1, _point_limbs(points, k, what)
+
+    def fr_bary_eval(self, evals, points, order=FR_ORDER_NATURAL):
+        """polynomials in evaluation form (include/bls12_381_hip.h: blsgpu_fr_bary_eval_many): `evals` is a (k, n, 4) u64 array of
+        Montgomery limbs (an (n, 4) array is k = 1), row v = p_v on the n-th roots of unity in natural (FR_ORDER_NATURAL) or bit-reversed
+        (FR_ORDER_BITREV) order, points[v] = z_v (Python ints in [0, r) or a (k, 4) array of Montgomery limbs, as fr_scan takes them).
+        Returns y = p_v(z_v) as a (k, 4) array ((4,) for k = 1 given as (n, 4)); a point inside the domain is handled exactly."""
+        v, one, k, log_n, pts = self._fr_bary_args("fr_bary_eval", evals, points)
+        y = np.zeros((k, 4), dtype=np.uint64)
+        check(self.lib.blsgpu_fr_bary_eval_many(self.h, _ptr(v), log_n, k, _ptr(pts), int(order), _ptr(y)), "fr_bary_eval")
+        return y[0] if one else y
+
+    def fr_bary_open(self, evals, points, order=FR_ORDER_NATURAL):
+        """as fr_bary_eval, and the evaluations q of the quotient (p_v(X) - y_v) / (X - z_v) on the same domain in the same order (the
+        scalars of a KZG proof over a Lagrange SRS).  Returns (y, q), q of the shape of `evals`."""
+        v, one, k, log_n, pts = self._fr_bary_args("fr_bary_open", evals, points)
+        y = np.zeros((k, 4), dtype=np.uint64)
+        q = np.zeros_like(v)
+        check(self.lib.blsgpu_fr_bary_open_many(self.h, _ptr(v), log_n, k, _ptr(pts), int(order), _ptr(y), _ptr(q)), "fr_bary_open")
+        return (y[0], q[0]) if one else (y, q)
+
+    def fr_bary_eval_device(self, d_evals, log_n, k, d_points, d_y, order=FR_ORDER_NATURAL):
+        """the same on k * 2^log_n scalars in device memory (d_points, d_y: k scalars), asynchronous on the context's stream"""
+        check(self.lib.blsgpu_fr_bary_eval_many_device(self.h, d_evals, log_n, k, d_points, int(order), d_y), "fr_bary_eval_device")
+
+    def fr_bary_open_device(self, d_evals, log_n, k, d_points, d_y, d_q, order=FR_ORDER_NATURAL):
+        """the same with the quotient written to d_q (k * 2^log_n scalars, no overlap with the inputs: there is no in-place form)"""
+        check(self.lib.blsgpu_fr_bary_open_many_device(self.h, d_evals, log_n, k, d_points, int(order), d_y, d_q), "fr_bary_open_device")
 
     def fr_matrix(self, row_ptr, col, val, n_cols):
         """a CSR matrix made resident (include/bls12_381_hip.h: blsgpu_fr_matrix_upload): row_ptr has n_rows + 1 entries from 0 to

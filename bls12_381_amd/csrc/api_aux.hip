@@ -4,6 +4,7 @@
 #include "fr.hip.h"
 #include "fr_plan.h"
 #include "fr_scan.hip.h"
+#include "fr_bary.hip.h"
 #include "fr_spmv.hip.h"
 #include "fr_mle.hip.h"
 #include "h2c.hip.h"
@@ -570,6 +571,104 @@ extern "C" int blsgpu_fr_batch_invert(blsgpu_ctx* c, const uint64_t* values, siz
   void* f = nonzero_flags ? h.out(c->flags_a, nonzero_flags, n) : nullptr;
   if (h.rc) return h.rc;
   return h.finish(blsgpu_fr_batch_invert_device(c, di, n, o, f));
+}
+
+// ---- polynomials in evaluation form: value at a point and the opening's quotient (fr_bary.hip.h; fr_bary_plan.h decides the launches) ------
+static bool frb_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + b_bytes && y < x + a_bytes;
+}
+// every argument check of the four forms, before anything is staged, reserved or launched.  *work: there is something to do.
+static int fr_bary_check(blsgpu_ctx* c, bool open, const void* evals, int log_n, size_t k, const void* points, int order, const void* y, const void* q, bool device, bool* work) {
+  *work = false;
+  if (!c) return bad("fr_bary: NULL context");
+  if (log_n < 0 || log_n > 28) return bad("fr_bary: log_n must be in [0, 28]");
+  if (k > (FRB_MAX_TOTAL >> log_n)) return bad("fr_bary: k * 2^log_n must not exceed 2^28");
+  if (order != BLSGPU_FR_ORDER_NATURAL && order != BLSGPU_FR_ORDER_BITREV) return bad("fr_bary: unknown order");
+  if (!k) return BLSGPU_OK;
+  if (!evals || !points || !y || (open && !q)) return bad("fr_bary: NULL pointer");
+  if (device && (((uintptr_t)evals | (uintptr_t)points | (uintptr_t)y | (uintptr_t)q) & 15)) return bad("fr_bary: device pointers must be 16-byte aligned");
+  const size_t data = (k << log_n) * 32, small = k * 32;
+  if (frb_overlap(y, small, evals, data) || frb_overlap(y, small, points, small)) return bad("fr_bary: y overlaps evals or points");
+  if (open && (frb_overlap(q, data, evals, data) || frb_overlap(q, data, points, small) || frb_overlap(q, data, y, small)))
+    return bad("fr_bary: q overlaps evals, points or y (there is no in-place form)");
+  *work = true;
+  return BLSGPU_OK;
+}
+// the tile kernels take more than the 64 KB of dynamic LDS a kernel gets unasked (as frs_lds_probe)
+static int frb_lds_probe(blsgpu_ctx* c) {
+  if (c->frb_lds_ready) return BLSGPU_OK;
+  const int want = (int)frb_lds_bytes(FrBaryShape());
+  HIPCHK(hipFuncSetAttribute((const void*)k_frb_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+  HIPCHK(hipFuncSetAttribute((const void*)k_frb_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+  c->frb_lds_ready = true;
+  return BLSGPU_OK;
+}
+template <bool OPEN>
+static int fr_bary_launch(blsgpu_ctx* c, const FrBaryPlan& plan, const u32* evals, int log_n, size_t k, const u32* points, int order, u32* y, u32* q) {
+  hipStream_t st = c->stream;
+  const unsigned chunk = FrBaryShape().chunk;
+  const u32* tw = c->fr_tw[0].as<u32>();
+  u32* buf[2] = {c->frb_rec.as<u32>(), c->frb_rowrec.as<u32>()};
+  for (int i = 0; i < plan.n_steps; i++) {
+    const FrBaryStep& s = plan.step[i];
+    u32* src = s.src >= 0 ? buf[s.src] : nullptr;
+    u32* dst = s.dst >= 0 ? buf[s.dst] : nullptr;
+    switch (s.kernel) {
+      case FRB_K_ROWS: case FRB_K_TILE:
+        KLAUNCH(k_frb_tile<OPEN>, dim3(s.grid), dim3(s.block), s.lds, st, s.kernel, evals, points, tw, log_n, k, order, chunk, y, q, dst);
+        break;
+      case FRB_K_ROW:
+        KLAUNCH(k_frb_row<OPEN>, dim3(s.grid), dim3(s.block), s.lds, st, (const u32*)src, ((size_t)1 << log_n) / plan.tile, (unsigned)plan.tile, points, log_n, k, y, q, dst);
+        break;
+      default:
+        KLAUNCH(k_frb_quot, dim3(s.grid), dim3(s.block), s.lds, st, evals, (const u32*)src, log_n, k, chunk, q);
+        break;
+    }
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+static int fr_bary_device(blsgpu_ctx* c, bool open, const void* d_evals, int log_n, size_t k, const void* d_points, int order, void* d_y, void* d_q) {
+  bool work;
+  if (int rc = fr_bary_check(c, open, d_evals, log_n, k, d_points, order, d_y, d_q, true, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = frb_lds_probe(c)) return rc;
+  const FrBaryPlan plan = fr_bary_plan(log_n, k, open);
+  if (plan.n_steps < 0) return bad("fr_bary: k * 2^log_n must not exceed 2^28");
+  if (c->frb_rec.reserve(plan.recs[FRB_BUF_REC] * FRB_REC_WORDS * 4) || c->frb_rowrec.reserve(plan.recs[FRB_BUF_ROWREC] * FRB_ROWREC_WORDS * 4) ||
+      (log_n && c->fr_tw[0].reserve(((size_t)1 << log_n) * 32))) {
+    g_err = "hipMalloc(fr bary scratch) failed"; return BLSGPU_ERR_HIP;
+  }
+  if (log_n) if (int rc = fr_twiddles_ready(c, log_n, 0)) return rc;      // D[i]: the transform's forward table (no level at log_n = 0)
+  if (open) return fr_bary_launch<true>(c, plan, (const u32*)d_evals, log_n, k, (const u32*)d_points, order, (u32*)d_y, (u32*)d_q);
+  return fr_bary_launch<false>(c, plan, (const u32*)d_evals, log_n, k, (const u32*)d_points, order, (u32*)d_y, (u32*)nullptr);
+}
+static int fr_bary_host(blsgpu_ctx* c, bool open, const uint64_t* evals, int log_n, size_t k, const uint64_t* points, int order, uint64_t* y, uint64_t* q) {
+  bool work;
+  if (int rc = fr_bary_check(c, open, evals, log_n, k, points, order, y, q, false, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HostCall h(c);
+  const size_t data = (k << log_n) * 32;
+  void* de = h.in(c->io_a, evals, data);
+  void* dp = h.in(c->io_b, points, k * 32);
+  void* dy = h.out(c->io_out, y, k * 32);
+  void* dq = open ? h.out(c->io_e, q, data) : nullptr;
+  if (h.rc) return h.rc;
+  return h.finish(fr_bary_device(c, open, de, log_n, k, dp, order, dy, dq));
+}
+extern "C" int blsgpu_fr_bary_eval_many_device(blsgpu_ctx* c, const void* d_evals, int log_n, size_t k, const void* d_points, int order, void* d_y) { CTX_CLAIM(c);
+  return fr_bary_device(c, false, d_evals, log_n, k, d_points, order, d_y, nullptr);
+}
+extern "C" int blsgpu_fr_bary_open_many_device(blsgpu_ctx* c, const void* d_evals, int log_n, size_t k, const void* d_points, int order, void* d_y, void* d_q) { CTX_CLAIM(c);
+  return fr_bary_device(c, true, d_evals, log_n, k, d_points, order, d_y, d_q);
+}
+extern "C" int blsgpu_fr_bary_eval_many(blsgpu_ctx* c, const uint64_t* evals, int log_n, size_t k, const uint64_t* points, int order, uint64_t* y) { CTX_CLAIM(c);
+  return fr_bary_host(c, false, evals, log_n, k, points, order, y, nullptr);
+}
+extern "C" int blsgpu_fr_bary_open_many(blsgpu_ctx* c, const uint64_t* evals, int log_n, size_t k, const uint64_t* points, int order, uint64_t* y, uint64_t* q) { CTX_CLAIM(c);
+  return fr_bary_host(c, true, evals, log_n, k, points, order, y, q);
 }
 
 // ---- sparse matrix-vector products: a resident CSR matrix times k vectors (fr_spmv.hip.h; fr_spmv_plan.h decides the launches) ------------

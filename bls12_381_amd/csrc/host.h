@@ -224,6 +224,8 @@ struct blsgpu_ctx {
   bool frs_lds_ready = false;           // the scan kernels' dynamic LDS (more than the 64 KB a kernel gets unasked) has been granted on this device
   DevBuf frm_rec, frm_scratch;          // blsgpu_fr_sumcheck_round_device: one record per tile; blsgpu_fr_mle_eval_device: the folded copy of the tables (fr_mle_plan.h)
   bool frm_lds_ready = false;           // ... and the round kernels' dynamic LDS
+  DevBuf frb_rec, frb_rowrec;           // blsgpu_fr_bary_*: one record per tile of a row longer than a tile, one per such row (fr_bary_plan.h)
+  bool frb_lds_ready = false;           // ... and the tile kernels' dynamic LDS
 };
 
 static inline KTimer* ktimer_of(blsgpu_ctx* c) { return &c->ktimer; }

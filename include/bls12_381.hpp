@@ -360,6 +360,32 @@ inline std::vector<FrLimbs> fr_batch_invert(const std::vector<FrLimbs>& v, std::
   check(blsgpu_fr_batch_invert(Context::instance().handle(), v[0].data(), v.size(), out[0].data(), nonzero ? nonzero->data() : nullptr), "fr_batch_invert");
   return out;
 }
+// Polynomials in evaluation form (include/bls12_381_hip.h: blsgpu_fr_bary_*): k rows of evals.size() / k = 2^log_n values on the roots of
+// unity, in natural or bit-reversed order, points[i] = z of row i (inside the domain or not).  fr_bary_eval returns y[i] = p_i(z_i);
+// fr_bary_open also the values of (p_i(X) - y[i]) / (X - z_i) on the same domain, in the same order.
+enum class FrOrder { Natural = 0, BitReversed = 1 };
+struct FrOpening { std::vector<FrLimbs> y, q; };
+namespace detail {
+inline int fr_bary_log_n(const char* what, size_t len, size_t k, size_t points) {
+  if (k == 0 || len == 0 || len % k || points != k) throw std::invalid_argument(std::string(what) + ": k rows of equal size and one point per row");
+  const size_t n = len / k;
+  if (n & (n - 1)) throw std::invalid_argument(std::string(what) + ": the row length must be a power of two");
+  int log_n = 0; while (((size_t)1 << log_n) < n) log_n++;
+  return log_n;
+}
+}  // namespace detail
+inline std::vector<FrLimbs> fr_bary_eval(const std::vector<FrLimbs>& evals, size_t k, const std::vector<FrLimbs>& points, FrOrder order = FrOrder::Natural) {
+  const int log_n = detail::fr_bary_log_n("fr_bary_eval", evals.size(), k, points.size());
+  std::vector<FrLimbs> y(k);
+  check(blsgpu_fr_bary_eval_many(Context::instance().handle(), evals[0].data(), log_n, k, points[0].data(), (int)order, y[0].data()), "fr_bary_eval");
+  return y;
+}
+inline FrOpening fr_bary_open(const std::vector<FrLimbs>& evals, size_t k, const std::vector<FrLimbs>& points, FrOrder order = FrOrder::Natural) {
+  const int log_n = detail::fr_bary_log_n("fr_bary_open", evals.size(), k, points.size());
+  FrOpening o{std::vector<FrLimbs>(k), std::vector<FrLimbs>(evals.size())};
+  check(blsgpu_fr_bary_open_many(Context::instance().handle(), evals[0].data(), log_n, k, points[0].data(), (int)order, o.y[0].data(), o.q[0].data()), "fr_bary_open");
+  return o;
+}
 // A CSR matrix over Fr resident on the device (blsgpu_fr_matrix): validated and planned once, multiplied many times.  row_ptr has
 // n_rows + 1 entries from 0 to nnz = col.size() = val.size(); col[p] < n_cols; repeated columns inside a row add; rows may be empty.
 class FrMatrix {

@@ -542,6 +542,31 @@ int blsgpu_fr_scan_many_device(blsgpu_ctx* ctx, int op, int exclusive, const voi
  * out == in, asynchrony and refusals as for blsgpu_fr_scan_many. */
 int blsgpu_fr_batch_invert(blsgpu_ctx* ctx, const uint64_t* values, size_t n, uint64_t* out, uint8_t* nonzero_flags);
 int blsgpu_fr_batch_invert_device(blsgpu_ctx* ctx, const void* d_in, size_t n, void* d_out, void* d_nonzero_flags);
+/* Polynomials held in EVALUATION form (the Lagrange basis): the value at a point and the quotient of a KZG opening without leaving that
+ * form.  k rows of n = 2^log_n scalars laid end to end (the layout of blsgpu_fr_ntt_many); row v holds f_v[i] = p_v(D[i]) for the unique
+ * p_v of degree < n, with w the root blsgpu_fr_ntt uses for log_n and
+ *   order BLSGPU_FR_ORDER_NATURAL  D[i] = w^i
+ *   order BLSGPU_FR_ORDER_BITREV   D[i] = w^bitrev(i, log_n)      (how blob formats store their rows)
+ * `points` holds k scalars, z_v the point of row v (data, so a device pointer in the device form, as for HORNER).
+ *   eval  y[v] = p_v(z_v)
+ *   open  y[v] as above and q[v][i] = q_v(D[i]) for q_v(X) = (p_v(X) - y[v]) / (X - z_v), of degree < n - 1: the scalars of the proof
+ *         MSM over a Lagrange SRS, in the order of the input.
+ * A point that lies IN the domain (z_v = D[j]) is handled exactly -- y = f[j], and q[j] is the sum the division by zero stands for --
+ * and is found and resolved on the device: the launches depend on the shape alone.  At log_n = 0, y = f[0] and q[0] = 0 for every z.
+ * Inputs must be canonical Montgomery limbs, outputs are.  One pass over the data per row that fits a tile of 2048 scalars (n <= 2048),
+ * one more for the quotient of longer rows; results are limb-identical from run to run.  log_n in [0, 28], k * 2^log_n <= 2^28, k == 0
+ * is a no-op.  Device pointers must be 16-byte aligned.  There is no in-place form: for rows longer than a tile d_q is staging while
+ * d_evals is still being read.  The device forms are asynchronous on the context's stream and never synchronise; their scratch is the
+ * context's own (the forward twiddle table of log_n, shared with the transform, and 112 bytes per tile of a long row) and is not shared
+ * with pipelined *_msm_device calls in flight.  BLSGPU_ERR_ARG (nothing staged or launched): a NULL pointer with work to do, log_n,
+ * k * 2^log_n (64-bit overflow included) or order out of range, a misaligned device pointer, any overlap of q or y with the evals or
+ * points ranges, or of q with y. */
+#define BLSGPU_FR_ORDER_NATURAL 0
+#define BLSGPU_FR_ORDER_BITREV  1
+int blsgpu_fr_bary_eval_many(blsgpu_ctx* ctx, const uint64_t* evals, int log_n, size_t k, const uint64_t* points, int order, uint64_t* y);
+int blsgpu_fr_bary_eval_many_device(blsgpu_ctx* ctx, const void* d_evals, int log_n, size_t k, const void* d_points, int order, void* d_y);
+int blsgpu_fr_bary_open_many(blsgpu_ctx* ctx, const uint64_t* evals, int log_n, size_t k, const uint64_t* points, int order, uint64_t* y, uint64_t* q);
+int blsgpu_fr_bary_open_many_device(blsgpu_ctx* ctx, const void* d_evals, int log_n, size_t k, const void* d_points, int order, void* d_y, void* d_q);
 /* Sparse matrix-vector products over Fr: the step a = A z, b = B z, c = C z in front of a Groth16 / Marlin / PLONK-style prover's
  * transforms -- each output a short linear combination of gathered witness entries with fixed per-circuit coefficients.  The matrix is
  * fixed per circuit and reused for every proof, exactly as an SRS is, so it is a resident handle like blsgpu_bases: upload, validate

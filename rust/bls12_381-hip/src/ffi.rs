@@ -166,6 +166,10 @@ extern "C" {
     pub fn blsgpu_fr_scan_many_device(ctx: *mut BlsgpuCtx, op: c_int, exclusive: c_int, d_in: *const c_void, len: usize, k: usize, d_points: *const c_void, d_out: *mut c_void) -> c_int;
     pub fn blsgpu_fr_batch_invert(ctx: *mut BlsgpuCtx, values: *const u64, n: usize, out: *mut u64, nonzero_flags: *mut u8) -> c_int;
     pub fn blsgpu_fr_batch_invert_device(ctx: *mut BlsgpuCtx, d_in: *const c_void, n: usize, d_out: *mut c_void, d_nonzero_flags: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_bary_eval_many(ctx: *mut BlsgpuCtx, evals: *const u64, log_n: c_int, k: usize, points: *const u64, order: c_int, y: *mut u64) -> c_int;
+    pub fn blsgpu_fr_bary_eval_many_device(ctx: *mut BlsgpuCtx, d_evals: *const c_void, log_n: c_int, k: usize, d_points: *const c_void, order: c_int, d_y: *mut c_void) -> c_int;
+    pub fn blsgpu_fr_bary_open_many(ctx: *mut BlsgpuCtx, evals: *const u64, log_n: c_int, k: usize, points: *const u64, order: c_int, y: *mut u64, q: *mut u64) -> c_int;
+    pub fn blsgpu_fr_bary_open_many_device(ctx: *mut BlsgpuCtx, d_evals: *const c_void, log_n: c_int, k: usize, d_points: *const c_void, order: c_int, d_y: *mut c_void, d_q: *mut c_void) -> c_int;
     pub fn blsgpu_fr_matrix_upload(ctx: *mut BlsgpuCtx, n_rows: usize, n_cols: usize, row_ptr: *const u32, col: *const u32, val: *const u64, out: *mut c_void) -> c_int;
     pub fn blsgpu_fr_matrix_from_device(ctx: *mut BlsgpuCtx, n_rows: usize, n_cols: usize, d_row_ptr: *const c_void, d_col: *const c_void, d_val: *const c_void, out: *mut c_void) -> c_int;
     pub fn blsgpu_fr_matrix_rows(m: *const c_void) -> usize;

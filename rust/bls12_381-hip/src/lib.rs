@@ -232,6 +232,37 @@ pub fn fr_batch_invert(gpu: &Gpu, values: &[Scalar]) -> Result<Vec<Option<Scalar
     check(unsafe { ffi::blsgpu_fr_batch_invert(gpu.ctx, input.as_ptr(), values.len(), out.as_mut_ptr(), flags.as_mut_ptr()) })?;
     Ok(limbs_scalars(gpu, &out)?.into_iter().zip(flags).map(|(s, f)| if f != 0 { Some(s) } else { None }).collect())
 }
+/// How a row of evaluations is ordered: `D[i] = w^i`, or `D[i] = w^bitrev(i)` (how blob formats store their rows).
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum FrOrder { Natural = 0, BitReversed = 1 }
+fn fr_bary_log_n(len: usize, k: usize, points: usize) -> c_int {
+    assert!(k > 0 && len > 0 && len % k == 0 && points == k);
+    let n = len / k;
+    assert!(n.is_power_of_two());
+    n.trailing_zeros() as c_int
+}
+/// `k` polynomials in evaluation form, row v = p_v on the `evals.len() / k` = 2^log_n roots of unity in the given order: returns
+/// `p_v(points[v])` (`blsgpu_fr_bary_eval_many`).  A point inside the domain is handled exactly.
+pub fn fr_bary_eval(gpu: &Gpu, evals: &[Scalar], k: usize, points: &[Scalar], order: FrOrder) -> Result<Vec<Scalar>, Error> {
+    if evals.is_empty() && k == 0 { return Ok(Vec::new()); }
+    let log_n = fr_bary_log_n(evals.len(), k, points.len());
+    let (input, pts) = (scalar_limbs(gpu, evals)?, scalar_limbs(gpu, points)?);
+    let mut y = vec![0u64; k * 4];
+    check(unsafe { ffi::blsgpu_fr_bary_eval_many(gpu.ctx, input.as_ptr(), log_n, k, pts.as_ptr(), order as c_int, y.as_mut_ptr()) })?;
+    limbs_scalars(gpu, &y)
+}
+/// As `fr_bary_eval`, and the evaluations on the same domain, in the same order, of the quotients (p_v(X) - y_v) / (X - z_v): the
+/// scalars of a KZG proof over a Lagrange SRS (`blsgpu_fr_bary_open_many`).  Returns `(y, q)`.
+pub fn fr_bary_open(gpu: &Gpu, evals: &[Scalar], k: usize, points: &[Scalar], order: FrOrder) -> Result<(Vec<Scalar>, Vec<Scalar>), Error> {
+    if evals.is_empty() && k == 0 { return Ok((Vec::new(), Vec::new())); }
+    let log_n = fr_bary_log_n(evals.len(), k, points.len());
+    let (input, pts) = (scalar_limbs(gpu, evals)?, scalar_limbs(gpu, points)?);
+    let (mut y, mut q) = (vec![0u64; k * 4], vec![0u64; input.len()]);
+    check(unsafe {
+        ffi::blsgpu_fr_bary_open_many(gpu.ctx, input.as_ptr(), log_n, k, pts.as_ptr(), order as c_int, y.as_mut_ptr(), q.as_mut_ptr())
+    })?;
+    Ok((limbs_scalars(gpu, &y)?, limbs_scalars(gpu, &q)?))
+}
 /// A CSR matrix over `Scalar` resident on the GPU (`blsgpu_fr_matrix`): a circuit's constraint matrices, uploaded, validated and planned
 /// once and multiplied with every proof's witness.  The FFI layer sees the handle as an untyped pointer; this is its type.
 pub struct FrMatrix { handle: *mut c_void, rows: usize, cols: usize }
