@@ -98,6 +98,19 @@ SIGNATURES = {
     "blsgpu_fr_sumcheck_round": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "blsgpu_fr_sumcheck_finish": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "blsgpu_fr_sumcheck_free": (None, [c_vp]),
+    "blsgpu_fr_poseidon_create": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)]),
+    "blsgpu_fr_poseidon_width": (c_int, [c_vp]),
+    "blsgpu_fr_poseidon_rounds_full": (c_int, [c_vp]),
+    "blsgpu_fr_poseidon_rounds_partial": (c_int, [c_vp]),
+    "blsgpu_fr_poseidon_form": (c_int, [c_vp]),
+    "blsgpu_fr_poseidon_products": (c_sz, [c_vp]),
+    "blsgpu_fr_poseidon_free": (None, [c_vp]),
+    "blsgpu_fr_poseidon_permute": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_fr_poseidon_permute_device": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_fr_poseidon_hash_many": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_fr_poseidon_hash_many_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_fr_poseidon_merkle": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_poseidon_merkle_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_sz, c_vp, c_vp]),
     "blsgpu_g1_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),
     "blsgpu_g2_ntt_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),
     "blsgpu_g1_ntt_many_device": (c_int, [c_vp, c_vp, c_int, c_sz, c_int]),

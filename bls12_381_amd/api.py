@@ -64,6 +64,7 @@ def _flags(f, n):
 
 FR_SCAN_SUM, FR_SCAN_PRODUCT, FR_SCAN_HORNER = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_SCAN_*
 FR_ORDER_NATURAL, FR_ORDER_BITREV = 0, 1                    # include/bls12_381_hip.h: BLSGPU_FR_ORDER_*
+FR_POSEIDON_AUTO, FR_POSEIDON_DENSE, FR_POSEIDON_SPARSE = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_POSEIDON_*
 FR_GENERATOR = 7                          # scalar.rs:99-105 GENERATOR (`MULTIPLICATIVE_GENERATOR` :708): the usual coset shift
 
 
@@ -199,6 +200,102 @@ class FrMatrix:
     def close(self):
         if self.handle:
             self.ctx.lib.blsgpu_fr_matrix_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _fr_limbs(values, shape, what):
+    """Python ints in [0, r) (nested lists allowed) | an array of Montgomery limbs -> a `shape` + (4,) u64 array of Montgomery limbs"""
+    if isinstance(values, np.ndarray):
+        return _u64(values, tuple(shape) + (4,)).copy()
+    flat = list(values) if isinstance(values, (list, tuple)) else [values]
+    while flat and isinstance(flat[0], (list, tuple)):
+        flat = [x for row in flat for x in row]
+    if all(isinstance(x, (int, np.integer)) for x in flat):
+        return _point_limbs(flat, len(flat), what).reshape(tuple(shape) + (4,))
+    return _u64(np.array(values, dtype=np.uint64), tuple(shape) + (4,)).copy()
+
+
+class FrPoseidon:
+    """A Poseidon instance over Fr resident on the device (`blsgpu_fr_poseidon`): width, rounds, round constants and matrix are the
+    CALLER's (the library ships no standard parameter set), validated and planned once by Context.fr_poseidon.  Scalars go in and come
+    out as u64 arrays of Montgomery limbs; Python ints in [0, r) are accepted for inputs and for the tag."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def _get(self, fn):
+        return int(fn(self.handle)) if self.handle else 0
+
+    @property
+    def width(self):
+        return self._get(self.ctx.lib.blsgpu_fr_poseidon_width)
+
+    @property
+    def rounds_full(self):
+        return self._get(self.ctx.lib.blsgpu_fr_poseidon_rounds_full)
+
+    @property
+    def rounds_partial(self):
+        return self._get(self.ctx.lib.blsgpu_fr_poseidon_rounds_partial)
+
+    @property
+    def form(self):
+        """FR_POSEIDON_DENSE or FR_POSEIDON_SPARSE: the partial rounds the handle runs"""
+        return self._get(self.ctx.lib.blsgpu_fr_poseidon_form)
+
+    @property
+    def products_per_permutation(self):
+        return self._get(self.ctx.lib.blsgpu_fr_poseidon_products)
+
+    def _tag(self, tag):
+        return _fr_limbs(tag, (), "fr_poseidon tag")
+
+    def permute(self, states):
+        """n states of t scalars ((n, t, 4) limbs or n x t ints) -> the permuted states as a new (n, t, 4) array"""
+        v = _fr_limbs(states, (-1, self.width), "fr_poseidon.permute")
+        out = np.zeros_like(v)
+        check(self.ctx.lib.blsgpu_fr_poseidon_permute(self.ctx.h, self.handle, _ptr(v), v.shape[0], _ptr(out)), "fr_poseidon_permute")
+        return out
+
+    def hash_many(self, inputs, tag=0):
+        """n preimages of t - 1 scalars -> n digests (n, 4): element 1 of the permutation of (tag, x_1 .. x_(t-1))"""
+        v = _fr_limbs(inputs, (-1, self.width - 1), "fr_poseidon.hash_many")
+        out = np.zeros((v.shape[0], 4), dtype=np.uint64)
+        check(self.ctx.lib.blsgpu_fr_poseidon_hash_many(self.ctx.h, self.handle, _ptr(self._tag(tag)), _ptr(v), v.shape[0], _ptr(out)), "fr_poseidon_hash_many")
+        return out
+
+    def merkle(self, leaves, height, k=1, tag=0, with_nodes=True):
+        """k trees of (t-1)^height leaves each, tree after tree ((k * a^height, 4) limbs or ints).  Returns (roots (k, 4), nodes): nodes
+        holds every inner level, level 1 first and the roots last (None with with_nodes=False)."""
+        a = self.width - 1
+        v = _fr_limbs(leaves, (k * a ** height,), "fr_poseidon.merkle")
+        count = k * height if a == 1 else k * (a ** height - 1) // (a - 1)
+        nodes = np.zeros((count, 4), dtype=np.uint64) if with_nodes else None
+        roots = np.zeros((k, 4), dtype=np.uint64)
+        check(self.ctx.lib.blsgpu_fr_poseidon_merkle(self.ctx.h, self.handle, _ptr(self._tag(tag)), _ptr(v), int(height), int(k), _ptr(nodes), _ptr(roots)), "fr_poseidon_merkle")
+        return roots, nodes
+
+    def permute_device(self, d_states, n, d_out):
+        """the same on n * t scalars in device memory, asynchronous on the context's stream; d_out == d_states is the in-place form"""
+        check(self.ctx.lib.blsgpu_fr_poseidon_permute_device(self.ctx.h, self.handle, d_states, int(n), d_out), "fr_poseidon_permute_device")
+
+    def hash_many_device(self, d_inputs, n, d_out, tag=0):
+        """n * (t - 1) scalars at d_inputs -> n digests at d_out; the tag is a host-side parameter"""
+        check(self.ctx.lib.blsgpu_fr_poseidon_hash_many_device(self.ctx.h, self.handle, _ptr(self._tag(tag)), d_inputs, int(n), d_out), "fr_poseidon_hash_many_device")
+
+    def merkle_device(self, d_leaves, height, k, d_roots, d_nodes=None, tag=0):
+        """k trees over k * (t-1)^height scalars at d_leaves -> k roots at d_roots and, if d_nodes is given, every inner level there"""
+        check(self.ctx.lib.blsgpu_fr_poseidon_merkle_device(self.ctx.h, self.handle, _ptr(self._tag(tag)), d_leaves, int(height), int(k), d_nodes, d_roots), "fr_poseidon_merkle_device")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_fr_poseidon_free(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -833,6 +930,21 @@ class Context:
     def fr_bary_open_device(self, d_evals, log_n, k, d_points, d_y, d_q, order=FR_ORDER_NATURAL):
         """the same with the quotient written to d_q (k * 2^log_n scalars, no overlap with the inputs: there is no in-place form)"""
         check(self.lib.blsgpu_fr_bary_open_many_device(self.h, d_evals, log_n, k, d_points, int(order), d_y, d_q), "fr_bary_open_device")
+
+    def fr_poseidon(self, t, r_full, r_partial, constants, mds, form=FR_POSEIDON_AUTO):
+        """a Poseidon instance made resident (include/bls12_381_hip.h: blsgpu_fr_poseidon_create): width t in {2, 3, 4, 5, 9, 12}, r_full
+        (even) full and r_partial partial rounds, constants[(r_full + r_partial)][t] and the t x t matrix mds as Python ints in [0, r) or
+        arrays of Montgomery limbs.  The parameters are the caller's: the library ships no standard set
+        (bls12_381_amd.synthetic.poseidon_test_params makes seeded TEST parameters).  form=FR_POSEIDON_AUTO takes the sparse partial
+        rounds when they can be derived, FR_POSEIDON_DENSE the textbook ones.  Returns an FrPoseidon."""
+        rc = _fr_limbs(constants, (-1,), "fr_poseidon constants")
+        mm = _fr_limbs(mds, (-1,), "fr_poseidon mds")
+        t, r_full, r_partial = int(t), int(r_full), int(r_partial)
+        if t < 1 or r_full < 0 or r_partial < 0 or rc.shape[0] != (r_full + r_partial) * t or mm.shape[0] != t * t:
+            raise ValueError("fr_poseidon: expected (r_full + r_partial) * t round constants and t * t matrix entries")
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_poseidon_create(self.h, t, r_full, r_partial, _ptr(rc), _ptr(mm), int(form), ctypes.byref(h)), "fr_poseidon")
+        return FrPoseidon(self, h)
 
     def fr_matrix(self, row_ptr, col, val, n_cols):
         """a CSR matrix made resident (include/bls12_381_hip.h: blsgpu_fr_matrix_upload): row_ptr has n_rows + 1 entries from 0 to

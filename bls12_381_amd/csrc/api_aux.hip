@@ -7,6 +7,7 @@
 #include "fr_bary.hip.h"
 #include "fr_spmv.hip.h"
 #include "fr_mle.hip.h"
+#include "fr_poseidon.hip.h"
 #include "h2c.hip.h"
 #include "expand_kernels.hip.h"
 #include "codec.hip.h"
@@ -864,6 +865,167 @@ extern "C" int blsgpu_fr_spmv(blsgpu_ctx* c, const blsgpu_fr_matrix* m, const ui
   if (h.rc) return h.rc;
   if (!dx) { if (!h.reserve(c->io_a, 16)) return h.rc; dx = c->io_a.p; }      // n_cols == 0: nothing is gathered, but the device form wants a pointer
   return h.finish(blsgpu_fr_spmv_device(c, m, dx, k, o));
+}
+
+// ---- Poseidon over Fr: permutations, hashes, Merkle trees (fr_poseidon.hip.h; fr_poseidon_plan.h validates, derives and plans) ------------
+extern "C" int blsgpu_fr_poseidon_create(blsgpu_ctx* c, int t, int r_full, int r_partial, const uint64_t* round_constants, const uint64_t* mds, int form, blsgpu_fr_poseidon** out) { CTX_CLAIM(c);
+  if (out) *out = nullptr;
+  if (!c || !out) return bad("fr_poseidon: NULL context / out");
+  FrPoseidonHost h;
+  const std::string what = fr_poseidon_build(t, r_full, r_partial, round_constants, mds, form, &h);
+  if (!what.empty()) { g_err = what; return BLSGPU_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  blsgpu_fr_poseidon* p = new blsgpu_fr_poseidon();
+  p->device = c->device; p->t = t; p->r_full = r_full; p->r_partial = r_partial; p->form = h.form; p->args = h.args; p->products = h.products;
+  const size_t bytes = h.image.size() * 4;
+  hipError_t e = hipMalloc((void**)&p->image, bytes);
+  if (e == hipSuccess) e = hipMemcpy(p->image, h.image.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { if (p->image) hipFree(p->image); delete p; return fail("fr_poseidon: upload of the constant image", e, __LINE__); }
+  *out = p;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_poseidon_width(const blsgpu_fr_poseidon* p) { return p ? p->t : 0; }
+extern "C" int blsgpu_fr_poseidon_rounds_full(const blsgpu_fr_poseidon* p) { return p ? p->r_full : 0; }
+extern "C" int blsgpu_fr_poseidon_rounds_partial(const blsgpu_fr_poseidon* p) { return p ? p->r_partial : 0; }
+extern "C" int blsgpu_fr_poseidon_form(const blsgpu_fr_poseidon* p) { return p ? p->form : 0; }
+extern "C" size_t blsgpu_fr_poseidon_products(const blsgpu_fr_poseidon* p) { return p ? p->products : 0; }
+extern "C" void blsgpu_fr_poseidon_free(blsgpu_fr_poseidon* p) {
+  if (!p) return;
+  hipSetDevice(p->device);
+  hipDeviceSynchronize();                  // an asynchronous call may still be reading the image
+  if (p->image) hipFree(p->image);
+  delete p;
+}
+static bool frp_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+}
+static int frp_handle_check(blsgpu_ctx* c, const blsgpu_fr_poseidon* p) {
+  if (!c) return bad("fr_poseidon: NULL context");
+  if (!p) return bad("fr_poseidon: NULL handle");
+  if (p->device != c->device) return bad("fr_poseidon: the handle lives on another device than the context");
+  return BLSGPU_OK;
+}
+static int frp_tag_check(const uint64_t* tag, FrArg* out) {
+  if (!tag) return bad("fr_poseidon: NULL tag");
+  if (!frp_below_r(tag)) return bad("fr_poseidon: tag is not a canonical Scalar (limbs >= r)");
+  for (int w = 0; w < 4; w++) { out->w[2 * w] = (u32)tag[w]; out->w[2 * w + 1] = (u32)(tag[w] >> 32); }
+  return BLSGPU_OK;
+}
+// every argument check of permute / hash_many in both forms, before anything is staged or launched.  *work: there is something to do.
+static int frp_many_check(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, bool hash, const uint64_t* tag, FrArg* tg, const void* in, size_t n, const void* out, bool device, bool* work) {
+  *work = false;
+  if (int rc = frp_handle_check(c, p)) return rc;
+  if (hash) if (int rc = frp_tag_check(tag, tg)) return rc;
+  if (n > FRP_MAX_TOTAL / (size_t)p->t) return bad("fr_poseidon: n * t must not exceed 2^28");
+  if (!n) return BLSGPU_OK;
+  if (!in || !out) return bad("fr_poseidon: NULL pointer with work to do");
+  if (device && (((uintptr_t)in | (uintptr_t)out) & 15)) return bad("fr_poseidon: device pointers must be 16-byte aligned");
+  const size_t in_bytes = n * (size_t)(hash ? p->t - 1 : p->t) * 32, out_bytes = n * (size_t)(hash ? 1 : p->t) * 32;
+  if (!(!hash && in == out) && frp_overlap(in, in_bytes, out, out_bytes))
+    return bad(hash ? "fr_poseidon_hash_many: out overlaps the inputs" : "fr_poseidon_permute: out overlaps the states (only out == states, the in-place form, is allowed)");
+  *work = true;
+  return BLSGPU_OK;
+}
+// one step of a plan on the kernels of the handle's width and form
+template <int T, bool SP>
+static void frp_launch_step(hipStream_t st, const blsgpu_fr_poseidon* p, const FrPoseidonStep& s, const FrArg& tag, const u32* src, u32* dst, u32* roots) {
+  const dim3 grid(s.grid), block(s.block);
+  switch (s.kernel) {
+    case FRP_K_PERMUTE: KLAUNCH((k_frp_permute<T, SP>), grid, block, 0, st, p->args, (const u32*)p->image, src, dst, s.items); break;
+    default: KLAUNCH((k_frp_hash<T, SP>), grid, block, 0, st, p->args, (const u32*)p->image, tag, src, dst, roots, s.items); break;      // HASH, LEVEL
+  }
+}
+static int frp_run_plan(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const FrPoseidonPlan& plan, const FrArg& tag, const u32* in, u32* out, u32* nodes) {
+  hipStream_t st = c->stream;
+  for (int i = 0; i < plan.n_steps; i++) {
+    const FrPoseidonStep& s = plan.step[i];
+    if (s.kernel == FRP_K_COPY) { HIPCHK(hipMemcpyAsync(out, in, s.items * 32, hipMemcpyDeviceToDevice, st)); continue; }
+    const u32* src = (s.src == FRP_BUF_IN ? in : (const u32*)nodes) + s.src_off * 8;
+    u32* dst = (s.dst == FRP_BUF_OUT ? out : nodes) + s.dst_off * 8;
+    u32* roots = s.roots && s.dst != FRP_BUF_OUT ? out : nullptr;      // the roots next to the nodes array
+#define FRP_CASE(T) case T: if (p->form == FRP_FORM_SPARSE) frp_launch_step<T, true>(st, p, s, tag, src, dst, roots); else frp_launch_step<T, false>(st, p, s, tag, src, dst, roots); break;
+    switch (p->t) { FRP_CASE(2) FRP_CASE(3) FRP_CASE(4) FRP_CASE(5) FRP_CASE(9) FRP_CASE(12) default: return bad("fr_poseidon: no kernel for this width"); }
+#undef FRP_CASE
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+static int frp_many_device(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, bool hash, const uint64_t* tag, const void* d_in, size_t n, void* d_out) {
+  bool work; FrArg tg = {};
+  if (int rc = frp_many_check(c, p, hash, tag, &tg, d_in, n, d_out, true, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const FrPoseidonPlan plan = fr_poseidon_many_plan(hash ? FRP_K_HASH : FRP_K_PERMUTE, p->t, n);
+  if (plan.n_steps < 0) return bad("fr_poseidon: n * t must not exceed 2^28");
+  return frp_run_plan(c, p, plan, tg, (const u32*)d_in, (u32*)d_out, nullptr);
+}
+static int frp_many_host(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, bool hash, const uint64_t* tag, const uint64_t* in, size_t n, uint64_t* out) {
+  bool work; FrArg tg = {};
+  if (int rc = frp_many_check(c, p, hash, tag, &tg, in, n, out, false, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HostCall h(c);
+  void* di = h.in(c->io_a, in, n * (size_t)(hash ? p->t - 1 : p->t) * 32);
+  void* dout = h.out(c->io_out, out, n * (size_t)(hash ? 1 : p->t) * 32);
+  if (h.rc) return h.rc;
+  return h.finish(frp_many_device(c, p, hash, tag, di, n, dout));
+}
+extern "C" int blsgpu_fr_poseidon_permute_device(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const void* d_states, size_t n, void* d_out) { CTX_CLAIM(c);
+  return frp_many_device(c, p, false, nullptr, d_states, n, d_out);
+}
+extern "C" int blsgpu_fr_poseidon_permute(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const uint64_t* states, size_t n, uint64_t* out) { CTX_CLAIM(c);
+  return frp_many_host(c, p, false, nullptr, states, n, out);
+}
+extern "C" int blsgpu_fr_poseidon_hash_many_device(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const void* d_inputs, size_t n, void* d_out) { CTX_CLAIM(c);
+  return frp_many_device(c, p, true, tag, d_inputs, n, d_out);
+}
+extern "C" int blsgpu_fr_poseidon_hash_many(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const uint64_t* inputs, size_t n, uint64_t* out) { CTX_CLAIM(c);
+  return frp_many_host(c, p, true, tag, inputs, n, out);
+}
+// every argument check of merkle in both forms; *plan: the launches (n_steps == 0: nothing to do)
+static int frp_merkle_check(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const uint64_t* tag, FrArg* tg, const void* leaves, int height, size_t k, const void* nodes, const void* roots,
+                            bool device, FrPoseidonPlan* plan) {
+  plan->n_steps = 0;
+  if (int rc = frp_handle_check(c, p)) return rc;
+  if (int rc = frp_tag_check(tag, tg)) return rc;
+  if (height < 0 || height > 28) return bad("fr_poseidon_merkle: height must be in [0, 28]");
+  *plan = fr_poseidon_merkle_plan(p->t, height, k, nodes != nullptr);
+  if (plan->n_steps < 0) { plan->n_steps = 0; return bad("fr_poseidon_merkle: k * (t-1)^height and the node count must not exceed 2^28"); }
+  if (!k) return BLSGPU_OK;
+  if (!leaves || !roots) { plan->n_steps = 0; return bad("fr_poseidon_merkle: NULL leaves / roots with work to do"); }
+  if (device && (((uintptr_t)leaves | (uintptr_t)nodes | (uintptr_t)roots) & 15)) { plan->n_steps = 0; return bad("fr_poseidon_merkle: device pointers must be 16-byte aligned"); }
+  const size_t lb = plan->leaves * 32, nb = plan->node_count * 32, rb = k * 32;
+  if (frp_overlap(leaves, lb, roots, rb) || frp_overlap(leaves, lb, nodes, nb) || frp_overlap(nodes, nb, roots, rb)) {
+    plan->n_steps = 0;
+    return bad("fr_poseidon_merkle: leaves, nodes and roots must not overlap");
+  }
+  return BLSGPU_OK;
+}
+static int frp_merkle_device(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const uint64_t* tag, const void* d_leaves, int height, size_t k, void* d_nodes, void* d_roots) {
+  FrPoseidonPlan plan; FrArg tg = {};
+  if (int rc = frp_merkle_check(c, p, tag, &tg, d_leaves, height, k, d_nodes, d_roots, true, &plan)) return rc;
+  if (!plan.n_steps) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  u32* nodes = (u32*)d_nodes;
+  if (!nodes && plan.scratch) {
+    if (c->frp_nodes.reserve(plan.scratch * 32)) { g_err = "hipMalloc(fr poseidon scratch) failed"; return BLSGPU_ERR_HIP; }
+    nodes = c->frp_nodes.as<u32>();
+  }
+  return frp_run_plan(c, p, plan, tg, (const u32*)d_leaves, (u32*)d_roots, nodes);
+}
+extern "C" int blsgpu_fr_poseidon_merkle_device(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const void* d_leaves, int height, size_t k, void* d_nodes, void* d_roots) { CTX_CLAIM(c);
+  return frp_merkle_device(c, p, tag, d_leaves, height, k, d_nodes, d_roots);
+}
+extern "C" int blsgpu_fr_poseidon_merkle(blsgpu_ctx* c, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const uint64_t* leaves, int height, size_t k, uint64_t* nodes, uint64_t* roots) { CTX_CLAIM(c);
+  FrPoseidonPlan plan; FrArg tg = {};
+  if (int rc = frp_merkle_check(c, p, tag, &tg, leaves, height, k, nodes, roots, false, &plan)) return rc;
+  if (!plan.n_steps) return BLSGPU_OK;
+  HostCall h(c);
+  void* dl = h.in(c->io_a, leaves, plan.leaves * 32);
+  void* dn = nodes && plan.node_count ? h.out(c->io_e, nodes, plan.node_count * 32) : nullptr;
+  void* dr = h.out(c->io_out, roots, k * 32);
+  if (h.rc) return h.rc;
+  return h.finish(frp_merkle_device(c, p, tag, dl, height, k, dn, dr));
 }
 
 // ---- multilinear tables: folds, eq tables, evaluation, sumcheck rounds (fr_mle.hip.h; fr_mle_plan.h decides the launches) -----------------

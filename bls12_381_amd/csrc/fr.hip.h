@@ -136,6 +136,16 @@ __global__ void __launch_bounds__(256) k_fr_tw_levels(u32* __restrict__ tw, int 
 //   F-stage     inputs up to A2 V4:  a + b -> A4 V8 -> frl_reduce -> A1 V2;  (a + 8r - b) w' : A5 V12 -> A1 V2
 // Column bound of the product: 9 * A * 2^58 + 9 * 2^58 < 2^64 needs A <= 6; value bound: a w' / 2^261 + r < 2r needs
 // V <= 70 (2^261 / r = 70.6).
+// Poseidon (fr_poseidon.hip.h) adds sums of products and longer sums:
+//   frl_dot<G>  sum_g a_g b_g in ONE accumulator and one reduction: the column bound becomes 9 * (sum_g A_a A_b) * 2^58 + 9 * 2^58 < 2^64,
+//               i.e. sum_g A_a A_b <= 6, the value bound sum_g V_a V_b <= 70; result A1 V2 as for frl_mul (G = 1 is frl_mul)
+//   frl_carry   carry propagation alone: A <= 7 (limbs below 2^32) -> limbs 0..7 below 2^29, the top limb holds the value's bits from
+//               232 on (V 2^23 at most: A1 for V <= 64); the value does not change
+//   frl_reduce  is frl_carry + one quotient step and holds beyond its original A <= 4, V <= 8: with x = T 2^232 + L, P = (r >> 232) + 1
+//               and q = floor(T / P), x - q r < r + (q + 1) 2^232, below 2r for every q < 2^22 -- so A <= 7 (the carry pass), V <= 64
+//   round state s + C: A1 V2 + canonical = A2 V3;  S-box x x: A 2 x 2, V 3 x 3;  x2 x2: A 1 x 1, V 2 x 2;  x4 x: A 1 x 2, V 2 x 3
+//   row sums    chunks of at most six products of A1 operands by canonical constants; two chunks: A2 V4 -> frl_reduce
+//   sparse rows y_j + col_j z0: A2 -> frl_carry -> A1, V grows by 2 per round, frl_reduce every fourth round: V <= 8 where y_j is an operand
 struct FrL { u32 l[9]; };
 constexpr u32 M29 = (1u << 29) - 1;
 struct FrL9 { u32 w[9]; };
@@ -172,6 +182,8 @@ template <int WHICH> DEV FrL frl_sub(const FrL& a, const FrL& b) {        // a +
   return r;
 }
 // (a * b) / 2^261 mod r, result A1 V2; a: A <= 6 / (A of b), b: A1 canonical twiddle (see the bound table above)
+// (frl_dot<1> below is this column schedule again, kept apart so that the transform kernels' code does not change: a change to the
+// schedule or to the bounds of one of the two must be made in both)
 DEV FrL frl_mul(const FrL& a, const FrL& b) {
   u32 m[9];
   FrL r;
@@ -198,13 +210,50 @@ DEV FrL frl_mul(const FrL& a, const FrL& b) {
   r.l[8] = (u32)acc;
   return r;
 }
-// A <= 4, V <= 8  ->  A1, value in [0, 2r): carry propagation, then q = floor(top / ((r >> 232) + 1)) <= floor(x / r)
-// undershoots by at most one, so x - q r < 2r
-DEV FrL frl_reduce(const FrL& a) {
+// sum_g a[g] b[g] / 2^261 mod r, result A1 V2: frl_mul's columns with G products each, one Montgomery reduction for the sum.
+// sum_g A(a_g) A(b_g) <= 6 and sum_g V(a_g) V(b_g) <= 70 (see the bound table above)
+template <int G> DEV FrL frl_dot(const FrL* a, const FrL* b) {
+  u32 m[9];
+  FrL r;
+  u64 acc = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+      for (int i = 0; i <= k; i++) acc += (u64)a[g].l[i] * b[g].l[k - i];
+#pragma unroll
+    for (int i = 0; i < k; i++) acc += (u64)m[i] * FR_MOD_L.w[k - i];
+    m[k] = (0u - (u32)acc) & M29;
+    acc += (u64)m[k] * FR_MOD_L.w[0];
+    acc >>= 29;
+  }
+#pragma unroll
+  for (int k = 9; k < 17; k++) {
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+      for (int i = k - 8; i < 9; i++) acc += (u64)a[g].l[i] * b[g].l[k - i];
+#pragma unroll
+    for (int i = k - 8; i < 9; i++) acc += (u64)m[i] * FR_MOD_L.w[k - i];
+    r.l[k - 9] = (u32)acc & M29;
+    acc >>= 29;
+  }
+  r.l[8] = (u32)acc;
+  return r;
+}
+// A <= 7 -> limbs 0..7 below 2^29, the value unchanged (the top limb takes what is left: A1 while V <= 64)
+DEV FrL frl_carry(const FrL& a) {
   FrL t; u32 c = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) { u32 v = a.l[i] + c; t.l[i] = v & M29; c = v >> 29; }
   t.l[8] = a.l[8] + c;
+  return t;
+}
+// A <= 4, V <= 8  ->  A1, value in [0, 2r): carry propagation, then q = floor(top / ((r >> 232) + 1)) <= floor(x / r)
+// undershoots by at most one, so x - q r < 2r  (A <= 7, V <= 64 hold as well: the bound table above)
+DEV FrL frl_reduce(const FrL& a) {
+  const FrL t = frl_carry(a);
   const u32 q = t.l[8] / BLS_FR_TOP_P1;
   FrL r; int64_t cc = 0;
 #pragma unroll

@@ -30,6 +30,7 @@
 #include "scalar.hip.h"
 #include "limits.h"
 #include "diag.h"
+#include "fr_poseidon_plan.h"
 
 using namespace bls;
 
@@ -226,6 +227,7 @@ struct blsgpu_ctx {
   bool frm_lds_ready = false;           // ... and the round kernels' dynamic LDS
   DevBuf frb_rec, frb_rowrec;           // blsgpu_fr_bary_*: one record per tile of a row longer than a tile, one per such row (fr_bary_plan.h)
   bool frb_lds_ready = false;           // ... and the tile kernels' dynamic LDS
+  DevBuf frp_nodes;                     // blsgpu_fr_poseidon_merkle_device with nodes == NULL: the levels below the roots (fr_poseidon_plan.h)
 };
 
 static inline KTimer* ktimer_of(blsgpu_ctx* c) { return &c->ktimer; }
@@ -270,6 +272,15 @@ struct blsgpu_fr_matrix {
   u32* tile_row = nullptr;                         // the row of every tile's first entry (+ one closing word)
   u32* flag = nullptr;                             // [0] the validation kernel's verdict, [1] a row is empty
   bool has_empty = false;                          // a row without entries: the product zeroes its output first
+};
+
+// a Poseidon instance resident on the device (api_aux.hip: blsgpu_fr_poseidon_create; fr_poseidon.hip.h): the shape, the offsets of the
+// constant image's sections and the image itself, built once by fr_poseidon_plan.h
+struct blsgpu_fr_poseidon {
+  int device = 0; int t = 0, r_full = 0, r_partial = 0, form = 0;
+  FrpArgs args = {};
+  size_t products = 0;
+  u32* image = nullptr;
 };
 
 // a sumcheck in progress (api_aux.hip: blsgpu_fr_sumcheck_begin*; fr_mle.hip.h): its own copy of the tables, which the rounds consume,

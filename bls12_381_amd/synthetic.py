@@ -71,3 +71,24 @@ def dot_mod_r(a_bytes, b_bytes):
         a = to_ints(a_bytes[lo:lo + step]); b = to_ints(b_bytes[lo:lo + step])
         tot += sum(x * y for x, y in zip(a, b))
     return tot % R_ORDER
+
+
+def poseidon_test_params(t, r_full, r_partial, seed=SEED):
+    """TEST parameters for a Poseidon instance of width t -- NOT the parameters of any standard or deployed instance, and not vetted
+    for security.  Returns (constants, mds) as Python ints in [0, r): (r_full + r_partial) rows of t seeded round constants, and the
+    t x t Cauchy matrix 1 / (x_i + y_j) over seeded pairwise distinct x_0 .. x_(t-1), y_0 .. y_(t-1) with no x_i + y_j = 0 (every
+    square submatrix of a Cauchy matrix is regular, so the sparse form of the partial rounds exists)."""
+    need = (r_full + r_partial) * t
+    vals = to_ints(scalars(need + 4 * t + 16, (seed ^ (t << 32) ^ (r_full << 40) ^ (r_partial << 48)) & 0xFFFFFFFFFFFFFFFF))
+    constants = [vals[r * t:(r + 1) * t] for r in range(r_full + r_partial)]
+    xs, ys = [], []
+    for v in vals[need:]:
+        if len(xs) < t:
+            if v not in xs:
+                xs.append(v)
+        elif len(ys) < t:
+            if v not in ys and all((x + v) % R_ORDER for x in xs):
+                ys.append(v)
+    assert len(xs) == t and len(ys) == t
+    mds = [[pow((x + y) % R_ORDER, R_ORDER - 2, R_ORDER) for y in ys] for x in xs]
+    return constants, mds

@@ -415,6 +415,60 @@ inline std::vector<FrLimbs> fr_spmv(const FrMatrix& m, const std::vector<FrLimbs
   check(blsgpu_fr_spmv(Context::instance().handle(), m.handle(), x[0].data(), k, out[0].data()), "fr_spmv");
   return out;
 }
+// A Poseidon instance over Fr resident on the device (blsgpu_fr_poseidon): width t, r_full full and r_partial partial rounds, round
+// constants (r_full + r_partial) x t and the t x t matrix (row-major) as canonical Montgomery limbs.  THE PARAMETERS ARE THE CALLER'S: the
+// library ships no standard set.  Validated and planned once; Form::Auto takes the sparse partial rounds when they can be derived.
+// permute: n states of t scalars end to end; hash_many: n preimages of t - 1 scalars, the digest is element 1 of the permutation of
+// (tag, x_1 .. x_(t-1)); merkle: k trees of (t-1)^height leaves each, tree after tree -> the k roots, and every inner level (level 1
+// first, the roots last) in *nodes when it is given.
+class FrPoseidon {
+ public:
+  enum class Form { Auto = BLSGPU_FR_POSEIDON_AUTO, Dense = BLSGPU_FR_POSEIDON_DENSE, Sparse = BLSGPU_FR_POSEIDON_SPARSE };
+  FrPoseidon(int t, int r_full, int r_partial, const std::vector<FrLimbs>& round_constants, const std::vector<FrLimbs>& mds, Form form = Form::Auto) {
+    if (t < 1 || r_full < 0 || r_partial < 0 || round_constants.size() != (size_t)(r_full + r_partial) * t || mds.size() != (size_t)t * t)
+      throw std::invalid_argument("FrPoseidon: (r_full + r_partial) * t round constants and t * t matrix entries");
+    check(blsgpu_fr_poseidon_create(Context::instance().handle(), t, r_full, r_partial, round_constants.data()->data(), mds.data()->data(), (int)form, &p_), "fr_poseidon_create");
+  }
+  ~FrPoseidon() { blsgpu_fr_poseidon_free(p_); }
+  FrPoseidon(const FrPoseidon&) = delete;
+  FrPoseidon& operator=(const FrPoseidon&) = delete;
+  FrPoseidon(FrPoseidon&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  int width() const { return blsgpu_fr_poseidon_width(p_); }
+  int rounds_full() const { return blsgpu_fr_poseidon_rounds_full(p_); }
+  int rounds_partial() const { return blsgpu_fr_poseidon_rounds_partial(p_); }
+  Form form() const { return (Form)blsgpu_fr_poseidon_form(p_); }
+  size_t products_per_permutation() const { return blsgpu_fr_poseidon_products(p_); }
+  const blsgpu_fr_poseidon* handle() const { return p_; }
+  std::vector<FrLimbs> permute(const std::vector<FrLimbs>& states) const {
+    if (states.size() % (size_t)width()) throw std::invalid_argument("FrPoseidon::permute: n states of t scalars");
+    std::vector<FrLimbs> out(states.size());
+    if (out.empty()) return out;
+    check(blsgpu_fr_poseidon_permute(Context::instance().handle(), p_, states[0].data(), states.size() / (size_t)width(), out[0].data()), "fr_poseidon_permute");
+    return out;
+  }
+  std::vector<FrLimbs> hash_many(const FrLimbs& tag, const std::vector<FrLimbs>& inputs) const {
+    const size_t a = (size_t)width() - 1;
+    if (inputs.size() % a) throw std::invalid_argument("FrPoseidon::hash_many: n preimages of t - 1 scalars");
+    std::vector<FrLimbs> out(inputs.size() / a);
+    if (out.empty()) return out;
+    check(blsgpu_fr_poseidon_hash_many(Context::instance().handle(), p_, tag.data(), inputs[0].data(), out.size(), out[0].data()), "fr_poseidon_hash_many");
+    return out;
+  }
+  std::vector<FrLimbs> merkle(const FrLimbs& tag, const std::vector<FrLimbs>& leaves, int height, size_t k, std::vector<FrLimbs>* nodes = nullptr) const {
+    const size_t a = (size_t)width() - 1;
+    size_t per = 1;
+    for (int i = 0; i < height; i++) per *= a;
+    if (height < 0 || leaves.size() != k * per) throw std::invalid_argument("FrPoseidon::merkle: k trees of (t-1)^height leaves");
+    std::vector<FrLimbs> roots(k);
+    if (!k) return roots;
+    if (nodes) nodes->assign(a == 1 ? k * (size_t)height : k * ((per - 1) / (a - 1)), FrLimbs{});
+    check(blsgpu_fr_poseidon_merkle(Context::instance().handle(), p_, tag.data(), leaves[0].data(), height, k, nodes && !nodes->empty() ? (*nodes)[0].data() : nullptr, roots[0].data()),
+          "fr_poseidon_merkle");
+    return roots;
+  }
+ private:
+  blsgpu_fr_poseidon* p_ = nullptr;
+};
 // Multilinear tables (include/bls12_381_hip.h): k tables of t.size() / k = 2^m scalars each, laid end to end; entry i is the value at the
 // point whose coordinate x_b is bit b of i.  fr_mle_fold binds the top variable at r (k x 2^(m-1) out), fr_eq_table is
 // eq(point)[i] = prod_b (bit b of i ? point[b] : 1 - point[b]), fr_mle_eval gives f_j(point) with point[b] the value of x_b.

@@ -654,6 +654,56 @@ int blsgpu_fr_sumcheck_degree(const blsgpu_fr_sumcheck* s);
 int blsgpu_fr_sumcheck_round(blsgpu_ctx* ctx, blsgpu_fr_sumcheck* s, const uint64_t* r_prev, uint64_t* evals);
 int blsgpu_fr_sumcheck_finish(blsgpu_ctx* ctx, blsgpu_fr_sumcheck* s, const uint64_t* r_last, uint64_t* values);
 void blsgpu_fr_sumcheck_free(blsgpu_fr_sumcheck* s);
+/* Poseidon over Fr: permutations, fixed-length hashes and Merkle trees, the field-native hash a prover commits to tables with and derives
+ * challenges from -- with the data where the transforms and sumcheck rounds left it.  An instance is width t, R_F full rounds (even: half
+ * before and half after the partial ones), R_P partial rounds, round constants C[r][i] (r < R_F + R_P, i < t) and a t x t matrix M:
+ *   for r = 0 .. R_F + R_P - 1:   s[i] += C[r][i];   s[i] = s[i]^5 (a full round: every i; a partial round: i = 0);   s'[i] = sum_j M[i][j] s[j]
+ * built on `Scalar`'s mul / add (scalar.rs:452-503, :435-449; the reference crate has no hash over Scalar).  x^5 permutes Fr:
+ * gcd(5, r - 1) = 1.  Fr values are unique, so the result is limb-identical to this definition whatever route the kernels take.
+ * THE LIBRARY SHIPS NO STANDARD PARAMETER SET: the constants of a published instance come out of the Poseidon paper's Grain LFSR, which
+ * cannot be pinned against published vectors here, and unverifiable constants have no place in a bit-exact library.  The caller passes the
+ * constants and the matrix of the instance it uses (security is the instance's: the round numbers and M are not judged here).
+ * create: the handle is resident like blsgpu_fr_matrix -- parameters validated and planned once, the constant image uploaded once (a setup
+ * call: it synchronises).  t in {2, 3, 4, 5, 9, 12}, r_full even in [2, 16], r_partial in [0, 128]; round_constants holds
+ * (r_full + r_partial) * t and mds t * t (row-major) scalars as four canonical Montgomery limbs each, in HOST memory.  form AUTO derives
+ * the sparse form of the partial rounds (2t + 2 products each instead of 3 + t^2, and (t-1)^2 once) when the lower-right (t-1) x (t-1)
+ * block of M is regular and falls back to the dense rounds otherwise; form DENSE asks for the dense rounds; blsgpu_fr_poseidon_form
+ * reports DENSE or SPARSE.  Anything else is BLSGPU_ERR_ARG, *out stays NULL and blsgpu_last_error names the argument or the first
+ * constant that is not below r.  blsgpu_fr_poseidon_free follows the rules of blsgpu_fr_matrix_free (it waits for the device; NULL is
+ * allowed).
+ *   permute    n states of t scalars laid end to end; out == states exactly is the in-place form, any other overlap is refused
+ *   hash_many  n preimages of t - 1 scalars; the state is (tag, x_1 .. x_(t-1)) and the digest is element 1 after the permutation; out
+ *              holds n scalars and must not overlap the inputs.  tag is four canonical Montgomery limbs in HOST memory in both forms (a
+ *              parameter, like `coset`): a domain separator, a level or a round number
+ *   merkle     arity a = t - 1: k trees of a^height leaves each, tree after tree; a node is the hash_many digest of its a children under
+ *              tag.  roots holds k scalars (required).  nodes (may be NULL) holds every inner level, level-major: level 1 (k a^(height-1)
+ *              nodes, tree-major) first, level `height` (the k roots) last, k (a^height - 1) / (a - 1) scalars (k * height for a = 1);
+ *              with NULL the inner levels live in the context's scratch.  height 0 copies the leaves to roots.  The leaves are never
+ *              written; every overlap between leaves, nodes and roots is refused.
+ * n * t, k * a^height and the node count are at most 2^28 (64-bit overflow checked); height in [0, 28]; n == 0 and k == 0 are no-ops.
+ * Device pointers must be 16-byte aligned.  Canonical inputs are a precondition (not validated); outputs are canonical and limb-identical
+ * from run to run (no atomics, no workgroup waits for another one).  One launch per permute / hash_many; merkle is one launch per level
+ * (a level of all k trees is a hash_many over the level below).  The device forms are asynchronous
+ * on the context's stream and never synchronise; their scratch is the context's own and is not shared with pipelined *_msm_device calls
+ * in flight.  BLSGPU_ERR_ARG (nothing staged or launched): a NULL pointer with work to do, a handle of another device, a tag that is not
+ * below r, a size out of range, a misaligned device pointer, an overlap. */
+typedef struct blsgpu_fr_poseidon blsgpu_fr_poseidon;
+#define BLSGPU_FR_POSEIDON_AUTO   0   /* sparse partial rounds when derivable, else dense */
+#define BLSGPU_FR_POSEIDON_DENSE  1   /* the textbook partial rounds */
+#define BLSGPU_FR_POSEIDON_SPARSE 2   /* reported by blsgpu_fr_poseidon_form only */
+int blsgpu_fr_poseidon_create(blsgpu_ctx* ctx, int t, int r_full, int r_partial, const uint64_t* round_constants, const uint64_t* mds, int form, blsgpu_fr_poseidon** out);
+int blsgpu_fr_poseidon_width(const blsgpu_fr_poseidon* p);
+int blsgpu_fr_poseidon_rounds_full(const blsgpu_fr_poseidon* p);
+int blsgpu_fr_poseidon_rounds_partial(const blsgpu_fr_poseidon* p);
+int blsgpu_fr_poseidon_form(const blsgpu_fr_poseidon* p);
+size_t blsgpu_fr_poseidon_products(const blsgpu_fr_poseidon* p);      /* field products of one permutation in the form the handle uses */
+void blsgpu_fr_poseidon_free(blsgpu_fr_poseidon* p);
+int blsgpu_fr_poseidon_permute(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t* states, size_t n, uint64_t* out);
+int blsgpu_fr_poseidon_permute_device(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const void* d_states, size_t n, void* d_out);
+int blsgpu_fr_poseidon_hash_many(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const uint64_t* inputs, size_t n, uint64_t* out);
+int blsgpu_fr_poseidon_hash_many_device(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const void* d_inputs, size_t n, void* d_out);
+int blsgpu_fr_poseidon_merkle(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const uint64_t* leaves, int height, size_t k, uint64_t* nodes, uint64_t* roots);
+int blsgpu_fr_poseidon_merkle_device(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const void* d_leaves, int height, size_t k, void* d_nodes, void* d_roots);
 /* The same radix-2 transform over GROUP elements: k vectors of 2^log_n G1 (G2) points each, laid end to end, in place, natural order in
  * and out:
  *   forward  Y[m] = sum_j [w^(jm)] P[j],   inverse  P[j] = [n^-1] sum_m [w^(-jm)] Y[m],   w as for blsgpu_fr_ntt

@@ -365,6 +365,72 @@ impl<'a> FrSumcheck<'a> {
 impl<'a> Drop for FrSumcheck<'a> {
     fn drop(&mut self) { unsafe { ffi::blsgpu_fr_sumcheck_free(self.handle) } }
 }
+/// Which partial rounds a `FrPoseidon` runs: `Auto` (a request) derives the sparse form when the matrix allows it.
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum FrPoseidonForm { Auto = 0, Dense = 1, Sparse = 2 }
+/// A Poseidon instance over `Scalar` resident on the GPU (`blsgpu_fr_poseidon`): width `t`, `r_full` full and `r_partial` partial rounds,
+/// `(r_full + r_partial) * t` round constants and the `t * t` matrix (row-major).  THE PARAMETERS ARE THE CALLER'S: the library ships no
+/// standard set.  Validated and planned once.  The FFI layer sees the handle as an untyped pointer; this is its type.
+pub struct FrPoseidon<'a> { gpu: &'a Gpu, handle: *mut c_void }
+impl<'a> FrPoseidon<'a> {
+    pub fn new(gpu: &'a Gpu, t: usize, r_full: usize, r_partial: usize, round_constants: &[Scalar], mds: &[Scalar], form: FrPoseidonForm) -> Result<FrPoseidon<'a>, Error> {
+        assert!(round_constants.len() == (r_full + r_partial) * t && mds.len() == t * t);
+        let (rc, mm) = (scalar_limbs(gpu, round_constants)?, scalar_limbs(gpu, mds)?);
+        let mut handle: *mut c_void = std::ptr::null_mut();
+        check(unsafe {
+            ffi::blsgpu_fr_poseidon_create(gpu.ctx, t as c_int, r_full as c_int, r_partial as c_int, rc.as_ptr(), mm.as_ptr(), form as c_int,
+                                           &mut handle as *mut *mut c_void as *mut c_void)
+        })?;
+        Ok(FrPoseidon { gpu, handle })
+    }
+    pub fn width(&self) -> usize { unsafe { ffi::blsgpu_fr_poseidon_width(self.handle as *const c_void) as usize } }
+    pub fn rounds_full(&self) -> usize { unsafe { ffi::blsgpu_fr_poseidon_rounds_full(self.handle as *const c_void) as usize } }
+    pub fn rounds_partial(&self) -> usize { unsafe { ffi::blsgpu_fr_poseidon_rounds_partial(self.handle as *const c_void) as usize } }
+    /// `Dense` or `Sparse`: what the handle runs.
+    pub fn form(&self) -> FrPoseidonForm {
+        if unsafe { ffi::blsgpu_fr_poseidon_form(self.handle as *const c_void) } == 2 { FrPoseidonForm::Sparse } else { FrPoseidonForm::Dense }
+    }
+    pub fn products_per_permutation(&self) -> usize { unsafe { ffi::blsgpu_fr_poseidon_products(self.handle as *const c_void) } }
+    /// `states.len() / t` states of `t` scalars laid end to end -> the permuted states.
+    pub fn permute(&self, states: &[Scalar]) -> Result<Vec<Scalar>, Error> {
+        assert!(states.len() % self.width() == 0);
+        if states.is_empty() { return Ok(Vec::new()); }
+        let input = scalar_limbs(self.gpu, states)?;
+        let mut out = vec![0u64; input.len()];
+        check(unsafe { ffi::blsgpu_fr_poseidon_permute(self.gpu.ctx, self.handle as *const c_void, input.as_ptr(), states.len() / self.width(), out.as_mut_ptr()) })?;
+        limbs_scalars(self.gpu, &out)
+    }
+    /// Preimages of `t - 1` scalars -> one digest each: element 1 of the permutation of `(tag, x_1 .. x_(t-1))`.
+    pub fn hash_many(&self, tag: &Scalar, inputs: &[Scalar]) -> Result<Vec<Scalar>, Error> {
+        let a = self.width() - 1;
+        assert!(inputs.len() % a == 0);
+        if inputs.is_empty() { return Ok(Vec::new()); }
+        let (tg, input) = (scalar_limbs(self.gpu, std::slice::from_ref(tag))?, scalar_limbs(self.gpu, inputs)?);
+        let n = inputs.len() / a;
+        let mut out = vec![0u64; n * 4];
+        check(unsafe { ffi::blsgpu_fr_poseidon_hash_many(self.gpu.ctx, self.handle as *const c_void, tg.as_ptr(), input.as_ptr(), n, out.as_mut_ptr()) })?;
+        limbs_scalars(self.gpu, &out)
+    }
+    /// `k` trees of `(t-1)^height` leaves each, tree after tree -> `(roots, nodes)`: `nodes` holds every inner level, level 1 first and the
+    /// roots last.
+    pub fn merkle(&self, tag: &Scalar, leaves: &[Scalar], height: u32, k: usize) -> Result<(Vec<Scalar>, Vec<Scalar>), Error> {
+        let a = self.width() - 1;
+        let per = a.pow(height);
+        assert!(leaves.len() == k * per);
+        if k == 0 { return Ok((Vec::new(), Vec::new())); }
+        let count = if a == 1 { k * height as usize } else { k * ((per - 1) / (a - 1)) };
+        let (tg, input) = (scalar_limbs(self.gpu, std::slice::from_ref(tag))?, scalar_limbs(self.gpu, leaves)?);
+        let (mut roots, mut nodes) = (vec![0u64; k * 4], vec![0u64; count * 4]);
+        check(unsafe {
+            ffi::blsgpu_fr_poseidon_merkle(self.gpu.ctx, self.handle as *const c_void, tg.as_ptr(), input.as_ptr(), height as c_int, k,
+                                           if count > 0 { nodes.as_mut_ptr() } else { std::ptr::null_mut() }, roots.as_mut_ptr())
+        })?;
+        Ok((limbs_scalars(self.gpu, &roots)?, limbs_scalars(self.gpu, &nodes)?))
+    }
+}
+impl<'a> Drop for FrPoseidon<'a> {
+    fn drop(&mut self) { unsafe { ffi::blsgpu_fr_poseidon_free(self.handle) } }
+}
 fn split72(flat: Vec<u64>) -> Vec<GtLimbs> {
     flat.chunks_exact(72).map(|c| { let mut a = [0u64; 72]; a.copy_from_slice(c); GtLimbs(a) }).collect()
 }
