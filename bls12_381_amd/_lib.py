@@ -72,6 +72,10 @@ SIGNATURES = {
     "blsgpu_fr_scan_many_device": (c_int, [c_vp, c_int, c_int, c_vp, c_sz, c_sz, c_vp, c_vp]),
     "blsgpu_fr_batch_invert": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
     "blsgpu_fr_batch_invert_device": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_grand_product": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_grand_product_device": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_frac_sum": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp]),
+    "blsgpu_fr_frac_sum_device": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_sz, c_vp, c_vp]),
     "blsgpu_fr_bary_eval_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_int, c_vp]),
     "blsgpu_fr_bary_eval_many_device": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_int, c_vp]),
     "blsgpu_fr_bary_open_many": (c_int, [c_vp, c_vp, c_int, c_sz, c_vp, c_int, c_vp, c_vp]),

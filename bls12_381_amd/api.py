@@ -63,6 +63,7 @@ def _flags(f, n):
 
 
 FR_SCAN_SUM, FR_SCAN_PRODUCT, FR_SCAN_HORNER = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_SCAN_*
+FR_FRAC_MAX_COLS, FR_FRAC_TILE = 8, 1024                   # include/bls12_381_hip.h: BLSGPU_FR_FRAC_*
 FR_ORDER_NATURAL, FR_ORDER_BITREV = 0, 1                    # include/bls12_381_hip.h: BLSGPU_FR_ORDER_*
 FR_POSEIDON_AUTO, FR_POSEIDON_DENSE, FR_POSEIDON_SPARSE = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_POSEIDON_*
 FR_GENERATOR = 7                          # scalar.rs:99-105 GENERATOR (`MULTIPLICATIVE_GENERATOR` :708): the usual coset shift
@@ -891,6 +892,72 @@ class Context:
 
     def fr_batch_invert_device(self, d_in, n, d_out, d_flags=None):
         check(self.lib.blsgpu_fr_batch_invert_device(self.h, d_in, n, d_out, d_flags), "fr_batch_invert_device")
+
+    @staticmethod
+    def _frac_set(what, name, s, shape=None):
+        """a column set as a contiguous (c, k, len, 4) u64 array (a (c, len, 4) array is k = 1); None stays None"""
+        if s is None:
+            return None
+        v = np.ascontiguousarray(np.array(s, dtype=np.uint64))
+        if v.ndim == 3:
+            v = v.reshape((v.shape[0], 1) + v.shape[1:])
+        if v.ndim != 4 or v.shape[3] != 4:
+            raise ValueError("%s: %s must be a (c, k, len, 4) or (c, len, 4) array" % (what, name))
+        if shape is not None and v.shape != shape:
+            raise ValueError("%s: %s has shape %s, expected %s" % (what, name, v.shape, shape))
+        return v
+
+    def fr_grand_product(self, num_a, num_b, den_a, den_b, beta, gamma, exclusive=False, return_flags=False):
+        """the accumulator column of a permutation argument in one call (include/bls12_381_hip.h): column sets of shape (c, k, len, 4) u64
+        Montgomery limbs ((c, len, 4) is k = 1), c in [1, 8]; num_b / den_b may be None (no beta term); beta, gamma: Python ints in
+        [0, r) or (4,) limb arrays.  f[i] = prod_j (num_a_j + beta num_b_j + gamma)[i] * inv0(prod_j (den_a_j + beta den_b_j + gamma)[i]),
+        out = the PRODUCT scan of f along each row (exclusive: out[v][0] = 1).  Returns a (k, len, 4) array ((len, 4) for k = 1 input);
+        return_flags also returns the (k, len) bytes that are 0 where a denominator factor was zero."""
+        what = "fr_grand_product"
+        one = np.ndim(num_a) == 3
+        na = self._frac_set(what, "num_a", num_a)
+        if na is None:
+            raise ValueError("fr_grand_product: num_a is required")
+        da = na if den_a is num_a else self._frac_set(what, "den_a", den_a, na.shape)
+        if da is None:
+            raise ValueError("fr_grand_product: den_a is required")
+        nb, db = self._frac_set(what, "num_b", num_b, na.shape), self._frac_set(what, "den_b", den_b, na.shape)
+        c, k, n = na.shape[:3]
+        out = np.zeros((k, n, 4), dtype=np.uint64)
+        flags = np.ones((k, n), dtype=np.uint8)
+        check(self.lib.blsgpu_fr_grand_product(self.h, 1 if exclusive else 0, c, _ptr(na), _ptr(nb), _ptr(da), _ptr(db), _ptr(_point_limbs([beta, gamma], 2)), n, k,
+                                               _ptr(out), _ptr(flags)), what)
+        if one:
+            out, flags = out[0], flags[0]
+        return (out, flags) if return_flags else out
+
+    def fr_grand_product_device(self, c, d_num_a, d_num_b, d_den_a, d_den_b, pitch, d_challenges, length, k, d_out, d_flags=None, exclusive=False):
+        """the same on column sets in device memory (table j of a set at + j * pitch scalars; d_num_b / d_den_b may be None),
+        d_challenges = (beta, gamma) in DEVICE memory, asynchronous on the context's stream"""
+        check(self.lib.blsgpu_fr_grand_product_device(self.h, 1 if exclusive else 0, c, d_num_a, d_num_b, d_den_a, d_den_b, pitch, d_challenges, length, k, d_out, d_flags),
+              "fr_grand_product_device")
+
+    def fr_frac_sum(self, mult, den_a, den_b, beta, gamma, exclusive=False, return_flags=False):
+        """the accumulator column of a log-derivative lookup argument in one call: f[i] = sum_j mult_j[i] * inv0(gamma + den_a_j[i] + beta
+        den_b_j[i]), out = the SUM scan of f along each row.  Shapes and challenges as fr_grand_product; mult None: every multiplicity
+        is 1 (signs belong in mult); den_b None: no beta term."""
+        what = "fr_frac_sum"
+        one = np.ndim(den_a) == 3
+        da = self._frac_set(what, "den_a", den_a)
+        if da is None:
+            raise ValueError("fr_frac_sum: den_a is required")
+        m, db = self._frac_set(what, "mult", mult, da.shape), self._frac_set(what, "den_b", den_b, da.shape)
+        c, k, n = da.shape[:3]
+        out = np.zeros((k, n, 4), dtype=np.uint64)
+        flags = np.ones((k, n), dtype=np.uint8)
+        check(self.lib.blsgpu_fr_frac_sum(self.h, 1 if exclusive else 0, c, _ptr(m), _ptr(da), _ptr(db), _ptr(_point_limbs([beta, gamma], 2)), n, k, _ptr(out), _ptr(flags)), what)
+        if one:
+            out, flags = out[0], flags[0]
+        return (out, flags) if return_flags else out
+
+    def fr_frac_sum_device(self, c, d_mult, d_den_a, d_den_b, pitch, d_challenges, length, k, d_out, d_flags=None, exclusive=False):
+        """the same on column sets in device memory (d_mult / d_den_b may be None), asynchronous on the context's stream"""
+        check(self.lib.blsgpu_fr_frac_sum_device(self.h, 1 if exclusive else 0, c, d_mult, d_den_a, d_den_b, pitch, d_challenges, length, k, d_out, d_flags), "fr_frac_sum_device")
 
     def _fr_bary_args(self, what, evals, points):
         v = np.ascontiguousarray(np.array(evals, dtype=np.uint64))

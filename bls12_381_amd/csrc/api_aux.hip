@@ -4,6 +4,7 @@
 #include "fr.hip.h"
 #include "fr_plan.h"
 #include "fr_scan.hip.h"
+#include "fr_frac.hip.h"
 #include "fr_bary.hip.h"
 #include "fr_spmv.hip.h"
 #include "fr_mle.hip.h"
@@ -574,11 +575,126 @@ extern "C" int blsgpu_fr_batch_invert(blsgpu_ctx* c, const uint64_t* values, siz
   return h.finish(blsgpu_fr_batch_invert_device(c, di, n, o, f));
 }
 
-// ---- polynomials in evaluation form: value at a point and the opening's quotient (fr_bary.hip.h; fr_bary_plan.h decides the launches) ------
+// two byte ranges share a byte (the fraction scans and the openings refuse such outputs)
 static bool frb_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
   return x < y + b_bytes && y < x + a_bytes;
 }
+// ---- fraction scans: permutation grand products and logUp sums (fr_frac.hip.h; fr_frac_plan.h decides the launches) -----------------------
+// every argument check of the four forms, before anything is staged, reserved or launched.  xa / xb: num_a / num_b (grand product) or
+// mult / nothing (fraction sum).  *work: there is something to do.
+static int fr_frac_check(blsgpu_ctx* c, int op, int exclusive, int cols, const void* xa, const void* xb, const void* da, const void* db, size_t pitch, const void* chal, size_t len,
+                         size_t k, const void* out, const void* flags, bool device, bool* work) {
+  *work = false;
+  if (!c) return bad("fr_frac: NULL context");
+  if (cols < 1 || cols > FRF_MAX_COLS) return bad("fr_frac: c must be in [1, 8]");
+  if (exclusive != 0 && exclusive != 1) return bad("fr_frac: exclusive must be 0 or 1");
+  if (len && k > FRS_MAX_TOTAL / len) return bad("fr_frac: k * len must not exceed 2^28");
+  if (!len || !k) return BLSGPU_OK;
+  const size_t total = len * k;
+  if (pitch < total) return bad("fr_frac: pitch must be at least k * len");
+  if (pitch > FRS_MAX_TOTAL || (size_t)(cols - 1) * pitch + total > FRS_MAX_TOTAL) return bad("fr_frac: (c - 1) * pitch + k * len must not exceed 2^28");
+  if ((op == FRF_GRAND_PRODUCT && !xa) || !da || !chal || !out) return bad("fr_frac: NULL pointer (num_a, den_a, challenges and out are required)");
+  if (device && (((uintptr_t)xa | (uintptr_t)xb | (uintptr_t)da | (uintptr_t)db | (uintptr_t)chal | (uintptr_t)out) & 15)) return bad("fr_frac: device pointers must be 16-byte aligned");
+  const size_t set = ((size_t)(cols - 1) * pitch + total) * 32, data = total * 32;
+  const void* ins[5] = {xa, xb, da, db, chal};
+  for (int i = 0; i < 5; i++) {
+    if (!ins[i]) continue;
+    const size_t bytes = i == 4 ? 64 : set;
+    if (frb_overlap(out, data, ins[i], bytes)) return bad("fr_frac: out overlaps an input (there is no in-place form)");
+    if (flags && frb_overlap(flags, total, ins[i], bytes)) return bad("fr_frac: nonzero_flags overlaps an input");
+  }
+  if (flags && frb_overlap(flags, total, out, data)) return bad("fr_frac: nonzero_flags overlaps out");
+  *work = true;
+  return BLSGPU_OK;
+}
+template <int OP>
+static int fr_frac_launch(blsgpu_ctx* c, const FrFracPlan& plan, int exclusive, int cols, const u32* xa, const u32* xb, const u32* da, const u32* db, size_t pitch, const u32* chal,
+                          size_t len, size_t k, u32* out, uint8_t* flags) {
+  constexpr int SOP = frf_scan_op(OP);
+  hipStream_t st = c->stream;
+  const unsigned chunk = (unsigned)plan.shape.chunk;
+  u32* buf[4] = {c->frs_agg[0].as<u32>(), c->frs_agg[1].as<u32>(), c->frs_carry[0].as<u32>(), c->frs_carry[1].as<u32>()};
+  for (int i = 0; i < plan.n_steps; i++) {
+    const FrScanStep& s = plan.step[i];
+    u32* src = s.src >= 0 ? buf[s.src] : nullptr;
+    u32* dst = s.dst >= 0 ? buf[s.dst] : nullptr;
+    u32* carry = s.carry >= 0 ? buf[s.carry] : nullptr;
+    switch (s.kernel) {
+      case FRF_K_FRONT:
+        KLAUNCH(k_frf_front<OP>, dim3(s.grid), dim3(s.block), s.lds, st, s.src, exclusive, cols, xa, xb, da, db, pitch, chal, len, k, chunk, out, flags, dst, c->frs_lane.as<u32>());
+        break;
+      case FRS_K_SCAN:
+        KLAUNCH(k_frs_tile<SOP>, dim3(s.grid), dim3(s.block), s.lds, st, s.kernel, exclusive, (const u32*)out, out, (const u32*)nullptr, len, k, chunk, dst, (const u32*)carry,
+                c->frs_lane.as<u32>());
+        break;
+      default:
+        KLAUNCH(k_frs_agg<SOP>, dim3(s.grid), dim3(s.block), s.lds, st, s.kernel, (const u32*)src, s.items, chunk, s.kernel == FRS_K_AGG_REDUCE ? dst : (u32*)nullptr,
+                (const u32*)carry, s.kernel == FRS_K_AGG_SCAN ? dst : (u32*)nullptr);
+        break;
+    }
+  }
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+static int fr_frac_device(blsgpu_ctx* c, int op, int exclusive, int cols, const void* xa, const void* xb, const void* da, const void* db, size_t pitch, const void* chal, size_t len,
+                          size_t k, void* out, void* flags) {
+  bool work;
+  if (int rc = fr_frac_check(c, op, exclusive, cols, xa, xb, da, db, pitch, chal, len, k, out, flags, true, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const FrFracPlan plan = fr_frac_plan(op, cols, len, k, pitch);
+  if (plan.n_steps < 0) return bad("fr_frac: a size is out of range");
+  const size_t rec = (size_t)frs_rec_words(frf_scan_op(op)) * 4;
+  if (c->frs_agg[0].reserve(plan.recs[FRS_BUF_AGG0] * rec) || c->frs_agg[1].reserve(plan.recs[FRS_BUF_AGG1] * rec) ||
+      c->frs_carry[0].reserve(plan.recs[FRS_BUF_CARRY0] * 32) || c->frs_carry[1].reserve(plan.recs[FRS_BUF_CARRY1] * 32) ||
+      c->frs_lane.reserve(plan.recs[FRS_BUF_LANE] * rec)) {
+    g_err = "hipMalloc(fr frac scratch) failed"; return BLSGPU_ERR_HIP;
+  }
+  if (op == FRF_GRAND_PRODUCT)
+    return fr_frac_launch<FRF_GRAND_PRODUCT>(c, plan, exclusive, cols, (const u32*)xa, (const u32*)xb, (const u32*)da, (const u32*)db, pitch, (const u32*)chal, len, k, (u32*)out, (uint8_t*)flags);
+  return fr_frac_launch<FRF_FRAC_SUM>(c, plan, exclusive, cols, (const u32*)xa, (const u32*)nullptr, (const u32*)da, (const u32*)db, pitch, (const u32*)chal, len, k, (u32*)out, (uint8_t*)flags);
+}
+// packed sets (pitch = k * len).  A set passed twice (num_a == den_a) is staged once, so the device sees the alias too.
+static int fr_frac_host(blsgpu_ctx* c, int op, int exclusive, int cols, const uint64_t* xa, const uint64_t* xb, const uint64_t* da, const uint64_t* db, const uint64_t* chal, size_t len,
+                        size_t k, uint64_t* out, uint8_t* flags) {
+  bool work;
+  const size_t pitch = len && k <= FRS_MAX_TOTAL / len ? len * k : 0;        // an overflowing product is refused by the check before pitch is looked at
+  if (int rc = fr_frac_check(c, op, exclusive, cols, xa, xb, da, db, pitch, chal, len, k, out, flags, false, &work)) return rc;
+  if (!work) return BLSGPU_OK;
+  HostCall h(c);
+  const size_t set = (size_t)cols * pitch * 32;
+  const void* src[4] = {xa, xb, da, db};
+  DevBuf* stage[4] = {&c->io_a, &c->io_b, &c->io_e, &c->io_f};
+  void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 4; i++) {
+    for (int j = 0; j < i && !dev[i]; j++) if (src[i] && src[j] == src[i]) dev[i] = dev[j];
+    if (!dev[i]) dev[i] = h.in(*stage[i], src[i], set);
+  }
+  void* dc = h.in(c->flags_b, chal, 64);
+  void* o = h.out(c->io_out, out, pitch * 32);
+  void* f = flags ? h.out(c->flags_a, flags, pitch) : nullptr;
+  if (h.rc) return h.rc;
+  return h.finish(fr_frac_device(c, op, exclusive, cols, dev[0], dev[1], dev[2], dev[3], pitch, dc, len, k, o, f));
+}
+extern "C" int blsgpu_fr_grand_product_device(blsgpu_ctx* c, int exclusive, int cols, const void* d_num_a, const void* d_num_b, const void* d_den_a, const void* d_den_b, size_t pitch,
+                                              const void* d_challenges, size_t len, size_t k, void* d_out, void* d_nonzero_flags) { CTX_CLAIM(c);
+  return fr_frac_device(c, FRF_GRAND_PRODUCT, exclusive, cols, d_num_a, d_num_b, d_den_a, d_den_b, pitch, d_challenges, len, k, d_out, d_nonzero_flags);
+}
+extern "C" int blsgpu_fr_frac_sum_device(blsgpu_ctx* c, int exclusive, int cols, const void* d_mult, const void* d_den_a, const void* d_den_b, size_t pitch, const void* d_challenges,
+                                         size_t len, size_t k, void* d_out, void* d_nonzero_flags) { CTX_CLAIM(c);
+  return fr_frac_device(c, FRF_FRAC_SUM, exclusive, cols, d_mult, nullptr, d_den_a, d_den_b, pitch, d_challenges, len, k, d_out, d_nonzero_flags);
+}
+extern "C" int blsgpu_fr_grand_product(blsgpu_ctx* c, int exclusive, int cols, const uint64_t* num_a, const uint64_t* num_b, const uint64_t* den_a, const uint64_t* den_b,
+                                       const uint64_t* challenges, size_t len, size_t k, uint64_t* out, uint8_t* nonzero_flags) { CTX_CLAIM(c);
+  return fr_frac_host(c, FRF_GRAND_PRODUCT, exclusive, cols, num_a, num_b, den_a, den_b, challenges, len, k, out, nonzero_flags);
+}
+extern "C" int blsgpu_fr_frac_sum(blsgpu_ctx* c, int exclusive, int cols, const uint64_t* mult, const uint64_t* den_a, const uint64_t* den_b, const uint64_t* challenges, size_t len,
+                                  size_t k, uint64_t* out, uint8_t* nonzero_flags) { CTX_CLAIM(c);
+  return fr_frac_host(c, FRF_FRAC_SUM, exclusive, cols, mult, nullptr, den_a, den_b, challenges, len, k, out, nonzero_flags);
+}
+
+// ---- polynomials in evaluation form: value at a point and the opening's quotient (fr_bary.hip.h; fr_bary_plan.h decides the launches) ------
 // every argument check of the four forms, before anything is staged, reserved or launched.  *work: there is something to do.
 static int fr_bary_check(blsgpu_ctx* c, bool open, const void* evals, int log_n, size_t k, const void* points, int order, const void* y, const void* q, bool device, bool* work) {
   *work = false;

@@ -153,19 +153,12 @@ template <bool REV> DEV void frs_tile_store(u32* out, size_t base, unsigned cnt,
 // bound by their products and not by HBM, have to spare.
 // `in` and `out` may be the same buffer: a workgroup has its whole tile in LDS before its first store and touches no other tile.
 // points: k scalars, the point of physical row v at points + 8 v (HORNER only).
+// The tile's elements are in LDS (frs_lds_addr; every lane sees its own chunk): the part of k_frs_tile between its load and its store,
+// shared with the fused front of fr_frac.hip.h, whose tile is built in LDS instead of loaded.  SINGLE and SCAN leave the scanned tile in
+// LDS (the caller stores it after a barrier), REDUCE leaves the elements as they were and writes the records.
 template <int OP>
-__global__ void __launch_bounds__(FRS_BLOCK, 2) k_frs_tile(int mode, int exclusive, const u32* in, u32* out, const u32* __restrict__ points, size_t len, size_t k, unsigned chunk,
-                                                           u32* __restrict__ agg_out, const u32* __restrict__ carry_in, u32* lane_rec) {
-  BLS_DYN_LDS(lds);
-  constexpr bool REV = OP == FRS_HORNER;
-  const size_t total = len * k;
-  const unsigned tile = blockDim.x * chunk;
-  const size_t base = (size_t)blockIdx.x * tile;
-  if (base >= total) return;
-  const unsigned cnt = total - base < (size_t)tile ? (unsigned)(total - base) : tile;
-  u32* wrec = lds + blockDim.x * (chunk * 8 + 4);
-  frs_tile_load<REV>(in, base, cnt, total, chunk, lds);
-  __syncthreads();
+DEV void frs_tile_body(int mode, int exclusive, u32* lds, u32* wrec, const u32* __restrict__ points, size_t len, size_t k, unsigned chunk, size_t base, unsigned cnt,
+                       u32* __restrict__ agg_out, const u32* __restrict__ carry_in, u32* lane_rec) {
   const unsigned s0 = threadIdx.x * chunk;
   const unsigned mine = s0 < cnt ? (cnt - s0 < chunk ? cnt - s0 : chunk) : 0u;
   const size_t row0 = mine ? (base + s0) / len : 0;                // logical row of the lane's first element, and its position in it
@@ -219,6 +212,22 @@ __global__ void __launch_bounds__(FRS_BLOCK, 2) k_frs_tile(int mode, int exclusi
       if (++q == len) { q = 0; row++; }
     }
   }
+}
+template <int OP>
+__global__ void __launch_bounds__(FRS_BLOCK, 2) k_frs_tile(int mode, int exclusive, const u32* in, u32* out, const u32* __restrict__ points, size_t len, size_t k, unsigned chunk,
+                                                           u32* __restrict__ agg_out, const u32* __restrict__ carry_in, u32* lane_rec) {
+  BLS_DYN_LDS(lds);
+  constexpr bool REV = OP == FRS_HORNER;
+  const size_t total = len * k;
+  const unsigned tile = blockDim.x * chunk;
+  const size_t base = (size_t)blockIdx.x * tile;
+  if (base >= total) return;
+  const unsigned cnt = total - base < (size_t)tile ? (unsigned)(total - base) : tile;
+  u32* wrec = lds + blockDim.x * (chunk * 8 + 4);
+  frs_tile_load<REV>(in, base, cnt, total, chunk, lds);
+  __syncthreads();
+  frs_tile_body<OP>(mode, exclusive, lds, wrec, points, len, k, chunk, base, cnt, agg_out, carry_in, lane_rec);
+  if (mode == FRS_K_REDUCE) return;
   __syncthreads();
   frs_tile_store<REV>(out, base, cnt, total, chunk, lds);
 }

@@ -92,3 +92,54 @@ def poseidon_test_params(t, r_full, r_partial, seed=SEED):
     assert len(xs) == t and len(ys) == t
     mds = [[pow((x + y) % R_ORDER, R_ORDER - 2, R_ORDER) for y in ys] for x in xs]
     return constants, mds
+
+
+def column_set(c, k, n, seed=SEED):
+    """a seeded column set for the fraction scans: c tables of k rows of n scalars, as nested lists of Python ints in [0, r)"""
+    vals = to_ints(scalars(c * k * n, (seed ^ (c << 32) ^ (k << 40) ^ (n << 20)) & 0xFFFFFFFFFFFFFFFF))
+    return [[vals[(j * k + v) * n:(j * k + v + 1) * n] for v in range(k)] for j in range(c)]
+
+
+def permutation_with_copy_cycles(c, log_n, seed=SEED, max_cycle=8):
+    """a seeded copy-constraint instance for a permutation argument over c wire columns of n = 2^log_n rows: the c n positions are cut
+    into cycles of 1 .. max_cycle positions (seeded, scattered over rows and columns), sigma maps a position to the next one of its
+    cycle, and every wire value is constant on its cycle.  Returns (wires, ids, sigmas), each c lists of n Python ints: the labels are
+    id_j[i] = 7^j w^i with w = 7^((r - 1) / n) (7 generates Fr*, so the cosets 7^j <w> are disjoint for j < 2^32 / n) and
+    sigma_j[i] = the id label of sigma(j, i).  With any beta, gamma: prod_{j,i} (w + beta id + gamma) / (w + beta sigma + gamma) = 1."""
+    n = 1 << log_n
+    total = c * n
+    words = splitmix64((seed ^ (c << 32) ^ (log_n << 40)) & 0xFFFFFFFFFFFFFFFF, 0, 2 * total)
+    order = np.argsort(words[:total], kind="stable")                 # a seeded shuffle of the positions
+    w = pow(7, (R_ORDER - 1) >> log_n, R_ORDER)
+    label, acc = [], 1
+    for _ in range(n):
+        label.append(acc)
+        acc = acc * w % R_ORDER
+    ident = [[pow(7, j, R_ORDER) * label[i] % R_ORDER for i in range(n)] for j in range(c)]
+    values = to_ints(scalars(total, seed ^ 0x5A5A))
+    wires = [[0] * n for _ in range(c)]
+    sigmas = [[0] * n for _ in range(c)]
+    at = 0
+    while at < total:
+        size = min(1 + int(words[total + at] % np.uint64(max_cycle)), total - at)
+        cyc = [int(p) for p in order[at:at + size]]
+        for q, p in enumerate(cyc):
+            nxt = cyc[(q + 1) % size]
+            wires[p // n][p % n] = values[at]
+            sigmas[p // n][p % n] = ident[nxt // n][nxt % n]
+        at += size
+    return wires, ident, sigmas
+
+
+def lookup_instance(n, seed=SEED):
+    """a seeded logUp instance of n rows: a table t of n distinct scalars, n looked-up values f drawn from it (some entries often, some
+    never) and the multiplicities m[i] = how often t[i] occurs in f.  Returns (f, t, m) as lists of Python ints; with any gamma that
+    meets no -f[i], -t[i]:  sum_i 1 / (gamma + f[i]) - m[i] / (gamma + t[i]) = 0."""
+    t = to_ints(scalars(n, seed ^ 0x7AB1E))
+    assert len(set(t)) == n
+    picks = splitmix64(seed ^ 0x100C, 0, n)
+    idx = [int(p % np.uint64(max(n // 3, 1))) * 3 % n for p in picks]        # only every third entry is ever looked up
+    m = [0] * n
+    for i in idx:
+        m[i] += 1
+    return [t[i] for i in idx], t, m

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <initializer_list>
 #include <utility>
 #include <vector>
 
@@ -358,6 +359,41 @@ inline std::vector<FrLimbs> fr_batch_invert(const std::vector<FrLimbs>& v, std::
   if (nonzero) nonzero->assign(v.size(), 1);
   if (v.empty()) return out;
   check(blsgpu_fr_batch_invert(Context::instance().handle(), v[0].data(), v.size(), out[0].data(), nonzero ? nonzero->data() : nullptr), "fr_batch_invert");
+  return out;
+}
+// Fraction scans (include/bls12_381_hip.h: blsgpu_fr_grand_product / blsgpu_fr_frac_sum): a column set is c tables of k rows, packed --
+// set.size() = c * k * len -- and an empty set stands for NULL (num_b, den_b: no beta term; mult: every multiplicity is 1).
+// fr_grand_product: f[i] = prod_j (num_a_j + beta num_b_j + gamma)[i] * inv0(prod_j (den_a_j + beta den_b_j + gamma)[i]), the PRODUCT scan
+// of f along each row; fr_frac_sum: f[i] = sum_j mult_j[i] * inv0(gamma + den_a_j[i] + beta den_b_j[i]), the SUM scan.  nonzero, if given,
+// gets a byte per element: 0 where a denominator factor was zero.
+namespace detail {
+inline size_t fr_frac_len(const char* what, size_t set, size_t c, size_t k, std::initializer_list<size_t> others) {
+  if (c == 0 || k == 0 || set % (c * k)) throw std::invalid_argument(std::string(what) + ": a set must be c tables of k rows of equal length");
+  for (size_t o : others) if (o && o != set) throw std::invalid_argument(std::string(what) + ": the column sets differ in size");
+  return set / (c * k);
+}
+}  // namespace detail
+inline std::vector<FrLimbs> fr_grand_product(size_t c, size_t k, const std::vector<FrLimbs>& num_a, const std::vector<FrLimbs>& num_b, const std::vector<FrLimbs>& den_a,
+                                             const std::vector<FrLimbs>& den_b, const FrLimbs& beta, const FrLimbs& gamma, bool exclusive = false, std::vector<uint8_t>* nonzero = nullptr) {
+  if (den_a.size() != num_a.size()) throw std::invalid_argument("fr_grand_product: num_a and den_a differ in size");
+  const size_t len = detail::fr_frac_len("fr_grand_product", num_a.size(), c, k, {num_b.size(), den_b.size()});
+  std::vector<FrLimbs> out(k * len);
+  if (nonzero) nonzero->assign(k * len, 1);
+  if (out.empty()) return out;
+  const FrLimbs chal[2] = {beta, gamma};
+  check(blsgpu_fr_grand_product(Context::instance().handle(), exclusive ? 1 : 0, (int)c, num_a[0].data(), num_b.empty() ? nullptr : num_b[0].data(), den_a[0].data(),
+                                den_b.empty() ? nullptr : den_b[0].data(), chal[0].data(), len, k, out[0].data(), nonzero ? nonzero->data() : nullptr), "fr_grand_product");
+  return out;
+}
+inline std::vector<FrLimbs> fr_frac_sum(size_t c, size_t k, const std::vector<FrLimbs>& mult, const std::vector<FrLimbs>& den_a, const std::vector<FrLimbs>& den_b, const FrLimbs& beta,
+                                        const FrLimbs& gamma, bool exclusive = false, std::vector<uint8_t>* nonzero = nullptr) {
+  const size_t len = detail::fr_frac_len("fr_frac_sum", den_a.size(), c, k, {mult.size(), den_b.size()});
+  std::vector<FrLimbs> out(k * len);
+  if (nonzero) nonzero->assign(k * len, 1);
+  if (out.empty()) return out;
+  const FrLimbs chal[2] = {beta, gamma};
+  check(blsgpu_fr_frac_sum(Context::instance().handle(), exclusive ? 1 : 0, (int)c, mult.empty() ? nullptr : mult[0].data(), den_a[0].data(), den_b.empty() ? nullptr : den_b[0].data(),
+                           chal[0].data(), len, k, out[0].data(), nonzero ? nonzero->data() : nullptr), "fr_frac_sum");
   return out;
 }
 // Polynomials in evaluation form (include/bls12_381_hip.h: blsgpu_fr_bary_*): k rows of evals.size() / k = 2^log_n values on the roots of

@@ -542,6 +542,42 @@ int blsgpu_fr_scan_many_device(blsgpu_ctx* ctx, int op, int exclusive, const voi
  * out == in, asynchrony and refusals as for blsgpu_fr_scan_many. */
 int blsgpu_fr_batch_invert(blsgpu_ctx* ctx, const uint64_t* values, size_t n, uint64_t* out, uint8_t* nonzero_flags);
 int blsgpu_fr_batch_invert_device(blsgpu_ctx* ctx, const void* d_in, size_t n, void* d_out, void* d_nonzero_flags);
+/* Fraction scans: the accumulator column of a permutation argument (grand product) and of a log-derivative lookup argument (logUp)
+ * from their c column sets in ONE call.  Rows as for blsgpu_fr_scan_many: k rows of `len` scalars laid end to end.  A column SET is c
+ * tables of k * len scalars each, table j starting j * pitch scalars behind the set's base pointer, pitch >= k * len (the addressing
+ * of blsgpu_fr_mle_fold_device); the host forms are packed, pitch = k * len.  challenges = (beta, gamma), two scalars behind ONE
+ * pointer: a DEVICE pointer in the device forms (like d_r of the fold: a transcript on the device needs no synchronisation), a host
+ * pointer in the host forms.  With inv0(x) = x^-1 and inv0(0) = 0 (blsgpu_fr_batch_invert's convention):
+ *   grand_product   n_j[i] = num_a_j[i] + beta * num_b_j[i] + gamma        d_j[i] = den_a_j[i] + beta * den_b_j[i] + gamma
+ *                   f[i]   = (prod_j n_j[i]) * inv0(prod_j d_j[i])
+ *                   out    = the PRODUCT scan of f along each row, exactly blsgpu_fr_scan_many's (exclusive: out[v][0] = 1)
+ *   frac_sum        f[i]   = sum_j mult_j[i] * inv0(gamma + den_a_j[i] + beta * den_b_j[i])
+ *                   out    = the SUM scan of f along each row, exactly blsgpu_fr_scan_many's (exclusive: out[v][0] = 0)
+ * so z = grand_product(exclusive, w, id, w, sigma) is PLONK's permutation accumulator and frac_sum's last element of a row is the
+ * logUp identity's left-hand side (signs belong in mult).  c in [1, 8].  num_b, den_b or both may be NULL: the beta term is dropped.
+ * mult may be NULL: every multiplicity is 1.  Input sets may alias each other in any way (num_a == den_a: both sides of the permutation
+ * argument read the same wires).  out is k * len scalars; nonzero_flags is k * len bytes or NULL: 0 where SOME denominator factor of
+ * element i is zero, 1 elsewhere.  A zero denominator follows the formulas above -- the product's f[i] is 0 and zeroes the rest of ITS
+ * row, the sum loses that one term -- so the results equal, limb for limb, the composition blsgpu_fr_op / blsgpu_fr_batch_invert /
+ * blsgpu_fr_scan_many in every case; a zero numerator factor is ordinary data.  The arithmetic is `Scalar`'s mul / add / invert
+ * (scalar.rs:435-503, :505-580); inputs and outputs are canonical Montgomery limbs, results are identical from run to run.
+ * out and nonzero_flags must overlap no input range and not each other: there is no in-place form.  k * len <= 2^28 and
+ * (c - 1) * pitch + k * len <= 2^28; k == 0 and len == 0 are no-ops.  Device pointers must be 16-byte aligned (nonzero_flags: any).
+ * The device forms are asynchronous on the context's stream and never synchronise; their scratch is the scans' (the context's own,
+ * not shared with pipelined *_msm_device calls in flight).  One field inversion per tile of BLSGPU_FR_FRAC_TILE elements whatever c
+ * is; a call of at most one tile is one launch.  BLSGPU_ERR_ARG (nothing staged or launched): c out of range, exclusive not 0 or 1, a
+ * NULL required pointer (num_a, den_a, challenges, out) with work to do, pitch < k * len, a size out of range (64-bit overflow
+ * included), a misaligned device pointer, out or nonzero_flags overlapping an input, the challenges or each other. */
+#define BLSGPU_FR_FRAC_MAX_COLS 8
+#define BLSGPU_FR_FRAC_TILE     1024   /* 512 for frac_sum with c > 4 */
+int blsgpu_fr_grand_product(blsgpu_ctx* ctx, int exclusive, int c, const uint64_t* num_a, const uint64_t* num_b, const uint64_t* den_a, const uint64_t* den_b,
+                            const uint64_t* challenges, size_t len, size_t k, uint64_t* out, uint8_t* nonzero_flags);
+int blsgpu_fr_grand_product_device(blsgpu_ctx* ctx, int exclusive, int c, const void* d_num_a, const void* d_num_b, const void* d_den_a, const void* d_den_b, size_t pitch,
+                                   const void* d_challenges, size_t len, size_t k, void* d_out, void* d_nonzero_flags);
+int blsgpu_fr_frac_sum(blsgpu_ctx* ctx, int exclusive, int c, const uint64_t* mult, const uint64_t* den_a, const uint64_t* den_b, const uint64_t* challenges, size_t len, size_t k,
+                       uint64_t* out, uint8_t* nonzero_flags);
+int blsgpu_fr_frac_sum_device(blsgpu_ctx* ctx, int exclusive, int c, const void* d_mult, const void* d_den_a, const void* d_den_b, size_t pitch, const void* d_challenges, size_t len,
+                              size_t k, void* d_out, void* d_nonzero_flags);
 /* Polynomials held in EVALUATION form (the Lagrange basis): the value at a point and the quotient of a KZG opening without leaving that
  * form.  k rows of n = 2^log_n scalars laid end to end (the layout of blsgpu_fr_ntt_many); row v holds f_v[i] = p_v(D[i]) for the unique
  * p_v of degree < n, with w the root blsgpu_fr_ntt uses for log_n and

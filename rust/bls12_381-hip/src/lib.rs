@@ -232,6 +232,53 @@ pub fn fr_batch_invert(gpu: &Gpu, values: &[Scalar]) -> Result<Vec<Option<Scalar
     check(unsafe { ffi::blsgpu_fr_batch_invert(gpu.ctx, input.as_ptr(), values.len(), out.as_mut_ptr(), flags.as_mut_ptr()) })?;
     Ok(limbs_scalars(gpu, &out)?.into_iter().zip(flags).map(|(s, f)| if f != 0 { Some(s) } else { None }).collect())
 }
+/// The accumulator column of a permutation argument (`blsgpu_fr_grand_product`): column sets of `c` tables of `k` rows, packed
+/// (`num_a.len() = c * k * len`); an empty `num_b` / `den_b` drops that side's beta term.  With n_j = num_a_j + beta num_b_j + gamma and
+/// d_j = den_a_j + beta den_b_j + gamma: f[i] = prod_j n_j[i] * (prod_j d_j[i])^-1 (0 where a d_j[i] is zero), and the result is the
+/// running product of f along each row (`exclusive`: starting from 1).  The flags are `false` where a denominator factor was zero.
+///
+/// # Panics
+/// If `c` or `k` is zero, a set's length is not a multiple of `c * k`, or the sets differ in length (the C++ mirror throws and the C ABI
+/// cannot see slice lengths at all: the sizes are checked here, before the call).  What the library itself refuses comes back as `Err`.
+pub fn fr_grand_product(gpu: &Gpu, c: usize, k: usize, num_a: &[Scalar], num_b: &[Scalar], den_a: &[Scalar], den_b: &[Scalar], beta: &Scalar, gamma: &Scalar,
+                        exclusive: bool) -> Result<(Vec<Scalar>, Vec<bool>), Error> {
+    assert!(c > 0 && k > 0 && num_a.len() % (c * k) == 0 && den_a.len() == num_a.len());
+    assert!((num_b.is_empty() || num_b.len() == num_a.len()) && (den_b.is_empty() || den_b.len() == num_a.len()));
+    let total = num_a.len() / c;
+    if total == 0 { return Ok((Vec::new(), Vec::new())); }
+    let lim = |v: &[Scalar]| if v.is_empty() { Ok(Vec::new()) } else { scalar_limbs(gpu, v) };
+    let (na, nb, da, db) = (lim(num_a)?, lim(num_b)?, lim(den_a)?, lim(den_b)?);
+    let chal = scalar_limbs(gpu, &[*beta, *gamma])?;
+    let opt = |v: &Vec<u64>| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+    let (mut out, mut flags) = (vec![0u64; total * 4], vec![0u8; total]);
+    check(unsafe {
+        ffi::blsgpu_fr_grand_product(gpu.ctx, exclusive as c_int, c as c_int, na.as_ptr(), opt(&nb), da.as_ptr(), opt(&db), chal.as_ptr(), total / k, k, out.as_mut_ptr(),
+                                     flags.as_mut_ptr())
+    })?;
+    Ok((limbs_scalars(gpu, &out)?, flags.into_iter().map(|f| f != 0).collect()))
+}
+/// The accumulator column of a log-derivative lookup argument (`blsgpu_fr_frac_sum`): f[i] = sum_j mult_j[i] / (gamma + den_a_j[i] +
+/// beta den_b_j[i]) with a zero denominator's term dropped, and the running sum of f along each row.  An empty `mult` means every
+/// multiplicity is 1 (signs belong in `mult`), an empty `den_b` drops the beta term.  Sets and flags as for `fr_grand_product`.
+///
+/// # Panics
+/// As `fr_grand_product`: on mismatched set sizes, before the call.
+pub fn fr_frac_sum(gpu: &Gpu, c: usize, k: usize, mult: &[Scalar], den_a: &[Scalar], den_b: &[Scalar], beta: &Scalar, gamma: &Scalar, exclusive: bool)
+                   -> Result<(Vec<Scalar>, Vec<bool>), Error> {
+    assert!(c > 0 && k > 0 && den_a.len() % (c * k) == 0);
+    assert!((mult.is_empty() || mult.len() == den_a.len()) && (den_b.is_empty() || den_b.len() == den_a.len()));
+    let total = den_a.len() / c;
+    if total == 0 { return Ok((Vec::new(), Vec::new())); }
+    let lim = |v: &[Scalar]| if v.is_empty() { Ok(Vec::new()) } else { scalar_limbs(gpu, v) };
+    let (m, da, db) = (lim(mult)?, lim(den_a)?, lim(den_b)?);
+    let chal = scalar_limbs(gpu, &[*beta, *gamma])?;
+    let opt = |v: &Vec<u64>| if v.is_empty() { std::ptr::null() } else { v.as_ptr() };
+    let (mut out, mut flags) = (vec![0u64; total * 4], vec![0u8; total]);
+    check(unsafe {
+        ffi::blsgpu_fr_frac_sum(gpu.ctx, exclusive as c_int, c as c_int, opt(&m), da.as_ptr(), opt(&db), chal.as_ptr(), total / k, k, out.as_mut_ptr(), flags.as_mut_ptr())
+    })?;
+    Ok((limbs_scalars(gpu, &out)?, flags.into_iter().map(|f| f != 0).collect()))
+}
 /// How a row of evaluations is ordered: `D[i] = w^i`, or `D[i] = w^bitrev(i)` (how blob formats store their rows).
 #[derive(Clone, Copy, PartialEq, Eq, Debug)]
 pub enum FrOrder { Natural = 0, BitReversed = 1 }
