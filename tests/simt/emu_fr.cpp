@@ -7,21 +7,11 @@
 // the same at any block size: `threads` == 0 runs the LDS kernels with ONE lane per workgroup in this thread (cheap: the breadth of
 // the cases), `threads` != 0 runs them with the plan's block size on one host thread per lane, which is what exercises the barriers.
 //
-// Built with -fsanitize=bounds,shift -fsanitize-trap=all, buffers from emu_guarded() end flush against an inaccessible page, and the
-// tests call this library from a child process (tests/simt_fr_child.py), as for tests/simt/emu_msm.cpp.
+// The lane pool, the launchers, the trapping checks and emu_guarded() are those of tests/simt/emu_harness.h; the tests call this
+// library from a child process (tests/simt_fr_child.py).
 #define EMU_LANES 512
 #define EMU_DYN_LDS_WORDS (9 * 4096)               // the largest column tile (FR_COLS_LOG)
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-#include <functional>
-#include <thread>
-#include <vector>
-
-thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuState g_emu;
-
-static inline unsigned long long __brevll(unsigned long long x) { return __builtin_bitreverse64(x); }
-static inline int __clzll(unsigned long long x) { return __builtin_clzll(x); }
+#include "emu_harness.h"
 
 #include "fr.hip.h"
 
@@ -29,42 +19,6 @@ using namespace bls;
 
 namespace {
 
-// the lane pool of tests/simt/emu_msm.cpp: EMU_LANES lane threads started once, a workgroup is one job for the lanes below its block size
-struct LanePool {
-  std::vector<std::thread> th;
-  EmuMeet<1> start, done;
-  std::function<void()> job;
-  unsigned block = 0, grid = 0, blk = 0;
-  LanePool() {
-    for (unsigned l = 0; l < EMU_LANES; l++)
-      th.emplace_back([this, l] {
-        for (;;) {
-          start.barrier(EMU_LANES + 1);
-          if (l < block) {
-            threadIdx.x = l; blockDim.x = block; blockIdx.x = blk; gridDim.x = grid;
-            job();
-          }
-          done.barrier(EMU_LANES + 1);
-        }
-      });
-  }
-  void workgroup(unsigned g, unsigned b, unsigned i, const std::function<void()>& fn) {
-    job = fn; grid = g; block = b; blk = i;
-    start.barrier(EMU_LANES + 1);
-    done.barrier(EMU_LANES + 1);
-  }
-};
-LanePool* pool() { static LanePool* p = new LanePool(); return p; }
-
-unsigned nblk(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-template <class Fn> void launch_threads(unsigned grid, unsigned block, Fn fn) {
-  for (unsigned i = 0; i < grid; i++) pool()->workgroup(grid, block, i, fn);
-}
-template <class Fn> void launch_loop(unsigned grid, unsigned block, Fn fn) {
-  blockDim.x = block; gridDim.x = grid;
-  for (unsigned i = 0; i < grid; i++)
-    for (unsigned l = 0; l < block; l++) { blockIdx.x = i; threadIdx.x = l; fn(); }
-}
 // a kernel that keeps a tile in LDS between barriers: its real block on lane threads, or one lane per workgroup
 template <class Fn> void launch_lds(bool threads, unsigned grid, unsigned block, Fn fn) {
   if (threads) launch_threads(grid, block, fn);
@@ -74,17 +28,6 @@ template <class Fn> void launch_lds(bool threads, unsigned grid, unsigned block,
 }  // namespace
 
 extern "C" {
-
-// as tests/simt/emu_msm.cpp: `bytes` bytes whose end is the start of an inaccessible page; never freed
-void* emu_guarded(size_t bytes) {
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  const size_t body = (bytes + page - 1) / page * page;
-  const size_t guard = (size_t)1 << 20;
-  char* m = (char*)mmap(nullptr, body + guard, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-  if (m == (char*)MAP_FAILED) return nullptr;
-  if (mprotect(m + body, guard, PROT_NONE) != 0) return nullptr;
-  return m + body - bytes;
-}
 
 // data: k 2^log_n scalars (8 u32 each), transformed in place.  tmp: as many (used when the plan says so, may be NULL otherwise);
 // tw: 2^log_n - 1 scalars; cs: 2^log_n scalars (coset != NULL); ninv: one scalar.  coset: 8 u32 Montgomery words or NULL.

@@ -3,19 +3,12 @@
 // launches from -- step by step, with its grids, blocks, LDS sizes and buffer roles, at whatever (block, chunk) the test asks for: a tile
 // of 64 x 2 elements reaches the multi-tile path at 129 elements and the second aggregate level at 128 * 128 + 1.
 //
-// As tests/simt/emu_fr_scan.cpp: every launch runs its block on one host thread per lane, the library is built with
-// -fsanitize=bounds,shift -fsanitize-trap=all, buffers from emu_guarded() end flush against an inaccessible page, and the tests call
-// this library from a child process (tests/simt_fr_frac_child.py).
+// Over tests/simt/emu_harness.h, as tests/simt/emu_fr_scan.cpp: every launch runs its block on one host thread per lane, the library
+// is built with the trapping bounds / shift checks, buffers from emu_guarded() end flush against an inaccessible page, and the
+// tests call this library from a child process (tests/simt_fr_frac_child.py).
 #define EMU_LANES 256
 #define EMU_DYN_LDS_WORDS (256 * (4 * 8 + 4) + 4 * 20)            // frs_lds_bytes of the largest shipped shape
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-#include <functional>
-#include <thread>
-#include <vector>
-
-thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuState g_emu;
+#include "emu_harness.h"
 
 #include "fr_frac.hip.h"
 static_assert(sizeof(bls::u32) * EMU_DYN_LDS_WORDS >= bls::frs_lds_bytes(bls::FrScanShape{bls::FRS_BLOCK, bls::FRF_CHUNK_MAX}), "EMU_DYN_LDS_WORDS is smaller than the shipped shapes' LDS");
@@ -23,35 +16,6 @@ static_assert(sizeof(bls::u32) * EMU_DYN_LDS_WORDS >= bls::frs_lds_bytes(bls::Fr
 using namespace bls;
 
 namespace {
-
-struct LanePool {
-  std::vector<std::thread> th;
-  EmuMeet<1> start, done;
-  std::function<void()> job;
-  unsigned block = 0, grid = 0, blk = 0;
-  LanePool() {
-    for (unsigned l = 0; l < EMU_LANES; l++)
-      th.emplace_back([this, l] {
-        for (;;) {
-          start.barrier(EMU_LANES + 1);
-          if (l < block) {
-            threadIdx.x = l; blockDim.x = block; blockIdx.x = blk; gridDim.x = grid;
-            job();
-          }
-          done.barrier(EMU_LANES + 1);
-        }
-      });
-  }
-  void workgroup(unsigned g, unsigned b, unsigned i, const std::function<void()>& fn) {
-    job = fn; grid = g; block = b; blk = i;
-    start.barrier(EMU_LANES + 1);
-    done.barrier(EMU_LANES + 1);
-  }
-};
-LanePool* pool() { static LanePool* p = new LanePool(); return p; }
-template <class Fn> void launch(unsigned grid, unsigned block, Fn fn) {
-  for (unsigned i = 0; i < grid; i++) pool()->workgroup(grid, block, i, fn);
-}
 
 struct Args { const u32 *xa, *xb, *da, *db, *chal; size_t pitch, len, k; int c, exclusive; u32* out; uint8_t* flags; };
 
@@ -68,13 +32,13 @@ int run(const FrFracPlan& plan, const Args& a, u32* const* buf, int* kernels_out
     kernels_out[i] = s.kernel;
     switch (s.kernel) {
       case FRF_K_FRONT:
-        launch(s.grid, s.block, [=] { k_frf_front<OP>(s.src, a.exclusive, a.c, a.xa, a.xb, a.da, a.db, a.pitch, a.chal, a.len, a.k, chunk, a.out, a.flags, dst, buf[FRS_BUF_LANE]); });
+        launch_threads(s.grid, s.block, [=] { k_frf_front<OP>(s.src, a.exclusive, a.c, a.xa, a.xb, a.da, a.db, a.pitch, a.chal, a.len, a.k, chunk, a.out, a.flags, dst, buf[FRS_BUF_LANE]); });
         break;
       case FRS_K_SCAN:
-        launch(s.grid, s.block, [=] { k_frs_tile<SOP>(s.kernel, a.exclusive, a.out, a.out, nullptr, a.len, a.k, chunk, dst, carry, buf[FRS_BUF_LANE]); });
+        launch_threads(s.grid, s.block, [=] { k_frs_tile<SOP>(s.kernel, a.exclusive, a.out, a.out, nullptr, a.len, a.k, chunk, dst, carry, buf[FRS_BUF_LANE]); });
         break;
       default:
-        launch(s.grid, s.block, [=] { k_frs_agg<SOP>(s.kernel, src, s.items, chunk, s.kernel == FRS_K_AGG_REDUCE ? dst : nullptr, carry, s.kernel == FRS_K_AGG_SCAN ? dst : nullptr); });
+        launch_threads(s.grid, s.block, [=] { k_frs_agg<SOP>(s.kernel, src, s.items, chunk, s.kernel == FRS_K_AGG_REDUCE ? dst : nullptr, carry, s.kernel == FRS_K_AGG_SCAN ? dst : nullptr); });
         break;
     }
   }
@@ -91,17 +55,6 @@ FrFracPlan plan_of(int op, int c, size_t len, size_t k, size_t pitch, int block,
 }  // namespace
 
 extern "C" {
-
-// as tests/simt/emu_msm.cpp: `bytes` bytes whose end is the start of an inaccessible page; never freed
-void* emu_guarded(size_t bytes) {
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  const size_t body = (bytes + page - 1) / page * page;
-  const size_t guard = (size_t)1 << 20;
-  char* m = (char*)mmap(nullptr, body + guard, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-  if (m == (char*)MAP_FAILED) return nullptr;
-  if (mprotect(m + body, guard, PROT_NONE) != 0) return nullptr;
-  return m + body - bytes;
-}
 
 // the plan of a call (block == 0: the shipped shape of (op, c)).  info: recs[5] (FrScanBuf order), then block, chunk, lds of step 0,
 // table_reach; kinds / grids: one entry per step.  Returns the number of steps, -1 for a refusal.

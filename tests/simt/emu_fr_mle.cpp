@@ -4,23 +4,13 @@
 // test asks for: a tile of 64 x 1 positions reaches the multi-workgroup path and the finish kernel at m = 8.
 //
 // The kernels add across lanes with __shfl_down and meet at the workgroup barrier, so every launch runs its block on one host thread per
-// lane (the lane pool of tests/simt/emu_fr_scan.cpp); there is no one-lane shortcut here.
+// lane (the lane pool of tests/simt/emu_harness.h); there is no one-lane shortcut here.
 //
-// Built with -fsanitize=bounds,shift -fsanitize-trap=all, buffers from emu_guarded() end flush against an inaccessible page, and the
+// Built with the trapping bounds / shift checks, buffers from emu_guarded() end flush against an inaccessible page, and the
 // tests call this library from a child process (tests/simt_fr_mle_child.py).
 #define EMU_LANES 256
 #define EMU_DYN_LDS_WORDS (256 * 2 * 8 * 8 + 4 * 7 * 8)           // frm_round_lds_bytes of the shipped shape with k = 8
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-#include <functional>
-#include <thread>
-#include <vector>
-
-thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuState g_emu;
-// fr.hip.h's transform code (not run here) uses two device intrinsics
-static inline unsigned long long __brevll(unsigned long long x) { return __builtin_bitreverse64(x); }
-static inline int __clzll(unsigned long long x) { return __builtin_clzll(x); }
+#include "emu_harness.h"
 
 #include "fr_mle.hip.h"
 static_assert(sizeof(bls::u32) * EMU_DYN_LDS_WORDS >= bls::frm_round_lds_bytes(bls::FrMleShape(), bls::FRM_MAX_K), "EMU_DYN_LDS_WORDS is smaller than the shipped shape's LDS");
@@ -30,35 +20,6 @@ using namespace bls;
 
 namespace {
 
-struct LanePool {
-  std::vector<std::thread> th;
-  EmuMeet<1> start, done;
-  std::function<void()> job;
-  unsigned block = 0, grid = 0, blk = 0;
-  LanePool() {
-    for (unsigned l = 0; l < EMU_LANES; l++)
-      th.emplace_back([this, l] {
-        for (;;) {
-          start.barrier(EMU_LANES + 1);
-          if (l < block) {
-            threadIdx.x = l; blockDim.x = block; blockIdx.x = blk; gridDim.x = grid;
-            job();
-          }
-          done.barrier(EMU_LANES + 1);
-        }
-      });
-  }
-  void workgroup(unsigned g, unsigned b, unsigned i, const std::function<void()>& fn) {
-    job = fn; grid = g; block = b; blk = i;
-    start.barrier(EMU_LANES + 1);
-    done.barrier(EMU_LANES + 1);
-  }
-};
-LanePool* pool() { static LanePool* p = new LanePool(); return p; }
-template <class Fn> void launch(unsigned grid, unsigned block, Fn fn) {
-  for (unsigned i = 0; i < grid; i++) pool()->workgroup(grid, block, i, fn);
-}
-bool shape_ok(int block, int chunk) { return block >= 64 && block <= EMU_LANES && block % 64 == 0 && chunk >= 1; }
 FrMleShape shape_of(int block, int chunk) { FrMleShape s; s.block = block; s.chunk = chunk; return s; }
 
 // api_aux.hip's frmle_launch with the launches replaced by the lane pool
@@ -76,23 +37,23 @@ int walk(const FrMlePlan& plan, FrMleShape shape, const u32* in, size_t pitch_in
     switch (s.kernel) {
       case FRM_K_FOLD: {
         const u32* rr = s.var >= 0 ? point + (size_t)s.var * 8 : r;
-        launch(s.grid, s.block, [=] { k_frm_fold(src, pi, dst, po, s.m - 1, s.items, rr); });
+        launch_threads(s.grid, s.block, [=] { k_frm_fold(src, pi, dst, po, s.m - 1, s.items, rr); });
         break;
       }
       case FRM_K_EQ:
-        launch(s.grid, s.block, [=] { k_frm_eq(point, s.m, frm_eq_lo(s.m, shape), dst); });
+        launch_threads(s.grid, s.block, [=] { k_frm_eq(point, s.m, frm_eq_lo(s.m, shape), dst); });
         break;
       case FRM_K_COPY:
         for (size_t j = 0; j < s.items; j++) memcpy(dst + j * po * 8, src + j * pi * 8, 32);
         break;
       case FRM_K_ROUND:
-        launch(s.grid, s.block, [=] { k_frm_round<false>(src, pi, s.items, (unsigned)k, (unsigned)shape.chunk, *prog, nullptr, dst); });
+        launch_threads(s.grid, s.block, [=] { k_frm_round<false>(src, pi, s.items, (unsigned)k, (unsigned)shape.chunk, *prog, nullptr, dst); });
         break;
       case FRM_K_ROUND_FUSED:
-        launch(s.grid, s.block, [=] { k_frm_round<true>(src, pi, s.items, (unsigned)k, (unsigned)shape.chunk, *prog, r, dst); });
+        launch_threads(s.grid, s.block, [=] { k_frm_round<true>(src, pi, s.items, (unsigned)k, (unsigned)shape.chunk, *prog, r, dst); });
         break;
       default:
-        launch(s.grid, s.block, [=] { k_frm_round_finish(src, s.items, prog->deg + 1, dst); });
+        launch_threads(s.grid, s.block, [=] { k_frm_round_finish(src, s.items, prog->deg + 1, dst); });
         break;
     }
   }
@@ -103,17 +64,6 @@ int walk(const FrMlePlan& plan, FrMleShape shape, const u32* in, size_t pitch_in
 }  // namespace
 
 extern "C" {
-
-// as tests/simt/emu_fr_scan.cpp: `bytes` bytes whose end is the start of an inaccessible page; never freed
-void* emu_guarded(size_t bytes) {
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  const size_t body = (bytes + page - 1) / page * page;
-  const size_t guard = (size_t)1 << 20;
-  char* m = (char*)mmap(nullptr, body + guard, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-  if (m == (char*)MAP_FAILED) return nullptr;
-  if (mprotect(m + body, guard, PROT_NONE) != 0) return nullptr;
-  return m + body - bytes;
-}
 
 // kernels_out of every entry point: the FrMleKernel of every step, -1 ends it (at least 30 ints).  Each returns the number of steps, -1
 // for a shape or size the plan does not take, -2 for a term program the validation refuses.

@@ -4,57 +4,18 @@
 // that header step by step, with its grids, blocks, buffer roles and level offsets, at whatever block the test asks for: with 16 lanes
 // per workgroup every level of a small tree still spans several workgroups and a partial last one.
 //
-// Every launch runs its block on one host thread per lane (the lane pool of tests/simt/emu_fr_scan.cpp), as the other emulations do.
+// Every launch runs its block on one host thread per lane (the lane pool of tests/simt/emu_harness.h), as the other emulations do.
 //
-// Built with -fsanitize=bounds,shift -fsanitize-trap=all, buffers from emu_guarded() -- the constant image included -- end flush against
+// Built with the trapping bounds / shift checks, buffers from emu_guarded() -- the constant image included -- end flush against
 // an inaccessible page, and the tests call this library from a child process (tests/simt_fr_poseidon_child.py).
 #define EMU_LANES 256
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-#include <functional>
-#include <thread>
-#include <vector>
-
-thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuState g_emu;
-// fr.hip.h's transform code (not run here) uses two device intrinsics
-static inline unsigned long long __brevll(unsigned long long x) { return __builtin_bitreverse64(x); }
-static inline int __clzll(unsigned long long x) { return __builtin_clzll(x); }
+#include "emu_harness.h"
 
 #include "fr_poseidon.hip.h"
 
 using namespace bls;
 
 namespace {
-
-struct LanePool {
-  std::vector<std::thread> th;
-  EmuMeet<1> start, done;
-  std::function<void()> job;
-  unsigned block = 0, grid = 0, blk = 0;
-  LanePool() {
-    for (unsigned l = 0; l < EMU_LANES; l++)
-      th.emplace_back([this, l] {
-        for (;;) {
-          start.barrier(EMU_LANES + 1);
-          if (l < block) {
-            threadIdx.x = l; blockDim.x = block; blockIdx.x = blk; gridDim.x = grid;
-            job();
-          }
-          done.barrier(EMU_LANES + 1);
-        }
-      });
-  }
-  void workgroup(unsigned g, unsigned b, unsigned i, const std::function<void()>& fn) {
-    job = fn; grid = g; block = b; blk = i;
-    start.barrier(EMU_LANES + 1);
-    done.barrier(EMU_LANES + 1);
-  }
-};
-LanePool* pool() { static LanePool* p = new LanePool(); return p; }
-template <class Fn> void launch(unsigned grid, unsigned block, Fn fn) {
-  for (unsigned i = 0; i < grid; i++) pool()->workgroup(grid, block, i, fn);
-}
 
 FrPoseidonHost g_inst;                              // the instance of the last emu_frp_create
 u32* g_img = nullptr;                               // its image, in a guarded buffer of exactly its size
@@ -64,25 +25,14 @@ void run_step(const FrPoseidonStep& s, const FrArg& tag, const u32* src, u32* ds
   const FrpArgs a = g_inst.args;
   const u32* img = g_img;
   switch (s.kernel) {
-    case FRP_K_PERMUTE: launch(s.grid, s.block, [=] { k_frp_permute<T, SP>(a, img, src, dst, s.items); }); break;
-    default: launch(s.grid, s.block, [=] { k_frp_hash<T, SP>(a, img, tag, src, dst, roots, s.items); }); break;      // HASH, LEVEL
+    case FRP_K_PERMUTE: launch_threads(s.grid, s.block, [=] { k_frp_permute<T, SP>(a, img, src, dst, s.items); }); break;
+    default: launch_threads(s.grid, s.block, [=] { k_frp_hash<T, SP>(a, img, tag, src, dst, roots, s.items); }); break;      // HASH, LEVEL
   }
 }
 
 }  // namespace
 
 extern "C" {
-
-// as tests/simt/emu_msm.cpp: `bytes` bytes whose end is the start of an inaccessible page; never freed
-void* emu_guarded(size_t bytes) {
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  const size_t body = (bytes + page - 1) / page * page;
-  const size_t guard = (size_t)1 << 20;
-  char* m = (char*)mmap(nullptr, body + guard, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-  if (m == (char*)MAP_FAILED) return nullptr;
-  if (mprotect(m + body, guard, PROT_NONE) != 0) return nullptr;
-  return m + body - bytes;
-}
 
 // blsgpu_fr_poseidon_create on the host: 0 and info = {form, products, image words}, or -1 and the refusal's text in `err`
 int emu_frp_create(int t, int r_full, int r_partial, const uint64_t* rc, const uint64_t* mds, int form, size_t* info, char* err, size_t err_len) {

@@ -4,20 +4,13 @@
 // elements reaches the multi-tile path at 129 elements and the second aggregate level at 128 * 128 + 1.
 //
 // The kernels scan across lanes with __shfl_up / __shfl_down and meet at the workgroup barrier, so every launch runs its block on one host
-// thread per lane (the lane pool of tests/simt/emu_fr.cpp); there is no one-lane shortcut here.
+// thread per lane (the lane pool of tests/simt/emu_harness.h); there is no one-lane shortcut here.
 //
-// Built with -fsanitize=bounds,shift -fsanitize-trap=all, buffers from emu_guarded() end flush against an inaccessible page, and the
+// Built with the trapping bounds / shift checks, buffers from emu_guarded() end flush against an inaccessible page, and the
 // tests call this library from a child process (tests/simt_fr_scan_child.py).
 #define EMU_LANES 256
 #define EMU_DYN_LDS_WORDS (256 * (8 * 8 + 4) + 4 * 20)            // frs_lds_bytes of the shipped shape
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-#include <functional>
-#include <thread>
-#include <vector>
-
-thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuState g_emu;
+#include "emu_harness.h"
 
 #include "fr_scan.hip.h"
 static_assert(sizeof(bls::u32) * EMU_DYN_LDS_WORDS >= bls::frs_lds_bytes(bls::FrScanShape()), "EMU_DYN_LDS_WORDS is smaller than the shipped shape's LDS");
@@ -25,36 +18,6 @@ static_assert(sizeof(bls::u32) * EMU_DYN_LDS_WORDS >= bls::frs_lds_bytes(bls::Fr
 using namespace bls;
 
 namespace {
-
-struct LanePool {
-  std::vector<std::thread> th;
-  EmuMeet<1> start, done;
-  std::function<void()> job;
-  unsigned block = 0, grid = 0, blk = 0;
-  LanePool() {
-    for (unsigned l = 0; l < EMU_LANES; l++)
-      th.emplace_back([this, l] {
-        for (;;) {
-          start.barrier(EMU_LANES + 1);
-          if (l < block) {
-            threadIdx.x = l; blockDim.x = block; blockIdx.x = blk; gridDim.x = grid;
-            job();
-          }
-          done.barrier(EMU_LANES + 1);
-        }
-      });
-  }
-  void workgroup(unsigned g, unsigned b, unsigned i, const std::function<void()>& fn) {
-    job = fn; grid = g; block = b; blk = i;
-    start.barrier(EMU_LANES + 1);
-    done.barrier(EMU_LANES + 1);
-  }
-};
-LanePool* pool() { static LanePool* p = new LanePool(); return p; }
-template <class Fn> void launch(unsigned grid, unsigned block, Fn fn) {
-  for (unsigned i = 0; i < grid; i++) pool()->workgroup(grid, block, i, fn);
-}
-bool shape_ok(int block, int chunk) { return block >= 64 && block <= EMU_LANES && block % 64 == 0 && chunk >= 1; }
 
 template <int OP>
 int run_scan(const FrScanPlan& plan, int exclusive, const u32* in, u32* out, const u32* points, size_t len, size_t k, unsigned chunk, u32* const* buf, int* kernels_out) {
@@ -67,10 +30,10 @@ int run_scan(const FrScanPlan& plan, int exclusive, const u32* in, u32* out, con
     kernels_out[i] = s.kernel;
     switch (s.kernel) {
       case FRS_K_SINGLE: case FRS_K_REDUCE: case FRS_K_SCAN:
-        launch(s.grid, s.block, [=] { k_frs_tile<OP>(s.kernel, exclusive, in, out, points, len, k, chunk, dst, carry, buf[FRS_BUF_LANE]); });
+        launch_threads(s.grid, s.block, [=] { k_frs_tile<OP>(s.kernel, exclusive, in, out, points, len, k, chunk, dst, carry, buf[FRS_BUF_LANE]); });
         break;
       default:
-        launch(s.grid, s.block, [=] { k_frs_agg<OP>(s.kernel, src, s.items, chunk, s.kernel == FRS_K_AGG_REDUCE ? dst : nullptr, carry, s.kernel == FRS_K_AGG_SCAN ? dst : nullptr); });
+        launch_threads(s.grid, s.block, [=] { k_frs_agg<OP>(s.kernel, src, s.items, chunk, s.kernel == FRS_K_AGG_REDUCE ? dst : nullptr, carry, s.kernel == FRS_K_AGG_SCAN ? dst : nullptr); });
         break;
     }
   }
@@ -81,17 +44,6 @@ int run_scan(const FrScanPlan& plan, int exclusive, const u32* in, u32* out, con
 }  // namespace
 
 extern "C" {
-
-// as tests/simt/emu_msm.cpp: `bytes` bytes whose end is the start of an inaccessible page; never freed
-void* emu_guarded(size_t bytes) {
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  const size_t body = (bytes + page - 1) / page * page;
-  const size_t guard = (size_t)1 << 20;
-  char* m = (char*)mmap(nullptr, body + guard, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-  if (m == (char*)MAP_FAILED) return nullptr;
-  if (mprotect(m + body, guard, PROT_NONE) != 0) return nullptr;
-  return m + body - bytes;
-}
 
 // the records each scratch buffer of the plan must hold (FrScanBuf order: agg0, agg1, carry0, carry1, lane); returns the number of steps
 int emu_fr_scan_recs(size_t len, size_t k, int block, int chunk, size_t* recs) {
@@ -125,7 +77,7 @@ int emu_fr_invert(const u32* in, u32* out, uint8_t* flags, size_t n, int block, 
     const FrScanStep s = plan.step[i];
     if (s.lds > sizeof(u32) * EMU_DYN_LDS_WORDS) return -1;
     kernels_out[i] = s.kernel;
-    launch(s.grid, s.block, [=] { k_frs_invert(in, out, flags, n, (unsigned)chunk); });
+    launch_threads(s.grid, s.block, [=] { k_frs_invert(in, out, flags, n, (unsigned)chunk); });
   }
   kernels_out[plan.n_steps] = -1;
   return plan.n_steps;

@@ -4,24 +4,14 @@
 // of 300 non-zeros already spans three tiles.  emu_fr_spmv_prepare / emu_fr_spmv_validate run the two upload kernels.
 //
 // The tile kernel scans across lanes with __shfl_up and meets at the workgroup barrier, the fix-up adds across a wavefront with
-// __shfl_down, so every launch runs its block on one host thread per lane (the lane pool of tests/simt/emu_fr_scan.cpp).
+// __shfl_down, so every launch runs its block on one host thread per lane (the lane pool of tests/simt/emu_harness.h).
 //
-// Built with -fsanitize=bounds,shift -fsanitize-trap=all, buffers from emu_guarded() end flush against an inaccessible page, and the
+// Built with the trapping bounds / shift checks, buffers from emu_guarded() end flush against an inaccessible page, and the
 // tests call this library from a child process (tests/simt_fr_spmv_child.py).
 #define EMU_LANES 256
 #define EMU_DYN_LDS_WORDS (256 * (8 * 8 + 4) + 256 * 8 + 4 * 20)      // frsp_lds_words of the shipped shape
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
+#include "emu_harness.h"
 #include <string.h>
-#include <functional>
-#include <thread>
-#include <vector>
-
-thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuState g_emu;
-// device intrinsics of fr.hip.h's transform kernels (included for the lazy limbs; as tests/simt/emu_fr.cpp)
-static inline unsigned long long __brevll(unsigned long long x) { return __builtin_bitreverse64(x); }
-static inline int __clzll(unsigned long long x) { return __builtin_clzll(x); }
 
 #include "fr_spmv.hip.h"
 static_assert(EMU_DYN_LDS_WORDS >= bls::frsp_lds_words(bls::FrSpmvShape()), "EMU_DYN_LDS_WORDS is smaller than the shipped shape's LDS");
@@ -30,51 +20,11 @@ using namespace bls;
 
 namespace {
 
-struct LanePool {
-  std::vector<std::thread> th;
-  EmuMeet<1> start, done;
-  std::function<void()> job;
-  unsigned block = 0, grid = 0, blk = 0;
-  LanePool() {
-    for (unsigned l = 0; l < EMU_LANES; l++)
-      th.emplace_back([this, l] {
-        for (;;) {
-          start.barrier(EMU_LANES + 1);
-          if (l < block) {
-            threadIdx.x = l; blockDim.x = block; blockIdx.x = blk; gridDim.x = grid;
-            job();
-          }
-          done.barrier(EMU_LANES + 1);
-        }
-      });
-  }
-  void workgroup(unsigned g, unsigned b, unsigned i, const std::function<void()>& fn) {
-    job = fn; grid = g; block = b; blk = i;
-    start.barrier(EMU_LANES + 1);
-    done.barrier(EMU_LANES + 1);
-  }
-};
-LanePool* pool() { static LanePool* p = new LanePool(); return p; }
-template <class Fn> void launch(unsigned grid, unsigned block, Fn fn) {
-  for (unsigned i = 0; i < grid; i++) pool()->workgroup(grid, block, i, fn);
-}
-bool shape_ok(int block, int chunk) { return block >= 64 && block <= EMU_LANES && block % 64 == 0 && chunk >= 1; }
 FrSpmvShape shape_of(int block, int chunk) { FrSpmvShape s; s.block = block; s.chunk = chunk; return s; }
 
 }  // namespace
 
 extern "C" {
-
-// as tests/simt/emu_msm.cpp: `bytes` bytes whose end is the start of an inaccessible page; never freed
-void* emu_guarded(size_t bytes) {
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  const size_t body = (bytes + page - 1) / page * page;
-  const size_t guard = (size_t)1 << 20;
-  char* m = (char*)mmap(nullptr, body + guard, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-  if (m == (char*)MAP_FAILED) return nullptr;
-  if (mprotect(m + body, guard, PROT_NONE) != 0) return nullptr;
-  return m + body - bytes;
-}
 
 // sizes[0] = tiles, [1] = scalars each of HEAD and TAIL must hold, [2] = words of META; returns the number of steps of the plan
 int emu_fr_spmv_sizes(size_t n_rows, size_t nnz, size_t k, int has_empty, int block, int chunk, size_t* sizes) {
@@ -86,7 +36,7 @@ int emu_fr_spmv_sizes(size_t n_rows, size_t nnz, size_t k, int has_empty, int bl
 // flag: one word, zero on entry
 void emu_fr_spmv_validate(const u32* row_ptr, const u32* col, const u32* val, size_t n_rows, size_t n_cols, size_t nnz, u32* flag) {
   const size_t span = nnz > n_rows ? nnz : n_rows;
-  launch((unsigned)((span + 255) / 256), 256, [=] { k_frsp_validate(row_ptr, col, val, n_rows, n_cols, nnz, flag); });
+  launch_threads((unsigned)((span + 255) / 256), 256, [=] { k_frsp_validate(row_ptr, col, val, n_rows, n_cols, nnz, flag); });
 }
 // val_out: nnz scalars; tile_row: tiles + 1 words; flag: two words, zero on entry (flag[1]: a row is empty)
 int emu_fr_spmv_prepare(const u32* row_ptr, const u32* val_in, u32* val_out, u32* tile_row, u32* flag, size_t n_rows, size_t nnz, int block, int chunk) {
@@ -94,7 +44,7 @@ int emu_fr_spmv_prepare(const u32* row_ptr, const u32* val_in, u32* val_out, u32
   const size_t tiles = frsp_tiles(nnz, shape_of(block, chunk));
   size_t span = nnz > n_rows ? nnz : n_rows;
   if (tiles + 1 > span) span = tiles + 1;
-  launch((unsigned)((span + 255) / 256), 256, [=] { k_frsp_prepare(row_ptr, val_in, val_out, tile_row, flag, n_rows, nnz, tiles, (unsigned)(block * chunk)); });
+  launch_threads((unsigned)((span + 255) / 256), 256, [=] { k_frsp_prepare(row_ptr, val_in, val_out, tile_row, flag, n_rows, nnz, tiles, (unsigned)(block * chunk)); });
   return 0;
 }
 // the prepared matrix (val = what emu_fr_spmv_prepare wrote) times x (k x n_cols scalars) -> out (k x n_rows scalars); head / tail:
@@ -113,10 +63,10 @@ int emu_fr_spmv(const u32* row_ptr, const u32* col, const u32* val, const u32* t
         memset(out, 0, s.items * 32);
         break;
       case FRSP_K_TILE:
-        launch(s.grid, s.block, [=] { k_frsp_tile(row_ptr, col, val, tile_row, n_rows, n_cols, nnz, x, out, k, (unsigned)chunk, head, tail, meta); });
+        launch_threads(s.grid, s.block, [=] { k_frsp_tile(row_ptr, col, val, tile_row, n_rows, n_cols, nnz, x, out, k, (unsigned)chunk, head, tail, meta); });
         break;
       default:
-        launch(s.grid, s.block, [=] { k_frsp_fixup(row_ptr, head, tail, meta, s.items, n_rows, k, (unsigned)plan.tile, out); });
+        launch_threads(s.grid, s.block, [=] { k_frsp_fixup(row_ptr, head, tail, meta, s.items, n_rows, k, (unsigned)plan.tile, out); });
         break;
     }
   }

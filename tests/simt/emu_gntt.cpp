@@ -8,21 +8,11 @@
 // shape exchanges values inside lane pairs and the team shapes meet at the mailbox barriers: they run with the plan's block size on one
 // host thread per lane (tests/simt/hip/hip_runtime.h).
 //
-// Built with -fsanitize=bounds,shift -fsanitize-trap=all, buffers from emu_guarded() end flush against an inaccessible page, and the
-// tests call this library from a child process (tests/simt_gntt_child.py), as for tests/simt/emu_fr.cpp.
+// The lane pool, the launchers, the trapping checks and emu_guarded() are those of tests/simt/emu_harness.h; the tests call this
+// library from a child process (tests/simt_gntt_child.py).
 #define EMU_LANES 256
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
+#include "emu_harness.h"
 #include <cstdlib>
-#include <functional>
-#include <thread>
-#include <vector>
-
-thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuState g_emu;
-
-static inline unsigned long long __brevll(unsigned long long x) { return __builtin_bitreverse64(x); }
-static inline int __clzll(unsigned long long x) { return __builtin_clzll(x); }
 
 #include "fr.hip.h"
 #include "gntt.hip.h"
@@ -30,43 +20,6 @@ static inline int __clzll(unsigned long long x) { return __builtin_clzll(x); }
 using namespace bls;
 
 namespace {
-
-// the lane pool of tests/simt/emu_msm.cpp: EMU_LANES lane threads started once, a workgroup is one job for the lanes below its block size
-struct LanePool {
-  std::vector<std::thread> th;
-  EmuMeet<1> start, done;
-  std::function<void()> job;
-  unsigned block = 0, grid = 0, blk = 0;
-  LanePool() {
-    for (unsigned l = 0; l < EMU_LANES; l++)
-      th.emplace_back([this, l] {
-        for (;;) {
-          start.barrier(EMU_LANES + 1);
-          if (l < block) {
-            threadIdx.x = l; blockDim.x = block; blockIdx.x = blk; gridDim.x = grid;
-            job();
-          }
-          done.barrier(EMU_LANES + 1);
-        }
-      });
-  }
-  void workgroup(unsigned g, unsigned b, unsigned i, const std::function<void()>& fn) {
-    job = fn; grid = g; block = b; blk = i;
-    start.barrier(EMU_LANES + 1);
-    done.barrier(EMU_LANES + 1);
-  }
-};
-LanePool* pool() { static LanePool* p = new LanePool(); return p; }
-
-unsigned nblk(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-template <class Fn> void launch_threads(unsigned grid, unsigned block, Fn fn) {
-  for (unsigned i = 0; i < grid; i++) pool()->workgroup(grid, block, i, fn);
-}
-template <class Fn> void launch_loop(unsigned grid, unsigned block, Fn fn) {
-  blockDim.x = block; gridDim.x = grid;
-  for (unsigned i = 0; i < grid; i++)
-    for (unsigned l = 0; l < block; l++) { blockIdx.x = i; threadIdx.x = l; fn(); }
-}
 
 // api_msm.hip g_ntt_many_device: the loop over the plan
 template <class LaneS, class TeamS>
@@ -85,17 +38,6 @@ void run_plan(const GnPlan& plan, u32* x, const u32* tw, const u32* ninv, int lo
 }  // namespace
 
 extern "C" {
-
-// as tests/simt/emu_msm.cpp: `bytes` bytes whose end is the start of an inaccessible page; never freed
-void* emu_guarded(size_t bytes) {
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  const size_t body = (bytes + page - 1) / page * page;
-  const size_t guard = (size_t)1 << 20;
-  char* m = (char*)mmap(nullptr, body + guard, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-  if (m == (char*)MAP_FAILED) return nullptr;
-  if (mprotect(m + body, guard, PROT_NONE) != 0) return nullptr;
-  return m + body - bytes;
-}
 
 // the plan alone: six ints per step (kernel, shape, grid, block, LDS bytes, stage) into out (at least 6 * 25 ints); returns the number
 // of steps, -1 for arguments the entry points refuse.  team_max < 0: BLSGPU_GNTT_TEAM_MAX or the built-in constant, as the library.

@@ -4,18 +4,10 @@
 // the lines it restates), every lane a host thread where lanes cooperate (tests/simt/hip/hip_runtime.h), so that the CPU suite can
 // compare the very code the GPU runs with the oracle (tests/test_simt_msm.py).
 //
-// Built with -fsanitize=bounds,shift -fsanitize-trap=all: an index outside an LDS array traps.  emu_guarded() places a buffer so that
-// it ends flush against an inaccessible page: a read past its end faults.  Both end the process, so the tests call this library from
-// a child process of their own.
+// The lane pool, the launchers, the trapping checks and emu_guarded() are those of tests/simt/emu_harness.h; the tests call this
+// library from a child process (tests/simt_msm_child.py).
 #define EMU_LANES 256
-#include <hip/hip_runtime.h>
-#include <sys/mman.h>
-#include <functional>
-#include <thread>
-#include <vector>
-
-thread_local EmuDim3 threadIdx, blockIdx, blockDim, gridDim;
-EmuState g_emu;
+#include "emu_harness.h"
 
 #include "msm_seg.hip.h"
 #include "abi_kernels.hip.h"
@@ -23,45 +15,6 @@ EmuState g_emu;
 using namespace bls;
 
 namespace {
-
-// A pool of EMU_LANES lane threads, started once: a workgroup is one job for the lanes below its block size.
-struct LanePool {
-  std::vector<std::thread> th;
-  EmuMeet<1> start, done;
-  std::function<void()> job;
-  unsigned block = 0, grid = 0, blk = 0;
-  LanePool() {
-    for (unsigned l = 0; l < EMU_LANES; l++)
-      th.emplace_back([this, l] {
-        for (;;) {
-          start.barrier(EMU_LANES + 1);
-          if (l < block) {
-            threadIdx.x = l; blockDim.x = block; blockIdx.x = blk; gridDim.x = grid;
-            job();
-          }
-          done.barrier(EMU_LANES + 1);
-        }
-      });
-  }
-  void workgroup(unsigned g, unsigned b, unsigned i, const std::function<void()>& fn) {
-    job = fn; grid = g; block = b; blk = i;
-    start.barrier(EMU_LANES + 1);
-    done.barrier(EMU_LANES + 1);
-  }
-};
-LanePool* pool() { static LanePool* p = new LanePool(); return p; }          // never destroyed: its threads wait for work until the process ends
-
-unsigned nblk(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }   // host.h
-// kernel<<<grid, block>>> with one host thread per lane
-template <class Fn> void launch_threads(unsigned grid, unsigned block, Fn fn) {
-  for (unsigned i = 0; i < grid; i++) pool()->workgroup(grid, block, i, fn);
-}
-// the same for a kernel without any cross-lane operation: the lanes one after the other in this thread
-template <class Fn> void launch_loop(unsigned grid, unsigned block, Fn fn) {
-  blockDim.x = block; gridDim.x = grid;
-  for (unsigned i = 0; i < grid; i++)
-    for (unsigned l = 0; l < block; l++) { blockIdx.x = i; threadIdx.x = l; fn(); }
-}
 
 // api_msm.hip msm_segments_launch (:644-661): the batch loop, accumulate -> combine -> export per batch of `batch` segments
 template <class F, int MODE, class FK>
@@ -82,17 +35,6 @@ void segments(const u32* rec, const u32* endo, size_t nbases, const u32* bf, con
 }  // namespace
 
 extern "C" {
-
-// `bytes` bytes (a multiple of 4) whose end is the start of an inaccessible page; never freed
-void* emu_guarded(size_t bytes) {
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  const size_t body = (bytes + page - 1) / page * page;
-  const size_t guard = (size_t)1 << 20;          // wider than any stride of the kernels: a read far past the end still faults
-  char* m = (char*)mmap(nullptr, body + guard, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-  if (m == (char*)MAP_FAILED) return nullptr;
-  if (mprotect(m + body, guard, PROT_NONE) != 0) return nullptr;
-  return m + body - bytes;
-}
 
 // api_msm.hip bases_import (:62), bases_make_endo (:32-33, :43-44); group 1 = G1, 2 = G2
 void emu_bases_import(int group, const u32* xy, const uint8_t* inf, u32* rec, size_t n) {

@@ -2,6 +2,8 @@
 // every lane of a quad is a host thread, DPP moves are slot exchanges (tests/simt/hip/hip_runtime.h).  The entry points run
 // the __global__ functions themselves, one quad per call, so that the CPU suite can compare the very code the GPU runs with
 // the oracle (tests/test_simt_emulation.py).
+// Not built on tests/simt/emu_harness.h: it starts fresh threads per call, with EMU_LANES from the command line, and has no use
+// for the pool or emu_guarded(); sharing the two definitions below would take a switch in the harness to leave the rest out.
 #include <hip/hip_runtime.h>
 #include <thread>
 #include <vector>

@@ -112,6 +112,9 @@ static inline unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetc
 static inline unsigned atomicOr(unsigned* p, unsigned v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
 static inline void __threadfence() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 template <class T> static inline T min(T a, T b) { return a < b ? a : b; }
+// bit intrinsics of fr.hip.h's transform kernels (every header that includes it for the field code sees them too)
+static inline unsigned long long __brevll(unsigned long long x) { return __builtin_bitreverse64(x); }
+static inline int __clzll(unsigned long long x) { return __builtin_clzll(x); }
 // wave vote: every emulated lane decides for itself (only used for an early loop exit whose extra iterations are identities)
 static inline int __all(int p) { return p; }
 struct uint4 { unsigned x, y, z, w; };

@@ -1,6 +1,6 @@
 """Builds the multilinear emulation library (tests/simt/emu_fr_mle.cpp) and runs its entry points in a CHILD process (tests/test_simt_fr_mle.py).
 
-As tests/simt_fr_scan_child.py: the library is built with trapping bounds / shift checks, every buffer the kernels touch has exactly the size
+Over tests/simt_harness.py: the library is built with trapping bounds / shift checks, every buffer the kernels touch has exactly the size
 the plan asks the host to reserve -- tables of (k - 1) * pitch + 2^m scalars, records, scratch -- and ends flush against an inaccessible
 page (emu_guarded), so a kernel bug ends the process that runs it: `run(jobs)` starts `python tests/simt_fr_mle_child.py IN OUT` with the
 pickled jobs, under a time limit, and turns a signal, a time-out or a non-zero exit into a pytest failure that names the job.
@@ -15,71 +15,33 @@ Montgomery words, placed `pitch` scalars apart in a buffer whose other words hol
 `kernels` is the sequence of fr_mle_plan.h FrMleKernel values the plan ran.
 Test infrastructure only: the product never imports this file."""
 import ctypes
-import os
-import pickle
-import signal
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-LIB = os.path.join(ROOT, "build", "libemu_fr_mle_test.so")
+import simt_harness
+
+ROOT, CLANG = simt_harness.ROOT, simt_harness.CLANG
+LIB = simt_harness.lib_path("emu_fr_mle_test")
 K_FOLD, K_EQ, K_ROUND, K_ROUND_FUSED, K_FINISH, K_COPY = 0, 1, 2, 3, 4, 5
 SHIPPED = (256, 4)                                                 # fr_mle_plan.h FRM_BLOCK, FRM_CHUNK
 SENTINEL = 0xA5C3F00D
 
 
 def build():
-    """build/libemu_fr_mle_test.so, rebuilt when a source is newer (as the other emulation libraries are)"""
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    src = os.path.join(ROOT, "tests", "simt", "emu_fr_mle.cpp")
-    csrc = os.path.join(ROOT, "bls12_381_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "tests", "simt", "hip", "hip_runtime.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        tmp = LIB + ".tmp%d" % os.getpid()
-        subprocess.check_call([CLANG, "-O1", "-std=c++17", "-pthread", "-fPIC", "-shared", "-Wno-unused-value", "-Wno-psabi",
-                               "-fsanitize=bounds,shift", "-fsanitize-trap=all",
-                               "-I" + os.path.join(ROOT, "tests", "simt"), "-I" + csrc, src, "-o", tmp])
-        os.replace(tmp, LIB)
-    return LIB
+    """build/libemu_fr_mle_test.so, rebuilt when a source is newer"""
+    return simt_harness.build("emu_fr_mle_test", "emu_fr_mle.cpp")
 
 
 def run(jobs, timeout=300):
     """the jobs in a fresh child process; returns their results or fails the calling test"""
-    import pytest
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in.pkl"), os.path.join(d, "out.pkl")
-        with open(fin, "wb") as fh:
-            pickle.dump(jobs, fh)
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=True)
-        except subprocess.TimeoutExpired as e:
-            err = e.stderr if isinstance(e.stderr, str) else (e.stderr or b"").decode()
-            pytest.fail("the emulation did not finish in %d s (a lane waiting at a barrier for ever?); last job: %s" % (timeout, _last_job(err)))
-        if p.returncode != 0:
-            what = "signal %s" % signal.Signals(-p.returncode).name if p.returncode < 0 else "exit status %d" % p.returncode
-            hint = {"SIGILL": " (a trapping bounds / shift check)", "SIGTRAP": " (a trapping bounds / shift check)",
-                    "SIGSEGV": " (an access outside a guarded buffer)"}.get(what.split()[-1], "")
-            pytest.fail("the emulation child ended with %s%s in job: %s\n%s" % (what, hint, _last_job(p.stderr), p.stderr[-2000:]))
-        with open(fout, "rb") as fh:
-            return pickle.load(fh)
-
-
-def _last_job(err):
-    marks = [l for l in (err or "").splitlines() if l.startswith("JOB ")]
-    return marks[-1][4:] if marks else "(none started)"
+    return simt_harness.run(__file__, jobs, timeout)
 
 
 # ---- child side --------------------------------------------------------------------------------------------------------------
-class _Child:
+class _Child(simt_harness.Child):
     def __init__(self):
-        self.lib = ctypes.CDLL(LIB)
+        super().__init__(LIB)
         vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-        self.lib.emu_guarded.restype = vp
-        self.lib.emu_guarded.argtypes = [sz]
         self.lib.emu_frm_fold.argtypes = [vp, sz, vp, sz, ci, sz, vp, ci, ci, vp]
         self.lib.emu_frm_eq.argtypes = [vp, ci, vp, ci, ci, vp]
         self.lib.emu_frm_eval_scratch.restype = sz
@@ -89,20 +51,6 @@ class _Child:
         self.lib.emu_frm_round_recs.argtypes = [ci, sz, ci, ci, ci, ci]
         self.lib.emu_frm_prog_degree.argtypes = [sz, sz, vp, vp, vp]
         self.lib.emu_frm_round.argtypes = [vp, sz, ci, sz, sz, vp, vp, vp, vp, vp, vp, ci, ci, vp]
-
-    def buf(self, words, init=None, dtype=np.uint32, fill=0):
-        """guarded buffer of exactly `words` items (its last item is the last accessible one), as (numpy view, address); None for none"""
-        if words == 0:
-            return None, None
-        size = np.dtype(dtype).itemsize
-        p = self.lib.emu_guarded(words * size)
-        assert p, "emu_guarded failed"
-        ct = {1: ctypes.c_uint8, 4: ctypes.c_uint32, 8: ctypes.c_uint64}[size]
-        a = np.frombuffer((ct * words).from_address(p), dtype=dtype)
-        a[:] = fill
-        if init is not None:
-            a[:] = np.ascontiguousarray(init, dtype=dtype).reshape(-1)
-        return a, ctypes.c_void_p(p)
 
     def tables(self, t, pitch):
         """k tables `pitch` scalars apart in a buffer of exactly (k - 1) * pitch + n scalars, SENTINEL in between"""
@@ -192,18 +140,5 @@ class _Child:
         return {"evals": dev.copy().reshape(-1, 8), "after": din.copy().reshape(-1, 8), "kernels": self.kernels(kern, rc), "degree": deg}
 
 
-def _main(fin, fout):
-    with open(fin, "rb") as fh:
-        jobs = pickle.load(fh)
-    c = _Child()
-    results = []
-    for i, j in enumerate(jobs):
-        sys.stderr.write("JOB %d %s: %s\n" % (i, j["op"], j.get("label", "")))
-        sys.stderr.flush()
-        results.append(getattr(c, j["op"])(j))
-    with open(fout, "wb") as fh:
-        pickle.dump(results, fh)
-
-
 if __name__ == "__main__":
-    _main(sys.argv[1], sys.argv[2])
+    _Child.main()

@@ -1,6 +1,6 @@
 """Builds the Poseidon emulation library (tests/simt/emu_fr_poseidon.cpp) and runs it in a CHILD process (tests/test_simt_fr_poseidon.py).
 
-As tests/simt_fr_bary_child.py: the library is built with trapping bounds / shift checks, every buffer the kernels touch -- the constant
+Over tests/simt_harness.py: the library is built with trapping bounds / shift checks, every buffer the kernels touch -- the constant
 image included -- has exactly the size the entry point reserves and ends flush against an inaccessible page (emu_guarded), so a kernel
 bug ends the process that runs it: `run(jobs)` starts `python tests/simt_fr_poseidon_child.py IN OUT` with the pickled jobs, under a time
 limit, and turns a signal, a time-out or a non-zero exit into a pytest failure that names the job.
@@ -15,89 +15,42 @@ kernels (the fr_poseidon_plan.h FrPoseidonKernel values the plan ran), data_afte
 Test infrastructure only: the product never imports this file."""
 import ctypes
 import os
-import pickle
-import signal
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fr_poseidon_ref as ref  # noqa: E402
+import simt_harness  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-LIB = os.path.join(ROOT, "build", "libemu_fr_poseidon_test.so")
+ROOT, CLANG = simt_harness.ROOT, simt_harness.CLANG
+LIB = simt_harness.lib_path("emu_fr_poseidon_test")
 K_PERMUTE, K_HASH, K_LEVEL, K_COPY = 0, 1, 2, 4
 FORM_AUTO, FORM_DENSE, FORM_SPARSE = 0, 1, 2
 SHIPPED = 256                                                      # fr_poseidon_plan.h FRP_BLOCK
 
 
 def build():
-    """build/libemu_fr_poseidon_test.so, rebuilt when a source is newer (as the other emulation libraries are)"""
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    src = os.path.join(ROOT, "tests", "simt", "emu_fr_poseidon.cpp")
-    csrc = os.path.join(ROOT, "bls12_381_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "tests", "simt", "hip", "hip_runtime.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        tmp = LIB + ".tmp%d" % os.getpid()
-        subprocess.check_call([CLANG, "-O1", "-std=c++17", "-pthread", "-fPIC", "-shared", "-Wno-unused-value", "-Wno-psabi",
-                               "-fsanitize=bounds,shift", "-fsanitize-trap=all",
-                               "-I" + os.path.join(ROOT, "tests", "simt"), "-I" + csrc, src, "-o", tmp])
-        os.replace(tmp, LIB)
-    return LIB
+    """build/libemu_fr_poseidon_test.so, rebuilt when a source is newer"""
+    return simt_harness.build("emu_fr_poseidon_test", "emu_fr_poseidon.cpp")
 
 
 def run(jobs, timeout=600):
     """the jobs in a fresh child process; returns their results or fails the calling test"""
-    import pytest
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in.pkl"), os.path.join(d, "out.pkl")
-        with open(fin, "wb") as fh:
-            pickle.dump(jobs, fh)
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=True)
-        except subprocess.TimeoutExpired as e:
-            err = e.stderr if isinstance(e.stderr, str) else (e.stderr or b"").decode()
-            pytest.fail("the emulation did not finish in %d s (a lane waiting at a barrier for ever?); last job: %s" % (timeout, _last_job(err)))
-        if p.returncode != 0:
-            what = "signal %s" % signal.Signals(-p.returncode).name if p.returncode < 0 else "exit status %d" % p.returncode
-            hint = {"SIGILL": " (a trapping bounds / shift check)", "SIGTRAP": " (a trapping bounds / shift check)",
-                    "SIGSEGV": " (an access outside a guarded buffer)"}.get(what.split()[-1], "")
-            pytest.fail("the emulation child ended with %s%s in job: %s\n%s" % (what, hint, _last_job(p.stderr), p.stderr[-2000:]))
-        with open(fout, "rb") as fh:
-            return pickle.load(fh)
-
-
-def _last_job(err):
-    marks = [l for l in (err or "").splitlines() if l.startswith("JOB ")]
-    return marks[-1][4:] if marks else "(none started)"
+    return simt_harness.run(__file__, jobs, timeout)
 
 
 # ---- child side --------------------------------------------------------------------------------------------------------------
-class _Child:
+class _Child(simt_harness.Child):
+    OP = "job"
+
     def __init__(self):
-        self.lib = ctypes.CDLL(LIB)
-        self.lib.emu_guarded.restype = ctypes.c_void_p
-        self.lib.emu_guarded.argtypes = [ctypes.c_size_t]
+        super().__init__(LIB)
         vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
         self.lib.emu_frp_create.argtypes = [ci, ci, ci, vp, vp, ci, vp, vp, sz]
         self.lib.emu_frp_plan.argtypes = [ci, sz, ci, ci, ci, vp]
         self.lib.emu_frp_run.argtypes = [ci, vp, vp, sz, ci, ci, vp, vp, ci, vp]
         self.last = None
-
-    def buf(self, words, init=None, fill=0):
-        """guarded buffer of exactly `words` u32 (its last word is the last accessible one), as (numpy view, address); None for none"""
-        if words == 0:
-            return None, None
-        p = self.lib.emu_guarded(words * 4)
-        assert p, "emu_guarded failed"
-        a = np.frombuffer((ctypes.c_uint32 * words).from_address(p), dtype=np.uint32)
-        a[:] = fill
-        if init is not None:
-            a[:] = np.ascontiguousarray(init, dtype=np.uint32).reshape(-1)
-        return a, ctypes.c_void_p(p)
 
     def create(self, j):
         t, rf, rp, consts, mds = j["params"]
@@ -162,18 +115,5 @@ class _Child:
         return res
 
 
-def _main(fin, fout):
-    with open(fin, "rb") as fh:
-        jobs = pickle.load(fh)
-    c = _Child()
-    results = []
-    for i, j in enumerate(jobs):
-        sys.stderr.write("JOB %d: %s\n" % (i, j.get("label", "")))
-        sys.stderr.flush()
-        results.append(c.job(j))
-    with open(fout, "wb") as fh:
-        pickle.dump(results, fh)
-
-
 if __name__ == "__main__":
-    _main(sys.argv[1], sys.argv[2])
+    _Child.main()

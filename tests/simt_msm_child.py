@@ -1,8 +1,9 @@
 """Builds the MSM emulation library (tests/simt/emu_msm.cpp) and runs its entry points in a CHILD process (tests/test_simt_msm.py).
 
-The library is built with trapping bounds / shift checks, and every buffer the kernels read ends flush against an inaccessible page
-(emu_guarded), so a kernel bug ends the process that runs it: `run(jobs)` starts `python tests/simt_msm_child.py IN OUT` with the
-pickled jobs, under a time limit, and turns a signal, a time-out or a non-zero exit into a pytest failure that names the job.
+Over tests/simt_harness.py: the library is built with trapping bounds / shift checks, and every buffer the kernels read ends flush
+against an inaccessible page (emu_guarded), so a kernel bug ends the process that runs it: `run(jobs)` starts
+`python tests/simt_msm_child.py IN OUT` with the pickled jobs, under a time limit, and turns a signal, a time-out or a non-zero exit into a
+pytest failure that names the job.
 
 A job is a dict with "op" and "label"; the result list has one dict per job:
   bases       group, xy (n, 12|24 u64 wire), inf (n u8) or None, [endo], [check]  -> rec, endo (u32 words), nbad
@@ -12,18 +13,13 @@ A job is a dict with "op" and "label"; the result list has one dict per job:
   accumulate  bases, nsplit, sorted, items (m, 3 u32), ctrl (4 u32), max_items, ndest, [bases2_endo]    -> records (ndest, 18 u64 wire)
 Test infrastructure only: the product never imports this file."""
 import ctypes
-import os
-import pickle
-import signal
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-LIB = os.path.join(ROOT, "build", "libemu_msm_test.so")
+import simt_harness
+
+ROOT, CLANG = simt_harness.ROOT, simt_harness.CLANG
+LIB = simt_harness.lib_path("emu_msm_test")
 AFF_WORDS = {1: 32, 2: 64}
 PROJ_WORDS = {1: 44, 2: 84}
 WIRE = {1: 6, 2: 12}                                               # u64 limbs per field element on the wire
@@ -31,53 +27,19 @@ NWIN = {(1, 1): 32, (1, 0): 64, (2, 1): 16, (2, 0): 64}            # msm_seg.hip
 
 
 def build():
-    """build/libemu_msm_test.so, rebuilt when a source is newer (as the other emulation libraries are)"""
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    src = os.path.join(ROOT, "tests", "simt", "emu_msm.cpp")
-    csrc = os.path.join(ROOT, "bls12_381_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "tests", "simt", "hip", "hip_runtime.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        tmp = LIB + ".tmp%d" % os.getpid()
-        subprocess.check_call([CLANG, "-O1", "-std=c++17", "-pthread", "-fPIC", "-shared", "-Wno-unused-value", "-Wno-psabi",
-                               "-fsanitize=bounds,shift", "-fsanitize-trap=all",
-                               "-I" + os.path.join(ROOT, "tests", "simt"), "-I" + csrc, src, "-o", tmp])
-        os.replace(tmp, LIB)
-    return LIB
+    """build/libemu_msm_test.so, rebuilt when a source is newer"""
+    return simt_harness.build("emu_msm_test", "emu_msm.cpp")
 
 
 def run(jobs, timeout=300):
     """the jobs in a fresh child process; returns their results or fails the calling test"""
-    import pytest
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in.pkl"), os.path.join(d, "out.pkl")
-        with open(fin, "wb") as fh:
-            pickle.dump(jobs, fh)
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=True)
-        except subprocess.TimeoutExpired as e:
-            err = e.stderr if isinstance(e.stderr, str) else (e.stderr or b"").decode()
-            pytest.fail("the emulation did not finish in %d s (a lane waiting for a partner that never comes?); last job: %s" % (timeout, _last_job(err)))
-        if p.returncode != 0:
-            what = "signal %s" % signal.Signals(-p.returncode).name if p.returncode < 0 else "exit status %d" % p.returncode
-            hint = {"SIGILL": " (a trapping bounds / shift check)", "SIGTRAP": " (a trapping bounds / shift check)",
-                    "SIGSEGV": " (an access outside a guarded buffer)"}.get(what.split()[-1], "")
-            pytest.fail("the emulation child ended with %s%s in job: %s\n%s" % (what, hint, _last_job(p.stderr), p.stderr[-2000:]))
-        with open(fout, "rb") as fh:
-            return pickle.load(fh)
-
-
-def _last_job(err):
-    marks = [l for l in (err or "").splitlines() if l.startswith("JOB ")]
-    return marks[-1][4:] if marks else "(none started)"
+    return simt_harness.run(__file__, jobs, timeout, stuck="a lane waiting for a partner that never comes?")
 
 
 # ---- child side --------------------------------------------------------------------------------------------------------------
-class _Child:
+class _Child(simt_harness.Child):
     def __init__(self):
-        self.lib = ctypes.CDLL(LIB)
-        self.lib.emu_guarded.restype = ctypes.c_void_p
-        self.lib.emu_guarded.argtypes = [ctypes.c_size_t]
-        self.results = []
+        super().__init__(LIB)
 
     def guarded(self, a):
         """a copy of the array that ends flush against an inaccessible page; returns its address (None for None)"""
@@ -165,17 +127,5 @@ class _Child:
         return {"records": wire.copy().view(np.uint64).reshape(ndest, 18)}
 
 
-def _main(fin, fout):
-    with open(fin, "rb") as fh:
-        jobs = pickle.load(fh)
-    c = _Child()
-    for i, j in enumerate(jobs):
-        sys.stderr.write("JOB %d %s: %s\n" % (i, j["op"], j.get("label", "")))
-        sys.stderr.flush()
-        c.results.append(getattr(c, j["op"])(j))
-    with open(fout, "wb") as fh:
-        pickle.dump(c.results, fh)
-
-
 if __name__ == "__main__":
-    _main(sys.argv[1], sys.argv[2])
+    _Child.main()

@@ -16,11 +16,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import simt_harness
 from oracle import bls12_381_ref as o
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-LIB = os.path.join(ROOT, "build", "libemu_test.so")
+ROOT = simt_harness.ROOT
 
 
 def fpw(x):
@@ -37,16 +36,8 @@ def vp(a):
 
 @pytest.fixture(scope="module")
 def emu():
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    src = os.path.join(ROOT, "tests", "simt", "emu_pairing.cpp")
-    csrc = os.path.join(ROOT, "bls12_381_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "tests", "simt", "hip", "hip_runtime.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call([CLANG, "-O1", "-std=c++17", "-pthread", "-fPIC", "-shared", "-Wno-unused-value", "-Wno-psabi", "-DEMU_WITH_QUAD",
-                               "-I" + os.path.join(ROOT, "tests", "simt"), "-I" + csrc, src, "-o", LIB])
-    return ctypes.CDLL(LIB)
+    # no trapping checks: the library is loaded into this process
+    return ctypes.CDLL(simt_harness.emu_lib(lambda: simt_harness.build("emu_test", "emu_pairing.cpp", defines=["EMU_WITH_QUAD"], sanitize=False)))
 
 
 def _pairs(seed, n):
@@ -126,16 +117,8 @@ def test_emulated_quad_tower_ops_match_oracle(emu):
 def test_emulated_wide_kernel_matches_oracle():
     """wide.hip.h (one pairing per 1024-lane workgroup) interpreting the generated programs, 1024 host threads as lanes: the raw
     Miller value, the pairing and the final exponentiation alone, bit for bit against the oracle"""
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    lib_path = os.path.join(ROOT, "build", "libemu_wide_test.so")
+    lib_path = simt_harness.emu_lib(lambda: simt_harness.build("emu_wide_test", "emu_pairing.cpp", defines=["EMU_WITH_WIDE", "EMU_LANES=1024"], sanitize=False))
     prog_path = os.path.join(ROOT, "build", "wide_prog_emu.bin")
-    src = os.path.join(ROOT, "tests", "simt", "emu_pairing.cpp")
-    csrc = os.path.join(ROOT, "bls12_381_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "tests", "simt", "hip", "hip_runtime.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(lib_path) or os.path.getmtime(lib_path) < max(os.path.getmtime(d) for d in deps):          # rebuilt only when a source changed
-        subprocess.check_call([CLANG, "-O1", "-std=c++17", "-pthread", "-fPIC", "-shared", "-Wno-unused-value", "-Wno-psabi", "-DEMU_WITH_WIDE", "-DEMU_LANES=1024",
-                               "-I" + os.path.join(ROOT, "tests", "simt"), "-I" + csrc, src, "-o", lib_path])
     gen = os.path.join(ROOT, "tools", "gen_wide_prog.py")
     gdeps = [gen]
     if not os.path.exists(prog_path) or os.path.getmtime(prog_path) < max(os.path.getmtime(d) for d in gdeps):

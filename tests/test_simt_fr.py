@@ -22,12 +22,12 @@ That the tests bite was checked by seeding faults into fr.hip.h / fr_plan.h one 
     (test_coset_inverse and test_coset_round_trip cover the same).
 
 Run time on an 8-core machine: 29 s, about 10 s of them the build of the library (tests/test_simt_msm.py: about 200 s)."""
-import os
 
 import numpy as np
 import pytest
 
 import simt_fr_child as child
+import simt_harness
 from oracle import bls12_381_ref as o
 
 RR = o.R_ORDER
@@ -41,9 +41,7 @@ K_LARGE = [1, 2, 3]
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
-    return child.build()
+    return simt_harness.emu_lib(child.build)
 
 
 def _words(vals):

@@ -21,12 +21,12 @@ That the tests bite was checked by seeding faults into fr_bary.hip.h one at a ti
   * the bit reversal applied to the wrong width (`64 - log_n - 1` in frb_exp): every BITREV case of test_every_size differs;
   * the hit element's slot not skipped by the quotient pass (`hit` compared without the + 1 in k_frb_quot): test_point_in_the_domain
     differs in the row-over-tiles shape."""
-import os
 
 import numpy as np
 import pytest
 
 import simt_fr_bary_child as child
+import simt_harness
 import fr_bary_ref as ref
 from oracle import bls12_381_ref as o
 
@@ -37,9 +37,7 @@ SMALL = [(64, 2), (128, 2)]
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
-    return child.build()
+    return simt_harness.emu_lib(child.build)
 
 
 def _rand_rows(k, n, seed):

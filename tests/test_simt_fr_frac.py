@@ -25,13 +25,13 @@ That the tests bite was checked by seeding faults into fr_frac.hip.h one at a ti
     kernel reads the poison between the tables); every packed case still passes.
 
 Run time on an 8-core machine: about a minute, 10 s of it the build of the library."""
-import os
 
 import numpy as np
 import pytest
 
 import fr_frac_ref as ref
 import simt_fr_frac_child as child
+import simt_harness
 from oracle import bls12_381_ref as o
 
 RR = ref.RR
@@ -42,9 +42,7 @@ SPECIAL = (0, 1, RR - 1)
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
-    return child.build()
+    return simt_harness.emu_lib(child.build)
 
 
 def _set(c, k, n, rng, special=True):

@@ -24,12 +24,12 @@ That the tests bite was checked by seeding faults one at a time (each was confir
   * the finish kernel reading one record too few (`i + 1 < n_rec`): the evaluations differ wherever there is more than one tile.
 
 Run time on an 8-core machine: about 30 s, 10 s of it the build of the library."""
-import os
 
 import numpy as np
 import pytest
 
 import simt_fr_mle_child as child
+import simt_harness
 from oracle import bls12_381_ref as o
 
 RR = o.R_ORDER
@@ -41,9 +41,7 @@ SENT = child.SENTINEL
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
-    return child.build()
+    return simt_harness.emu_lib(child.build)
 
 
 # ---- Python integers: the definitions ------------------------------------------------------------------------------------------------

@@ -23,12 +23,12 @@ That the tests bite was checked by seeding faults one at a time (each was confir
     instances at t = 3 pass;
   * a Merkle level written where the level below lies (the plan's dst_off taken from the previous level): test_merkle_binary,
     test_merkle_arities, test_merkle_one_leaf_changes_its_path and test_shipped_shape differ."""
-import os
 
 import numpy as np
 import pytest
 
 import simt_fr_poseidon_child as child
+import simt_harness
 import fr_poseidon_ref as ref
 from bls12_381_amd import synthetic
 
@@ -51,9 +51,7 @@ def params(t, rf, rp, seed=1):
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
-    return child.build()
+    return simt_harness.emu_lib(child.build)
 
 
 def rand(n, seed):

@@ -22,12 +22,12 @@ That the tests bite was checked by seeding faults into fr_scan.hip.h one at a ti
   * the tile guard removed (`cnt = tile` in k_frs_tile): the child of test_lengths_at_every_boundary ends outside a guarded buffer.
 
 Run time on an 8-core machine: about 55 s, 10 s of them the build of the library."""
-import os
 
 import numpy as np
 import pytest
 
 import simt_fr_scan_child as child
+import simt_harness
 from oracle import bls12_381_ref as o
 
 RR = o.R_ORDER
@@ -38,9 +38,7 @@ SHAPES = [(128, 2), (64, 3), child.SHIPPED]
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
-    return child.build()
+    return simt_harness.emu_lib(child.build)
 
 
 def _words(vals):

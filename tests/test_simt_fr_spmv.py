@@ -22,12 +22,12 @@ That the tests bite was checked by seeding faults one at a time (each was confir
   * the fix-up stopping one tile early (`u < t_end` in k_frsp_fixup): every product test fails.
 
 Run time on an 8-core machine: about 15 s, 5 s of them the build of the library."""
-import os
 
 import numpy as np
 import pytest
 
 import simt_fr_spmv_child as child
+import simt_harness
 from oracle import bls12_381_ref as o
 
 RR = o.R_ORDER
@@ -38,9 +38,7 @@ FILL, TILE, FIXUP = child.K_FILL, child.K_TILE, child.K_FIXUP
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
-    return child.build()
+    return simt_harness.emu_lib(child.build)
 
 
 def _words(vals):

@@ -26,12 +26,12 @@ That the tests bite was checked by seeding faults into gntt.hip.h one at a time 
 Run time on an 8-core machine: 5 to 8 minutes.  A minute is the build of the library and about a minute and a half the oracle's side of
 the naive case list (its n^2 products per vector are cached per point); the rest is the emulation itself, most of it the G2 sizes
 of the discrete-log identity, whose lane-pair and team shapes run one host thread per lane."""
-import os
 
 import numpy as np
 import pytest
 
 import simt_gntt_child as child
+import simt_harness
 from g_ntt_points import G, RR, dlog_expect, naive, scalars
 
 LANE_MAX, TEAM_MAX = 0, 1 << 40                                    # BLSGPU_GNTT_TEAM_MAX values that force a shape
@@ -39,9 +39,7 @@ LANE_MAX, TEAM_MAX = 0, 1 << 40                                    # BLSGPU_GNTT
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
-    return child.build()
+    return simt_harness.emu_lib(child.build)
 
 
 def _job(g, vecs, inverse=False, team_max=LANE_MAX, label=""):

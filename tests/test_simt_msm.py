@@ -23,13 +23,13 @@ reaches lane b = 0, the one that stores: no output can differ; `(b & (4 * d - 1)
 Cost on an 8-core machine, emulation libraries built from scratch in both runs: `pytest tests -q -m "not gpu"` took 206 s before this
 file existed and 408 s with it (this file alone about 200 s, 21 s of them the build of the library; three quarters of the rest are the
 two G2 configurations).  The counts below are sized for that: cut counts, G2 plain first, never a class of cases."""
-import os
 
 import numpy as np
 import pytest
 
 import decomp_model
 import simt_msm_child as child
+import simt_harness
 from msm_edge_values import boundary_values, carry_values
 from oracle import bls12_381_ref as o
 from oracle import c_oracle
@@ -47,10 +47,9 @@ LAMBDA = decomp_model.L
 
 @pytest.fixture(scope="module", autouse=True)
 def emu_lib():
-    if not os.path.exists(child.CLANG):
-        pytest.skip("no host clang++ in this image")
+    lib = simt_harness.emu_lib(child.build)
     c_oracle.build()
-    return child.build()
+    return lib
 
 
 # ---- points and scalars ------------------------------------------------------------------------------------------------------------
