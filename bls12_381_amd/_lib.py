@@ -102,6 +102,15 @@ SIGNATURES = {
     "blsgpu_fr_sumcheck_round": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "blsgpu_fr_sumcheck_finish": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "blsgpu_fr_sumcheck_free": (None, [c_vp]),
+    "blsgpu_fr_expr_create": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_sz, c_vp, ctypes.POINTER(c_vp)]),
+    "blsgpu_fr_expr_cols": (c_int, [c_vp]),
+    "blsgpu_fr_expr_regs": (c_int, [c_vp]),
+    "blsgpu_fr_expr_instructions": (c_sz, [c_vp]),
+    "blsgpu_fr_expr_products": (c_sz, [c_vp]),
+    "blsgpu_fr_expr_cols_read": (ctypes.c_uint32, [c_vp]),
+    "blsgpu_fr_expr_free": (None, [c_vp]),
+    "blsgpu_fr_expr_eval": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "blsgpu_fr_expr_eval_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "blsgpu_fr_poseidon_create": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)]),
     "blsgpu_fr_poseidon_width": (c_int, [c_vp]),
     "blsgpu_fr_poseidon_rounds_full": (c_int, [c_vp]),

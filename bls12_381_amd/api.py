@@ -66,6 +66,8 @@ FR_SCAN_SUM, FR_SCAN_PRODUCT, FR_SCAN_HORNER = 0, 1, 2      # include/bls12_381_
 FR_FRAC_MAX_COLS, FR_FRAC_TILE = 8, 1024                   # include/bls12_381_hip.h: BLSGPU_FR_FRAC_*
 FR_ORDER_NATURAL, FR_ORDER_BITREV = 0, 1                    # include/bls12_381_hip.h: BLSGPU_FR_ORDER_*
 FR_POSEIDON_AUTO, FR_POSEIDON_DENSE, FR_POSEIDON_SPARSE = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_POSEIDON_*
+FR_EXPR_ADD, FR_EXPR_SUB, FR_EXPR_MUL, FR_EXPR_MAD, FR_EXPR_MOV = 0, 1, 2, 3, 4      # include/bls12_381_hip.h: BLSGPU_FR_EXPR_*
+FR_EXPR_MAX_COLS, FR_EXPR_MAX_REGS, FR_EXPR_MAX_CONSTS, FR_EXPR_MAX_INSTR = 32, 8, 32, 256
 FR_GENERATOR = 7                          # scalar.rs:99-105 GENERATOR (`MULTIPLICATIVE_GENERATOR` :708): the usual coset shift
 
 
@@ -220,6 +222,122 @@ def _fr_limbs(values, shape, what):
     if all(isinstance(x, (int, np.integer)) for x in flat):
         return _point_limbs(flat, len(flat), what).reshape(tuple(shape) + (4,))
     return _u64(np.array(values, dtype=np.uint64), tuple(shape) + (4,)).copy()
+
+
+_FR_EXPR_OPS = {"ADD": FR_EXPR_ADD, "SUB": FR_EXPR_SUB, "MUL": FR_EXPR_MUL, "MAD": FR_EXPR_MAD, "MOV": FR_EXPR_MOV}
+
+
+def fr_expr_operand(x):
+    """an operand word of an expression program (BLSGPU_FR_EXPR_REG / _COL / _CONST): a bare int or ("reg", i) is register i,
+    ("col", j) or ("col", j, rot) column j rotated by rot rows (a signed 16-bit integer), ("const", i) constant i"""
+    if isinstance(x, (int, np.integer)):
+        x = ("reg", int(x))
+    kind = str(x[0]).lower()
+    idx = int(x[1])
+    if not 0 <= idx <= 0xFF:
+        raise ValueError("fr_expr: an operand index must be in [0, 255]")
+    if kind == "reg" and len(x) == 2:
+        return idx
+    if kind == "col" and len(x) in (2, 3):
+        rot = int(x[2]) if len(x) == 3 else 0
+        if not -32768 <= rot <= 32767:
+            raise ValueError("fr_expr: a rotation must fit a signed 16-bit integer")
+        return 0x40000000 | ((rot & 0xFFFF) << 8) | idx
+    if kind == "const" and len(x) == 2:
+        return 0x80000000 | idx
+    raise ValueError("fr_expr: an operand is a register number, (\"reg\", i), (\"col\", j[, rot]) or (\"const\", i)")
+
+
+def fr_expr_assemble(instrs):
+    """tuples like ("MAD", 2, ("col", 3, +1), ("const", 0)) -- (op, dst register, a, b), MOV without b -- -> the (n_instr, 3) u32 code words of
+    blsgpu_fr_expr_create.  Only the FORMAT is handled here: the rules (ranges, read-before-write) are checked by the library."""
+    code = np.zeros((len(instrs), 3), dtype=np.uint32)
+    for i, ins in enumerate(instrs):
+        op = _FR_EXPR_OPS.get(str(ins[0]).upper()) if not isinstance(ins[0], (int, np.integer)) else int(ins[0])
+        if op is None or len(ins) not in (3, 4) or (len(ins) == 3 and op != FR_EXPR_MOV):
+            raise ValueError("fr_expr: instruction %d must be (op, dst, a, b) with op in ADD / SUB / MUL / MAD, or (\"MOV\", dst, a)" % i)
+        dst = int(ins[1])
+        if not (0 <= op <= 0xFF and 0 <= dst <= 0xFF):
+            raise ValueError("fr_expr: instruction %d: op and dst must be in [0, 255]" % i)
+        code[i] = (op | (dst << 8), fr_expr_operand(ins[2]), fr_expr_operand(ins[3]) if len(ins) == 4 else 0)
+    return code
+
+
+class FrExpr:
+    """An Fr expression program resident on the device (`blsgpu_fr_expr`): a straight-line program over columns, registers and constants,
+    validated once by Context.fr_expr and evaluated per row in one pass (include/bls12_381_hip.h)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def _get(self, fn):
+        return int(fn(self.handle)) if self.handle else 0
+
+    @property
+    def cols(self):
+        return self._get(self.ctx.lib.blsgpu_fr_expr_cols)
+
+    @property
+    def regs(self):
+        return self._get(self.ctx.lib.blsgpu_fr_expr_regs)
+
+    @property
+    def instructions(self):
+        return self._get(self.ctx.lib.blsgpu_fr_expr_instructions)
+
+    @property
+    def products_per_row(self):
+        return self._get(self.ctx.lib.blsgpu_fr_expr_products)
+
+    @property
+    def cols_read(self):
+        """bit j: some instruction reads column j"""
+        return self._get(self.ctx.lib.blsgpu_fr_expr_cols_read)
+
+    def _lens(self, col_log_len):
+        if col_log_len is None:
+            return None
+        ll = np.ascontiguousarray(col_log_len, dtype=np.uint8).reshape(-1)
+        if ll.shape[0] != self.cols:
+            raise ValueError("fr_expr.eval: col_log_len needs one entry per column")
+        return ll
+
+    def eval(self, cols, log_n, log_stride=0, col_log_len=None):
+        """cols: one entry per column -- an (len, 4) u64 array of Montgomery limbs, a list of Python ints in [0, r), or None for a column
+        the program does not read; column j has 2^col_log_len[j] scalars (None: every column has 2^log_n).  Entries that are the SAME
+        array object reach the device as one buffer.  Returns the (2^log_n, 4) result."""
+        if len(cols) != self.cols:
+            raise ValueError("fr_expr.eval: expected %d columns" % self.cols)
+        ll = self._lens(col_log_len)
+        keep, ptrs = {}, (ctypes.c_void_p * len(cols))()
+        for j, c in enumerate(cols):
+            if c is None:
+                continue
+            if id(c) not in keep:
+                keep[id(c)] = _fr_limbs(c, (1 << (int(ll[j]) if ll is not None else log_n),), "fr_expr.eval column %d" % j)
+            ptrs[j] = keep[id(c)].ctypes.data
+        out = np.zeros((1 << log_n, 4), dtype=np.uint64)
+        check(self.ctx.lib.blsgpu_fr_expr_eval(self.ctx.h, self.handle, ptrs, _ptr(ll), int(log_n), int(log_stride), _ptr(out)), "fr_expr_eval")
+        return out
+
+    def eval_device(self, d_cols, log_n, d_out, log_stride=0, col_log_len=None):
+        """the same on columns in device memory: d_cols is one device pointer (an int or None) per column; asynchronous on the context's
+        stream, no scratch"""
+        if len(d_cols) != self.cols:
+            raise ValueError("fr_expr.eval_device: expected %d columns" % self.cols)
+        ptrs = (ctypes.c_void_p * len(d_cols))(*[None if p is None else int(p) for p in d_cols])
+        check(self.ctx.lib.blsgpu_fr_expr_eval_device(self.ctx.h, self.handle, ptrs, _ptr(self._lens(col_log_len)), int(log_n), int(log_stride), d_out), "fr_expr_eval_device")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_fr_expr_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FrPoseidon:
@@ -1012,6 +1130,19 @@ class Context:
         h = ctypes.c_void_p()
         check(self.lib.blsgpu_fr_poseidon_create(self.h, t, r_full, r_partial, _ptr(rc), _ptr(mm), int(form), ctypes.byref(h)), "fr_poseidon")
         return FrPoseidon(self, h)
+
+    def fr_expr(self, n_cols, n_regs, consts, instrs):
+        """an expression program made resident (include/bls12_381_hip.h: blsgpu_fr_expr_create): n_cols columns, n_regs registers, consts
+        as Python ints in [0, r) or an (n, 4) array of Montgomery limbs (None or empty: none), instrs either tuples for fr_expr_assemble
+        or an (n_instr, 3) u32 array of code words.  The program is validated here, once; a bad one raises with the instruction index
+        and the rule.  Returns an FrExpr (.eval, .eval_device, .close())."""
+        code = np.ascontiguousarray(instrs, dtype=np.uint32).reshape(-1, 3) if isinstance(instrs, np.ndarray) else fr_expr_assemble(list(instrs))
+        cs = None
+        if consts is not None and len(consts):
+            cs = _fr_limbs(consts, (-1,), "fr_expr consts")
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_expr_create(self.h, int(n_cols), int(n_regs), 0 if cs is None else cs.shape[0], _ptr(cs), code.shape[0], _ptr(code), ctypes.byref(h)), "fr_expr")
+        return FrExpr(self, h)
 
     def fr_matrix(self, row_ptr, col, val, n_cols):
         """a CSR matrix made resident (include/bls12_381_hip.h: blsgpu_fr_matrix_upload): row_ptr has n_rows + 1 entries from 0 to

@@ -9,6 +9,7 @@
 #include "fr_spmv.hip.h"
 #include "fr_mle.hip.h"
 #include "fr_poseidon.hip.h"
+#include "fr_expr.hip.h"
 #include "h2c.hip.h"
 #include "expand_kernels.hip.h"
 #include "codec.hip.h"
@@ -1142,6 +1143,95 @@ extern "C" int blsgpu_fr_poseidon_merkle(blsgpu_ctx* c, const blsgpu_fr_poseidon
   void* dr = h.out(c->io_out, roots, k * 32);
   if (h.rc) return h.rc;
   return h.finish(frp_merkle_device(c, p, tag, dl, height, k, dn, dr));
+}
+
+// ---- expression programs: gate and quotient columns in one pass (fr_expr.hip.h; fr_expr_plan.h validates, builds the image and plans) ------
+extern "C" int blsgpu_fr_expr_create(blsgpu_ctx* c, int n_cols, int n_regs, int n_consts, const uint64_t* consts, size_t n_instr, const uint32_t* code, blsgpu_fr_expr** out) { CTX_CLAIM(c);
+  if (out) *out = nullptr;
+  if (!c || !out) return bad("fr_expr: NULL context / out");
+  FrxProg prog; FrxInfo info;
+  if (const char* what = frx_prog_build(n_cols, n_regs, n_consts, consts, n_instr, code, &prog, &info)) return bad(what);
+  HIPCHK(hipSetDevice(c->device));
+  blsgpu_fr_expr* e = new blsgpu_fr_expr();
+  e->device = c->device; e->info = info;
+  hipError_t err = hipMalloc((void**)&e->image, sizeof(FrxProg));
+  if (err == hipSuccess) err = hipMemcpy(e->image, prog.w, sizeof(FrxProg), hipMemcpyHostToDevice);
+  if (err != hipSuccess) { if (e->image) hipFree(e->image); delete e; return fail("fr_expr: upload of the program image", err, __LINE__); }
+  *out = e;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_expr_cols(const blsgpu_fr_expr* e) { return e ? e->info.n_cols : 0; }
+extern "C" int blsgpu_fr_expr_regs(const blsgpu_fr_expr* e) { return e ? e->info.n_regs : 0; }
+extern "C" size_t blsgpu_fr_expr_instructions(const blsgpu_fr_expr* e) { return e ? e->info.n_instr : 0; }
+extern "C" size_t blsgpu_fr_expr_products(const blsgpu_fr_expr* e) { return e ? e->info.products : 0; }
+extern "C" uint32_t blsgpu_fr_expr_cols_read(const blsgpu_fr_expr* e) { return e ? e->info.cols_read : 0; }
+extern "C" void blsgpu_fr_expr_free(blsgpu_fr_expr* e) {
+  if (!e) return;
+  hipSetDevice(e->device);
+  hipDeviceSynchronize();                  // an asynchronous evaluation may still be reading the image
+  if (e->image) hipFree(e->image);
+  delete e;
+}
+// every argument check of both forms, before anything is staged or launched; fills the kernel's column argument from the columns the
+// program reads (the others stay NULL / 0: the kernel never looks at them)
+static int fr_expr_check(blsgpu_ctx* c, const blsgpu_fr_expr* e, const void* const* cols, const uint8_t* col_log_len, int log_n, int log_stride, const void* out, bool device, FrxCols* k) {
+  if (!c) return bad("fr_expr_eval: NULL context");
+  if (!e) return bad("fr_expr_eval: NULL handle");
+  if (e->device != c->device) return bad("fr_expr_eval: the handle lives on another device than the context");
+  if (!cols || !out) return bad("fr_expr_eval: NULL cols / out");
+  if (log_n < 0 || log_n > FRX_MAX_LOG_N) return bad("fr_expr_eval: log_n must be in [0, 28]");
+  if (log_stride < 0 || log_stride > log_n) return bad("fr_expr_eval: log_stride must be in [0, log_n]");
+  if (device && ((uintptr_t)out & 15)) return bad("fr_expr_eval: device pointers must be 16-byte aligned");
+  for (int j = 0; j < FRX_MAX_COLS; j++) { k->p[j] = nullptr; k->log_len[j] = 0; }
+  const size_t out_bytes = (size_t)32 << log_n;
+  for (int j = 0; j < e->info.n_cols; j++) {
+    if (!((e->info.cols_read >> j) & 1u)) continue;
+    const int ll = col_log_len ? (int)col_log_len[j] : log_n;
+    if (ll > log_n) return bad("fr_expr_eval: a column is longer than 2^log_n (col_log_len[j] must not exceed log_n)");
+    if (!cols[j]) return bad("fr_expr_eval: NULL pointer of a column the program reads");
+    if (device && ((uintptr_t)cols[j] & 15)) return bad("fr_expr_eval: device pointers must be 16-byte aligned");
+    if (frb_overlap(out, out_bytes, cols[j], (size_t)32 << ll)) return bad("fr_expr_eval: out overlaps a column the program reads (there is no in-place form)");
+    k->p[j] = (const uint32_t*)cols[j]; k->log_len[j] = (uint32_t)ll;
+  }
+  return BLSGPU_OK;
+}
+static int fr_expr_launch(blsgpu_ctx* c, const blsgpu_fr_expr* e, const FrxCols& k, int log_n, int log_stride, void* d_out) {
+  HIPCHK(hipSetDevice(c->device));
+  const FrExprPlan plan = fr_expr_plan(log_n, e->info.n_regs);
+  if (!plan.ok) return bad("fr_expr_eval: log_n is out of range");
+  KLAUNCH(k_frx_eval, dim3(plan.grid), dim3(plan.block), plan.lds, c->stream, (const u32*)e->image, k, log_n, log_stride, plan.chunk, (u32*)d_out);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_expr_eval_device(blsgpu_ctx* c, const blsgpu_fr_expr* e, const void* const* d_cols, const uint8_t* col_log_len, int log_n, int log_stride, void* d_out) { CTX_CLAIM(c);
+  FrxCols k;
+  if (int rc = fr_expr_check(c, e, d_cols, col_log_len, log_n, log_stride, d_out, true, &k)) return rc;
+  return fr_expr_launch(c, e, k, log_n, log_stride, d_out);
+}
+// the columns the program reads are staged end to end in ONE buffer (each a multiple of 32 bytes, so every one stays 16-byte aligned); a
+// host pointer passed for several columns of one length is staged once, so the device sees the alias too
+extern "C" int blsgpu_fr_expr_eval(blsgpu_ctx* c, const blsgpu_fr_expr* e, const uint64_t* const* cols, const uint8_t* col_log_len, int log_n, int log_stride, uint64_t* out) { CTX_CLAIM(c);
+  FrxCols k;
+  if (int rc = fr_expr_check(c, e, (const void* const*)cols, col_log_len, log_n, log_stride, out, false, &k)) return rc;
+  HostCall h(c);
+  size_t off[FRX_MAX_COLS] = {}, total = 0;
+  for (int j = 0; j < e->info.n_cols; j++) {
+    if (!k.p[j]) continue;
+    int same = -1;
+    for (int i = 0; i < j && same < 0; i++) if (k.p[i] == k.p[j] && k.log_len[i] == k.log_len[j]) same = i;
+    if (same >= 0) { off[j] = off[same]; continue; }
+    off[j] = total; total += (size_t)32 << k.log_len[j];
+  }
+  if (!h.reserve(c->io_a, total)) return h.rc;
+  size_t done = 0;
+  for (int j = 0; j < e->info.n_cols && !h.rc; j++) {
+    if (!k.p[j]) continue;
+    if (off[j] == done) { h.rc = staged_upload(c, (char*)c->io_a.p + off[j], k.p[j], (size_t)32 << k.log_len[j]); done += (size_t)32 << k.log_len[j]; }
+  }
+  void* o = h.out(c->io_out, out, (size_t)32 << log_n);
+  if (h.rc) return h.rc;
+  for (int j = 0; j < e->info.n_cols; j++) if (k.p[j]) k.p[j] = (const uint32_t*)((const char*)c->io_a.p + off[j]);
+  return h.finish(fr_expr_launch(c, e, k, log_n, log_stride, o));
 }
 
 // ---- multilinear tables: folds, eq tables, evaluation, sumcheck rounds (fr_mle.hip.h; fr_mle_plan.h decides the launches) -----------------

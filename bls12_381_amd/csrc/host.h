@@ -31,6 +31,7 @@
 #include "limits.h"
 #include "diag.h"
 #include "fr_poseidon_plan.h"
+#include "fr_expr_plan.h"
 
 using namespace bls;
 
@@ -280,6 +281,14 @@ struct blsgpu_fr_poseidon {
   int device = 0; int t = 0, r_full = 0, r_partial = 0, form = 0;
   FrpArgs args = {};
   size_t products = 0;
+  u32* image = nullptr;
+};
+
+// an Fr expression program resident on the device (api_aux.hip: blsgpu_fr_expr_create; fr_expr.hip.h): what the accessors report and
+// the image frx_prog_build made of the validated program (fr_expr_plan.h)
+struct blsgpu_fr_expr {
+  int device = 0;
+  FrxInfo info;
   u32* image = nullptr;
 };
 

@@ -143,3 +143,71 @@ def lookup_instance(n, seed=SEED):
     for i in idx:
         m[i] += 1
     return [t[i] for i in idx], t, m
+
+
+# ---- a vanilla PLONK instance and its quotient expression (blsgpu_fr_expr_*) ---------------------------------------------------------
+# the column map of plonk_quotient_program: full-length columns first, then the periodic one, then the challenges (length 1)
+PLONK_COLS = {name: j for j, name in enumerate(
+    ["a", "b", "c", "qL", "qR", "qO", "qM", "qC", "s1", "s2", "s3", "z", "X", "L1", "zh_inv", "beta", "gamma", "alpha", "alpha2"])}
+PLONK_K = (1, 7, 49)                      # the coset labels of the three wire columns: id_j = k_j X (permutation_with_copy_cycles)
+
+
+def plonk_instance(log_n, seed=SEED):
+    """a seeded SATISFYING vanilla-PLONK instance on the domain of n = 2^log_n rows, as a dict of lists of n Python ints in [0, r):
+    wires a, b, c with copy constraints (permutation_with_copy_cycles), their sigma columns s1, s2, s3 (labels k_j w^i, k = PLONK_K),
+    seeded selectors qL, qR, qO, qM and the qC that satisfies  qL a + qR b + qO c + qM a b + qC = 0  in every row, and the permutation
+    accumulator z (z[0] = 1, z[i + 1] = z[i] prod_j (w_j + beta k_j w^i + gamma) / (w_j + beta s_j + gamma)[i], closing at z[n] = 1);
+    "beta", "gamma", "alpha" are ints."""
+    n = 1 << log_n
+    (a, b, c), ident, (s1, s2, s3) = permutation_with_copy_cycles(3, log_n, seed)
+    sel = to_ints(scalars(4 * n + 3, seed ^ 0x5E1EC7))
+    qL, qR, qO, qM = (sel[i * n:(i + 1) * n] for i in range(4))
+    beta, gamma, alpha = sel[4 * n:]
+    qC = [-(qL[i] * a[i] + qR[i] * b[i] + qO[i] * c[i] + qM[i] * a[i] * b[i]) % R_ORDER for i in range(n)]
+    z, acc = [], 1
+    for i in range(n):
+        z.append(acc)
+        num = den = 1
+        for w, idc, sg in ((a, ident[0], s1), (b, ident[1], s2), (c, ident[2], s3)):
+            num = num * (w[i] + beta * idc[i] + gamma) % R_ORDER
+            den = den * (w[i] + beta * sg[i] + gamma) % R_ORDER
+        acc = acc * num % R_ORDER * pow(den, R_ORDER - 2, R_ORDER) % R_ORDER
+    assert acc == 1, "the permutation product does not close"
+    return {"a": a, "b": b, "c": c, "qL": qL, "qR": qR, "qO": qO, "qM": qM, "qC": qC, "s1": s1, "s2": s2, "s3": s3, "z": z,
+            "beta": beta, "gamma": gamma, "alpha": alpha}
+
+
+def plonk_quotient_program():
+    """the standard program over PLONK_COLS:
+        (qL a + qR b + qO c + qM a b + qC  +  alpha perm  +  alpha^2 (z - 1) L1) * zh_inv
+        perm = z prod_j (w_j + beta k_j X + gamma)  -  z(next row) prod_j (w_j + beta s_j + gamma)
+    Returns (n_cols, n_regs, consts, instrs) for Context.fr_expr: constants (k_1, k_2, 1) = (7, 49, 1) as ints, instructions as
+    tuples for fr_expr_assemble.  21 field products per row; the next row is rotation +1 (times 2^log_stride on an extended domain)."""
+    C = lambda name, rot=0: ("col", PLONK_COLS[name], rot)
+    K1, K2, ONE = ("const", 0), ("const", 1), ("const", 2)
+    ins = [("MUL", 0, C("qL"), C("a")), ("MAD", 0, C("qR"), C("b")), ("MAD", 0, C("qO"), C("c")), ("MUL", 1, C("qM"), C("a")), ("MAD", 0, 1, C("b")),
+           ("ADD", 0, 0, C("qC")),
+           ("MUL", 1, C("beta"), C("X")),
+           ("ADD", 2, C("a"), C("gamma")), ("ADD", 2, 2, 1),
+           ("MUL", 3, 1, K1), ("ADD", 3, 3, C("b")), ("ADD", 3, 3, C("gamma")), ("MUL", 2, 2, 3),
+           ("MUL", 3, 1, K2), ("ADD", 3, 3, C("c")), ("ADD", 3, 3, C("gamma")), ("MUL", 2, 2, 3),
+           ("MUL", 2, 2, C("z")),
+           ("MUL", 3, C("beta"), C("s1")), ("ADD", 3, 3, C("a")), ("ADD", 3, 3, C("gamma")),
+           ("MUL", 4, C("beta"), C("s2")), ("ADD", 4, 4, C("b")), ("ADD", 4, 4, C("gamma")), ("MUL", 3, 3, 4),
+           ("MUL", 4, C("beta"), C("s3")), ("ADD", 4, 4, C("c")), ("ADD", 4, 4, C("gamma")), ("MUL", 3, 3, 4),
+           ("MUL", 3, 3, C("z", 1)),
+           ("SUB", 2, 2, 3),
+           ("MAD", 0, C("alpha"), 2),
+           ("SUB", 1, C("z"), ONE), ("MUL", 1, 1, C("L1")),
+           ("MAD", 0, C("alpha2"), 1),
+           ("MUL", 0, 0, C("zh_inv"))]
+    return len(PLONK_COLS), 5, [PLONK_K[1], PLONK_K[2], 1], ins
+
+
+def plonk_col_log_len(log_n, log_stride):
+    """col_log_len of the PLONK_COLS map on an extended domain of 2^log_n rows: zh_inv has 2^log_stride values, the challenges one"""
+    ll = [log_n] * len(PLONK_COLS)
+    ll[PLONK_COLS["zh_inv"]] = log_stride
+    for name in ("beta", "gamma", "alpha", "alpha2"):
+        ll[PLONK_COLS[name]] = 0
+    return ll

@@ -505,6 +505,59 @@ class FrPoseidon {
  private:
   blsgpu_fr_poseidon* p_ = nullptr;
 };
+// An Fr expression program resident on the device (blsgpu_fr_expr; include/bls12_381_hip.h documents the format): straight-line code
+// over columns, registers and constants, validated once by the constructor (a bad program throws with the instruction index and the
+// rule), evaluated per row in one pass by eval().  Build the code with the static helpers:
+//   FrExpr::Code code; code.mul(0, FrExpr::col(0), FrExpr::col(1)); code.mad(0, FrExpr::col(2, +1), FrExpr::constant(0)); ...
+// The row's result is the dst of the last instruction.  eval: cols[j] holds 2^col_log_len[j] scalars (col_log_len empty: every column
+// has N = 2^log_n), read modulo its own length at (row + rot * 2^log_stride); a column the program does not read may be left empty.
+// The domain point X and L_1 are columns, not operands: the coset transforms of (0, 1, 0, ...) and of (1/n, ..., 1/n, 0, ..., 0).
+class FrExpr {
+ public:
+  static uint32_t reg(unsigned i) { return BLSGPU_FR_EXPR_REG(i); }
+  static uint32_t col(unsigned j, int rot = 0) { return BLSGPU_FR_EXPR_COL(j, rot); }
+  static uint32_t constant(unsigned i) { return BLSGPU_FR_EXPR_CONST(i); }
+  struct Code {
+    std::vector<uint32_t> words;
+    Code& add(unsigned dst, uint32_t a, uint32_t b) { return push(BLSGPU_FR_EXPR_ADD, dst, a, b); }
+    Code& sub(unsigned dst, uint32_t a, uint32_t b) { return push(BLSGPU_FR_EXPR_SUB, dst, a, b); }
+    Code& mul(unsigned dst, uint32_t a, uint32_t b) { return push(BLSGPU_FR_EXPR_MUL, dst, a, b); }
+    Code& mad(unsigned dst, uint32_t a, uint32_t b) { return push(BLSGPU_FR_EXPR_MAD, dst, a, b); }
+    Code& mov(unsigned dst, uint32_t a) { return push(BLSGPU_FR_EXPR_MOV, dst, a, 0); }
+    Code& push(unsigned op, unsigned dst, uint32_t a, uint32_t b) { words.push_back(BLSGPU_FR_EXPR_INSTR(op, dst)); words.push_back(a); words.push_back(b); return *this; }
+  };
+  FrExpr(int n_cols, int n_regs, const std::vector<FrLimbs>& consts, const Code& code) {
+    check(blsgpu_fr_expr_create(Context::instance().handle(), n_cols, n_regs, (int)consts.size(), consts.empty() ? nullptr : consts[0].data(), code.words.size() / 3,
+                                code.words.data(), &e_), "fr_expr_create");
+  }
+  ~FrExpr() { blsgpu_fr_expr_free(e_); }
+  FrExpr(const FrExpr&) = delete;
+  FrExpr& operator=(const FrExpr&) = delete;
+  FrExpr(FrExpr&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+  int cols() const { return blsgpu_fr_expr_cols(e_); }
+  int regs() const { return blsgpu_fr_expr_regs(e_); }
+  size_t instructions() const { return blsgpu_fr_expr_instructions(e_); }
+  size_t products_per_row() const { return blsgpu_fr_expr_products(e_); }
+  uint32_t cols_read() const { return blsgpu_fr_expr_cols_read(e_); }
+  const blsgpu_fr_expr* handle() const { return e_; }
+  std::vector<FrLimbs> eval(const std::vector<std::vector<FrLimbs>>& columns, int log_n, int log_stride = 0, const std::vector<uint8_t>& col_log_len = {}) const {
+    if (columns.size() != (size_t)cols() || (!col_log_len.empty() && col_log_len.size() != columns.size()))
+      throw std::invalid_argument("FrExpr::eval: one column (and one col_log_len, if any) per column of the program");
+    if (log_n < 0 || log_n > 28) throw std::invalid_argument("FrExpr::eval: log_n must be in [0, 28]");
+    std::vector<const uint64_t*> ptr(columns.size(), nullptr);
+    for (size_t j = 0; j < columns.size(); j++) {
+      if (columns[j].empty()) continue;
+      const int ll = col_log_len.empty() ? log_n : (int)col_log_len[j];
+      if (ll > 28 || columns[j].size() != (size_t)1 << ll) throw std::invalid_argument("FrExpr::eval: a column does not have 2^col_log_len scalars");
+      ptr[j] = columns[j][0].data();
+    }
+    std::vector<FrLimbs> out((size_t)1 << log_n);
+    check(blsgpu_fr_expr_eval(Context::instance().handle(), e_, ptr.data(), col_log_len.empty() ? nullptr : col_log_len.data(), log_n, log_stride, out[0].data()), "fr_expr_eval");
+    return out;
+  }
+ private:
+  blsgpu_fr_expr* e_ = nullptr;
+};
 // Multilinear tables (include/bls12_381_hip.h): k tables of t.size() / k = 2^m scalars each, laid end to end; entry i is the value at the
 // point whose coordinate x_b is bit b of i.  fr_mle_fold binds the top variable at r (k x 2^(m-1) out), fr_eq_table is
 // eq(point)[i] = prod_b (bit b of i ? point[b] : 1 - point[b]), fr_mle_eval gives f_j(point) with point[b] the value of x_b.

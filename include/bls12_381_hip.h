@@ -740,6 +740,70 @@ int blsgpu_fr_poseidon_hash_many(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, c
 int blsgpu_fr_poseidon_hash_many_device(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const void* d_inputs, size_t n, void* d_out);
 int blsgpu_fr_poseidon_merkle(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const uint64_t* leaves, int height, size_t k, uint64_t* nodes, uint64_t* roots);
 int blsgpu_fr_poseidon_merkle_device(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const void* d_leaves, int height, size_t k, void* d_nodes, void* d_roots);
+/* Fr EXPRESSION PROGRAMS: the row-wise evaluation of a constraint expression -- gates, a permutation term with its next-row operand,
+ * boundary terms, all times 1 / Z_H -- over columns resident on the device, in ONE pass: the quotient numerator of a PLONK / halo2-style
+ * prover on the extended coset domain between blsgpu_fr_ntt_many (onto the coset) and blsgpu_fr_ntt_many (back).  The expression is a
+ * small straight-line program over a register file, fixed per circuit: validated once, when the handle is created, and interpreted per
+ * row by one precompiled kernel (there is no runtime compilation).  Every column is read where it is used, every intermediate stays on
+ * the chip, only the result of a row is written.
+ *   program   n_instr instructions of three words in HOST memory, {op | dst << 8, a, b}: BLSGPU_FR_EXPR_INSTR(op, dst), then two operand
+ *             words.  ADD dst = a + b; SUB dst = a - b; MUL dst = a * b; MAD dst = dst + a * b; MOV dst = a (b must be 0).
+ *             An operand is BLSGPU_FR_EXPR_REG(i), i < n_regs; BLSGPU_FR_EXPR_COL(j, rot), j < n_cols, rot a signed 16-bit rotation;
+ *             or BLSGPU_FR_EXPR_CONST(i), i < n_consts (kind in bits 31..30, index in bits 7..0, rot in bits 23..8, every other bit 0).
+ *             The result of a row is the dst of the LAST instruction.
+ *   limits    n_cols in [1, 32], n_regs in [1, 8], n_consts in [0, 32] (canonical Montgomery limbs, four u64 each; consts is NULL
+ *             exactly when there are none), n_instr in [1, 256].
+ *   refused   at create, BLSGPU_ERR_ARG with *out left NULL and blsgpu_last_error naming the instruction index and the rule: an
+ *             unknown op or operand kind, an index out of range, a stray bit, a constant not below r, and a register READ -- as an
+ *             operand or as MAD's dst -- before any instruction wrote it (results never depend on what a register held before).
+ * blsgpu_fr_expr_create uploads the program image (about 4 KB, owned by the handle) and synchronises: a setup call.  The accessors
+ * report the handle's shape; _products is the number of MUL + MAD instructions (field products per row), _cols_read has bit j set when
+ * some instruction reads column j.  blsgpu_fr_expr_free follows the rules of blsgpu_fr_matrix_free (it waits for the device; NULL is
+ * allowed).
+ *
+ * Evaluation: N = 2^log_n rows, log_n in [0, 28].  cols is a HOST array of n_cols pointers (device pointers in the device form, host
+ * pointers in the host form): a parameter like `coset`, the columns come from different allocations.  Column j holds
+ * 2^col_log_len[j] scalars, col_log_len[j] <= log_n (col_log_len == NULL: every column has N), and is read MODULO ITS OWN LENGTH:
+ *   for row i, COL(j, rot) = col_j[(i + rot * 2^log_stride) mod 2^col_log_len[j]]        (64-bit signed arithmetic; log_stride in [0, log_n])
+ * which is three things at once.  Rotations on an extended domain: on N = n * 2^e points the next row of the trace is
+ * w_n = w_N^(2^e), so log_stride = e.  Periodic columns: 1 / Z_H on the coset g <w_N> depends on i mod 2^e only -- a column of length
+ * 2^e (blsgpu_fr_batch_invert of the 2^e values g^n w_N^(n i) - 1).  Challenges on the device: a column of length 1 is one scalar in
+ * device memory (d_challenges of the fraction scans), so a transcript on the device needs no synchronisation.
+ * The domain point X is NOT an operand kind: it is a column, the coset transform (blsgpu_fr_ntt_many, forward, coset = g) of the
+ * coefficient vector (0, 1, 0, ...).  Likewise L_1: the coset transform of the coefficients (1/n, 1/n, ..., 1/n, 0, ..., 0) (n of them,
+ * then zeros up to N), i.e. of the inverse transform of (1, 0, ..., 0) on the trace domain, zero-padded.
+ * The arithmetic is `Scalar`'s add / sub / mul (scalar.rs:414-503).  Inputs are canonical Montgomery limbs (a precondition, not
+ * validated); outputs are canonical, so they are limb-identical to the same expression composed from blsgpu_fr_op, and identical from
+ * run to run.  out is N scalars and must not overlap any column the program reads (checked on the 64-bit ranges: a rotated read would
+ * race); columns may alias each other freely; there is no in-place form.  Pointers and lengths of columns no instruction reads are
+ * ignored (the pointers may be NULL).  Device pointers must be 16-byte aligned.  The device form is asynchronous on the context's
+ * stream, never synchronises and uses no scratch, so it shares nothing with pipelined *_msm_device calls in flight.
+ * BLSGPU_ERR_ARG (nothing staged or launched): a NULL context or handle, a handle created on another device, NULL cols / out or a NULL
+ * pointer of a column that is read, log_n, log_stride or a read column's col_log_len out of range, a misaligned device pointer, out
+ * overlapping a column that is read. */
+typedef struct blsgpu_fr_expr blsgpu_fr_expr;
+#define BLSGPU_FR_EXPR_ADD 0
+#define BLSGPU_FR_EXPR_SUB 1
+#define BLSGPU_FR_EXPR_MUL 2
+#define BLSGPU_FR_EXPR_MAD 3
+#define BLSGPU_FR_EXPR_MOV 4
+#define BLSGPU_FR_EXPR_MAX_COLS   32
+#define BLSGPU_FR_EXPR_MAX_REGS   8
+#define BLSGPU_FR_EXPR_MAX_CONSTS 32
+#define BLSGPU_FR_EXPR_MAX_INSTR  256
+#define BLSGPU_FR_EXPR_REG(i)       ((uint32_t)(i) & 0xffu)
+#define BLSGPU_FR_EXPR_COL(j, rot)  (0x40000000u | (((uint32_t)(rot) & 0xffffu) << 8) | ((uint32_t)(j) & 0xffu))
+#define BLSGPU_FR_EXPR_CONST(i)     (0x80000000u | ((uint32_t)(i) & 0xffu))
+#define BLSGPU_FR_EXPR_INSTR(op, dst) (((uint32_t)(op) & 0xffu) | (((uint32_t)(dst) & 0xffu) << 8))
+int blsgpu_fr_expr_create(blsgpu_ctx* ctx, int n_cols, int n_regs, int n_consts, const uint64_t* consts, size_t n_instr, const uint32_t* code, blsgpu_fr_expr** out);
+int blsgpu_fr_expr_cols(const blsgpu_fr_expr* e);
+int blsgpu_fr_expr_regs(const blsgpu_fr_expr* e);
+size_t blsgpu_fr_expr_instructions(const blsgpu_fr_expr* e);
+size_t blsgpu_fr_expr_products(const blsgpu_fr_expr* e);
+uint32_t blsgpu_fr_expr_cols_read(const blsgpu_fr_expr* e);
+void blsgpu_fr_expr_free(blsgpu_fr_expr* e);
+int blsgpu_fr_expr_eval(blsgpu_ctx* ctx, const blsgpu_fr_expr* e, const uint64_t* const* cols, const uint8_t* col_log_len, int log_n, int log_stride, uint64_t* out);
+int blsgpu_fr_expr_eval_device(blsgpu_ctx* ctx, const blsgpu_fr_expr* e, const void* const* d_cols, const uint8_t* col_log_len, int log_n, int log_stride, void* d_out);
 /* The same radix-2 transform over GROUP elements: k vectors of 2^log_n G1 (G2) points each, laid end to end, in place, natural order in
  * and out:
  *   forward  Y[m] = sum_j [w^(jm)] P[j],   inverse  P[j] = [n^-1] sum_m [w^(-jm)] Y[m],   w as for blsgpu_fr_ntt

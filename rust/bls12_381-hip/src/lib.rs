@@ -478,6 +478,83 @@ impl<'a> FrPoseidon<'a> {
 impl<'a> Drop for FrPoseidon<'a> {
     fn drop(&mut self) { unsafe { ffi::blsgpu_fr_poseidon_free(self.handle) } }
 }
+/// An operand of an `FrExpr` instruction (`BLSGPU_FR_EXPR_REG` / `_COL` / `_CONST`).
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum FrExprOperand { Reg(u8), Col(u8, i16), Const(u8) }
+impl FrExprOperand {
+    pub fn word(self) -> u32 {
+        match self {
+            FrExprOperand::Reg(i) => i as u32,
+            FrExprOperand::Col(j, rot) => 0x4000_0000 | (((rot as u16) as u32) << 8) | j as u32,
+            FrExprOperand::Const(i) => 0x8000_0000 | i as u32,
+        }
+    }
+}
+/// One instruction of an `FrExpr`: `Mad` is dst = dst + a * b, `Mov` takes one operand.
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub enum FrExprInstr {
+    Add(u8, FrExprOperand, FrExprOperand), Sub(u8, FrExprOperand, FrExprOperand), Mul(u8, FrExprOperand, FrExprOperand), Mad(u8, FrExprOperand, FrExprOperand),
+    Mov(u8, FrExprOperand),
+}
+impl FrExprInstr {
+    pub fn words(self) -> [u32; 3] {
+        let (op, dst, a, b) = match self {
+            FrExprInstr::Add(d, a, b) => (0u32, d, a.word(), b.word()), FrExprInstr::Sub(d, a, b) => (1, d, a.word(), b.word()),
+            FrExprInstr::Mul(d, a, b) => (2, d, a.word(), b.word()), FrExprInstr::Mad(d, a, b) => (3, d, a.word(), b.word()),
+            FrExprInstr::Mov(d, a) => (4, d, a.word(), 0),
+        };
+        [op | ((dst as u32) << 8), a, b]
+    }
+}
+/// An expression program over `Scalar` columns resident on the GPU (`blsgpu_fr_expr`): straight-line code over columns, registers and
+/// constants, validated once by `new` (a bad program is an `Err` naming the instruction and the rule) and evaluated per row in one pass:
+/// gate and quotient columns of a PLONK-style prover.  The FFI layer sees the handle as an untyped pointer; this is its type.
+pub struct FrExpr<'a> { gpu: &'a Gpu, handle: *mut c_void }
+impl<'a> FrExpr<'a> {
+    pub fn new(gpu: &'a Gpu, n_cols: usize, n_regs: usize, consts: &[Scalar], code: &[FrExprInstr]) -> Result<FrExpr<'a>, Error> {
+        let cs = if consts.is_empty() { Vec::new() } else { scalar_limbs(gpu, consts)? };
+        let words: Vec<u32> = code.iter().flat_map(|i| i.words()).collect();
+        let mut handle: *mut c_void = std::ptr::null_mut();
+        check(unsafe {
+            ffi::blsgpu_fr_expr_create(gpu.ctx, n_cols as c_int, n_regs as c_int, consts.len() as c_int, if cs.is_empty() { std::ptr::null() } else { cs.as_ptr() }, code.len(),
+                                       words.as_ptr(), &mut handle as *mut *mut c_void as *mut c_void)
+        })?;
+        Ok(FrExpr { gpu, handle })
+    }
+    pub fn cols(&self) -> usize { unsafe { ffi::blsgpu_fr_expr_cols(self.handle as *const c_void) as usize } }
+    pub fn regs(&self) -> usize { unsafe { ffi::blsgpu_fr_expr_regs(self.handle as *const c_void) as usize } }
+    pub fn instructions(&self) -> usize { unsafe { ffi::blsgpu_fr_expr_instructions(self.handle as *const c_void) } }
+    pub fn products_per_row(&self) -> usize { unsafe { ffi::blsgpu_fr_expr_products(self.handle as *const c_void) } }
+    /// Bit j: some instruction reads column j.
+    pub fn cols_read(&self) -> u32 { unsafe { ffi::blsgpu_fr_expr_cols_read(self.handle as *const c_void) as u32 } }
+    /// The program over 2^`log_n` rows: column j has `columns[j].len()` scalars, a power of two at most 2^`log_n` (an empty slice for a
+    /// column the program does not read), and is read modulo its own length at row + rot * 2^`log_stride`.
+    ///
+    /// # Panics
+    /// If there is not one slice per column or a length is not a power of two at most 2^`log_n` (the C ABI cannot see slice lengths: the
+    /// sizes are checked here, before the call).  What the library itself refuses comes back as `Err`.
+    pub fn eval(&self, columns: &[&[Scalar]], log_n: u32, log_stride: u32) -> Result<Vec<Scalar>, Error> {
+        assert!(columns.len() == self.cols() && log_n <= 28);
+        let n = 1usize << log_n;
+        let mut limbs: Vec<Vec<u64>> = Vec::with_capacity(columns.len());
+        let mut lens = vec![0u8; columns.len()];
+        for (j, c) in columns.iter().enumerate() {
+            if c.is_empty() { limbs.push(Vec::new()); continue; }
+            assert!(c.len().is_power_of_two() && c.len() <= n);
+            lens[j] = c.len().trailing_zeros() as u8;
+            limbs.push(scalar_limbs(self.gpu, c)?);
+        }
+        let ptrs: Vec<*const c_void> = limbs.iter().map(|l| if l.is_empty() { std::ptr::null() } else { l.as_ptr() as *const c_void }).collect();
+        let mut out = vec![0u64; n * 4];
+        check(unsafe {
+            ffi::blsgpu_fr_expr_eval(self.gpu.ctx, self.handle as *const c_void, ptrs.as_ptr(), lens.as_ptr(), log_n as c_int, log_stride as c_int, out.as_mut_ptr())
+        })?;
+        limbs_scalars(self.gpu, &out)
+    }
+}
+impl<'a> Drop for FrExpr<'a> {
+    fn drop(&mut self) { unsafe { ffi::blsgpu_fr_expr_free(self.handle) } }
+}
 fn split72(flat: Vec<u64>) -> Vec<GtLimbs> {
     flat.chunks_exact(72).map(|c| { let mut a = [0u64; 72]; a.copy_from_slice(c); GtLimbs(a) }).collect()
 }
