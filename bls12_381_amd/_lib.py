@@ -111,6 +111,15 @@ SIGNATURES = {
     "blsgpu_fr_expr_free": (None, [c_vp]),
     "blsgpu_fr_expr_eval": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "blsgpu_fr_expr_eval_device": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "blsgpu_fr_lookup_create": (c_int, [c_vp, c_int, c_vp, c_sz, ctypes.POINTER(c_vp)]),
+    "blsgpu_fr_lookup_from_device": (c_int, [c_vp, c_int, c_vp, c_sz, c_sz, ctypes.POINTER(c_vp)]),
+    "blsgpu_fr_lookup_cols": (c_int, [c_vp]),
+    "blsgpu_fr_lookup_rows": (c_sz, [c_vp]),
+    "blsgpu_fr_lookup_distinct": (c_sz, [c_vp]),
+    "blsgpu_fr_lookup_slots": (c_sz, [c_vp]),
+    "blsgpu_fr_lookup_free": (None, [c_vp]),
+    "blsgpu_fr_lookup_count": (c_int, [c_vp, c_vp, c_vp, c_sz, c_int, c_vp, c_vp, c_vp]),
+    "blsgpu_fr_lookup_count_device": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp, c_vp]),
     "blsgpu_fr_poseidon_create": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)]),
     "blsgpu_fr_poseidon_width": (c_int, [c_vp]),
     "blsgpu_fr_poseidon_rounds_full": (c_int, [c_vp]),

@@ -68,6 +68,7 @@ FR_ORDER_NATURAL, FR_ORDER_BITREV = 0, 1                    # include/bls12_381_
 FR_POSEIDON_AUTO, FR_POSEIDON_DENSE, FR_POSEIDON_SPARSE = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_POSEIDON_*
 FR_EXPR_ADD, FR_EXPR_SUB, FR_EXPR_MUL, FR_EXPR_MAD, FR_EXPR_MOV = 0, 1, 2, 3, 4      # include/bls12_381_hip.h: BLSGPU_FR_EXPR_*
 FR_EXPR_MAX_COLS, FR_EXPR_MAX_REGS, FR_EXPR_MAX_CONSTS, FR_EXPR_MAX_INSTR = 32, 8, 32, 256
+FR_LOOKUP_LDS_ROWS, FR_LOOKUP_MISS = 4096, 0xFFFFFFFF    # include/bls12_381_hip.h: BLSGPU_FR_LOOKUP_*
 FR_GENERATOR = 7                          # scalar.rs:99-105 GENERATOR (`MULTIPLICATIVE_GENERATOR` :708): the usual coset shift
 
 
@@ -261,6 +262,85 @@ def fr_expr_assemble(instrs):
             raise ValueError("fr_expr: instruction %d: op and dst must be in [0, 255]" % i)
         code[i] = (op | (dst << 8), fr_expr_operand(ins[2]), fr_expr_operand(ins[3]) if len(ins) == 4 else 0)
     return code
+
+
+class FrLookup:
+    """A lookup table over Fr resident on the device (`blsgpu_fr_lookup`): an index over rows of c scalars built once by
+    Context.fr_lookup; .count gives the logUp multiplicity column, the table row of every looked-up row and the number of misses
+    (include/bls12_381_hip.h)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def _get(self, fn):
+        return int(fn(self.handle)) if self.handle else 0
+
+    @property
+    def cols(self):
+        return self._get(self.ctx.lib.blsgpu_fr_lookup_cols)
+
+    @property
+    def rows(self):
+        return self._get(self.ctx.lib.blsgpu_fr_lookup_rows)
+
+    @property
+    def distinct(self):
+        """the number of different keys among the table's rows"""
+        return self._get(self.ctx.lib.blsgpu_fr_lookup_distinct)
+
+    @property
+    def slots(self):
+        return self._get(self.ctx.lib.blsgpu_fr_lookup_slots)
+
+    def count(self, f, negate=False, return_index=False):
+        """f: the looked-up rows as a (c, n, 4) u64 array of Montgomery limbs ((n, 4) for c = 1) or Python ints in [0, r) nested the same
+        way.  Returns (mult, missing[, index]): mult the (rows, 4) multiplicities (first-occurrence rule; r - m with negate), missing
+        the number of rows of f in no table row, index the (n,) u32 table rows (FR_LOOKUP_MISS for a miss)."""
+        v = _fr_lookup_set(f, self.cols, "fr_lookup.count")
+        n = v.shape[1]
+        mult = np.zeros((self.rows, 4), dtype=np.uint64)
+        index = np.zeros(n, dtype=np.uint32) if return_index else None
+        missing = np.zeros(1, dtype=np.uint64)
+        check(self.ctx.lib.blsgpu_fr_lookup_count(self.ctx.h, self.handle, _ptr(v) if n else None, n, 1 if negate else 0, _ptr(mult), _ptr(index), _ptr(missing)), "fr_lookup_count")
+        return (mult, int(missing[0]), index) if return_index else (mult, int(missing[0]))
+
+    def count_device(self, d_f, pitch, n, d_mult=None, d_index=None, d_missing=None, negate=False):
+        """the same on rows in device memory (column j at j * pitch scalars): device pointers as ints, any output None; asynchronous on
+        the context's stream.  A handle serves one stream at a time."""
+        check(self.ctx.lib.blsgpu_fr_lookup_count_device(self.ctx.h, self.handle, d_f, int(pitch), int(n), 1 if negate else 0, d_mult, d_index, d_missing), "fr_lookup_count_device")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_fr_lookup_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _fr_lookup_set(values, c, what):
+    """a column set of keys -> a contiguous (c, n, 4) u64 array of Montgomery limbs.  c None: taken from the input ((n, 4) / a flat list
+    of ints is c = 1)"""
+    if isinstance(values, np.ndarray):
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        if v.ndim == 2:
+            v = v.reshape((1,) + v.shape)
+        if v.ndim != 3 or v.shape[2] != 4:
+            raise ValueError("%s: expected a (c, n, 4) or (n, 4) array" % what)
+    else:
+        cols = list(values)
+        if not cols or not isinstance(cols[0], (list, tuple)):
+            cols = [cols]
+        n = len(cols[0])
+        if any(len(col) != n for col in cols):
+            raise ValueError("%s: the columns differ in length" % what)
+        v = _fr_limbs(cols, (len(cols), n), what) if n else np.zeros((len(cols), 0, 4), dtype=np.uint64)
+    if c is not None and v.shape[0] != c:
+        raise ValueError("%s: expected %d columns" % (what, c))
+    return v
 
 
 class FrExpr:
@@ -1130,6 +1210,21 @@ class Context:
         h = ctypes.c_void_p()
         check(self.lib.blsgpu_fr_poseidon_create(self.h, t, r_full, r_partial, _ptr(rc), _ptr(mm), int(form), ctypes.byref(h)), "fr_poseidon")
         return FrPoseidon(self, h)
+
+    def fr_lookup(self, table):
+        """a lookup table made resident (include/bls12_381_hip.h: blsgpu_fr_lookup_create): `table` is a (c, rows, 4) u64 array of
+        Montgomery limbs ((rows, 4) for c = 1) or Python ints in [0, r) nested the same way; a key is a row of c scalars.  Returns an
+        FrLookup (.count, .count_device, .rows / .cols / .distinct / .slots, .close())."""
+        t = _fr_lookup_set(table, None, "fr_lookup")
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_lookup_create(self.h, t.shape[0], _ptr(t), t.shape[1], ctypes.byref(h)), "fr_lookup")
+        return FrLookup(self, h)
+
+    def fr_lookup_from_device(self, c, d_table, pitch, rows):
+        """the same from c columns in device memory (column j at j * pitch scalars); the handle keeps its own copy"""
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_lookup_from_device(self.h, int(c), d_table, int(pitch), int(rows), ctypes.byref(h)), "fr_lookup_from_device")
+        return FrLookup(self, h)
 
     def fr_expr(self, n_cols, n_regs, consts, instrs):
         """an expression program made resident (include/bls12_381_hip.h: blsgpu_fr_expr_create): n_cols columns, n_regs registers, consts

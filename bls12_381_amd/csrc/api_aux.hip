@@ -10,6 +10,7 @@
 #include "fr_mle.hip.h"
 #include "fr_poseidon.hip.h"
 #include "fr_expr.hip.h"
+#include "fr_lookup.hip.h"
 #include "h2c.hip.h"
 #include "expand_kernels.hip.h"
 #include "codec.hip.h"
@@ -1232,6 +1233,110 @@ extern "C" int blsgpu_fr_expr_eval(blsgpu_ctx* c, const blsgpu_fr_expr* e, const
   if (h.rc) return h.rc;
   for (int j = 0; j < e->info.n_cols; j++) if (k.p[j]) k.p[j] = (const uint32_t*)((const char*)c->io_a.p + off[j]);
   return h.finish(fr_expr_launch(c, e, k, log_n, log_stride, o));
+}
+
+// ---- lookup tables: logUp multiplicities and row indices in one call (fr_lookup.hip.h; fr_lookup_plan.h checks, sizes and plans) -----------
+static void frl_release(blsgpu_fr_lookup* h) {
+  if (h->keys) hipFree(h->keys);
+  if (h->slot) hipFree(h->slot);
+  if (h->counters) hipFree(h->counters);
+  delete h;
+}
+// the handle of a table whose columns are in device memory: its own row-major copy of the keys, the slot array, the counters.  Ends
+// with the stream synchronised (a setup call: `distinct` comes back, and the caller's buffer is free again).
+static int frl_build(blsgpu_ctx* c, int cols, const void* d_t, size_t pitch, size_t rows, blsgpu_fr_lookup** out) {
+  HIPCHK(hipSetDevice(c->device));
+  const FrLookupPlan plan = fr_lookup_plan(rows, 0);
+  if (!plan.ok) return bad("fr_lookup: rows must be in [1, 2^24]");
+  blsgpu_fr_lookup* h = new blsgpu_fr_lookup();
+  h->device = c->device; h->c = cols; h->rows = rows; h->slots = plan.slots;
+  hipStream_t st = c->stream;
+  u32 distinct = 0;
+  hipError_t err = hipMalloc((void**)&h->keys, rows * (size_t)cols * 32);
+  if (err == hipSuccess) err = hipMalloc((void**)&h->slot, plan.slots * 4);
+  if (err == hipSuccess) err = hipMalloc((void**)&h->counters, rows * 4);
+  if (err == hipSuccess) err = hipMemsetAsync(h->slot, 0, plan.slots * 4, st);
+  if (err == hipSuccess) err = hipMemsetAsync(h->counters, 0, 4, st);        // counters[0] doubles as the `distinct` word of the build
+  if (err == hipSuccess) {
+    KLAUNCH(k_frl_build, dim3(plan.build_grid), dim3(plan.block), 0, st, (const u32*)d_t, pitch, (u32)rows, cols, h->keys, h->slot, (u32)(plan.slots - 1), h->counters);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipMemcpyAsync(&distinct, h->counters, 4, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);
+  if (err != hipSuccess) { frl_release(h); return fail("fr_lookup: building the table", err, __LINE__); }
+  h->distinct = distinct;
+  *out = h;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_lookup_from_device(blsgpu_ctx* c, int cols, const void* d_t, size_t pitch, size_t rows, blsgpu_fr_lookup** out) { CTX_CLAIM(c);
+  if (out) *out = nullptr;
+  if (!c || !out) return bad("fr_lookup: NULL context / out");
+  if (const char* what = frl_table_check(cols, d_t, pitch, rows, true)) return bad(what);
+  return frl_build(c, cols, d_t, pitch, rows, out);
+}
+extern "C" int blsgpu_fr_lookup_create(blsgpu_ctx* c, int cols, const uint64_t* t, size_t rows, blsgpu_fr_lookup** out) { CTX_CLAIM(c);
+  if (out) *out = nullptr;
+  if (!c || !out) return bad("fr_lookup: NULL context / out");
+  if (const char* what = frl_table_check(cols, t, rows, rows, false)) return bad(what);
+  HostCall h(c);
+  void* dt = h.in(c->io_a, t, (size_t)cols * rows * 32);
+  if (h.rc) return h.rc;
+  return frl_build(c, cols, dt, rows, rows, out);
+}
+extern "C" int blsgpu_fr_lookup_cols(const blsgpu_fr_lookup* h) { return h ? h->c : 0; }
+extern "C" size_t blsgpu_fr_lookup_rows(const blsgpu_fr_lookup* h) { return h ? h->rows : 0; }
+extern "C" size_t blsgpu_fr_lookup_distinct(const blsgpu_fr_lookup* h) { return h ? h->distinct : 0; }
+extern "C" size_t blsgpu_fr_lookup_slots(const blsgpu_fr_lookup* h) { return h ? h->slots : 0; }
+extern "C" void blsgpu_fr_lookup_free(blsgpu_fr_lookup* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  hipDeviceSynchronize();                  // an asynchronous count may still be using the table
+  frl_release(h);
+}
+// every argument check of both count forms, before anything is staged or launched
+static int frl_count_check_all(blsgpu_ctx* c, const blsgpu_fr_lookup* h, const void* f, size_t pitch, size_t n, int negate, const void* mult, const void* index, const void* missing, bool device) {
+  if (!c) return bad("fr_lookup_count: NULL context");
+  if (!h) return bad("fr_lookup_count: NULL handle");
+  if (h->device != c->device) return bad("fr_lookup_count: the handle lives on another device than the context");
+  FrlCountArgs a;
+  a.c = h->c; a.rows = h->rows; a.f = f; a.pitch = pitch; a.n = n; a.negate = negate; a.mult = mult; a.index = index; a.missing = missing; a.device = device;
+  if (const char* what = frl_count_check(a)) return bad(what);
+  return BLSGPU_OK;
+}
+static int frl_count_launch(blsgpu_ctx* c, const blsgpu_fr_lookup* h, const void* d_f, size_t pitch, size_t n, int negate, void* d_mult, void* d_index, void* d_missing) {
+  HIPCHK(hipSetDevice(c->device));
+  const FrLookupPlan plan = fr_lookup_plan(h->rows, n);
+  if (!plan.ok) return bad("fr_lookup_count: a size is out of range");
+  hipStream_t st = c->stream;
+  if (d_missing) HIPCHK(hipMemsetAsync(d_missing, 0, 8, st));
+  if (d_mult) HIPCHK(hipMemsetAsync(h->counters, 0, h->rows * 4, st));
+  u32* counters = d_mult ? h->counters : nullptr;
+  if (plan.count_grid && (d_mult || d_index || d_missing)) {
+    const u32 mask = (u32)(h->slots - 1);
+    if (plan.lds_path)
+      KLAUNCH(k_frl_count<true>, dim3(plan.count_grid), dim3(plan.block), plan.count_lds, st, (const u32*)d_f, pitch, n, h->c, (const u32*)h->keys, (const u32*)h->slot, mask, (u32)h->rows,
+              plan.iters, counters, (u32*)d_index, (unsigned long long*)d_missing);
+    else
+      KLAUNCH(k_frl_count<false>, dim3(plan.count_grid), dim3(plan.block), plan.count_lds, st, (const u32*)d_f, pitch, n, h->c, (const u32*)h->keys, (const u32*)h->slot, mask, (u32)h->rows,
+              plan.iters, counters, (u32*)d_index, (unsigned long long*)d_missing);
+  }
+  if (d_mult) KLAUNCH(k_frl_finish, dim3(plan.finish_grid), dim3(plan.block), 0, st, (const u32*)h->counters, (u32)h->rows, negate, (u32*)d_mult);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_lookup_count_device(blsgpu_ctx* c, const blsgpu_fr_lookup* h, const void* d_f, size_t pitch, size_t n, int negate, void* d_mult, void* d_index, void* d_missing) { CTX_CLAIM(c);
+  if (int rc = frl_count_check_all(c, h, d_f, pitch, n, negate, d_mult, d_index, d_missing, true)) return rc;
+  return frl_count_launch(c, h, d_f, pitch, n, negate, d_mult, d_index, d_missing);
+}
+extern "C" int blsgpu_fr_lookup_count(blsgpu_ctx* c, const blsgpu_fr_lookup* h, const uint64_t* f, size_t n, int negate, uint64_t* mult, uint32_t* index, uint64_t* missing) { CTX_CLAIM(c);
+  if (int rc = frl_count_check_all(c, h, f, n, n, negate, mult, index, missing, false)) return rc;
+  HostCall hc(c);
+  void* df = hc.in(c->io_a, f, (size_t)h->c * n * 32);
+  void* dm = mult ? hc.out(c->io_out, mult, h->rows * 32) : nullptr;
+  void* di = index ? hc.out(c->io_b, index, n * 4) : nullptr;
+  void* ds = missing ? hc.out(c->flags_a, missing, 8) : nullptr;
+  if (hc.rc) return hc.rc;
+  return hc.finish(frl_count_launch(c, h, df, n, n, negate, dm, di, ds));
 }
 
 // ---- multilinear tables: folds, eq tables, evaluation, sumcheck rounds (fr_mle.hip.h; fr_mle_plan.h decides the launches) -----------------

@@ -32,6 +32,7 @@
 #include "diag.h"
 #include "fr_poseidon_plan.h"
 #include "fr_expr_plan.h"
+#include "fr_lookup_plan.h"
 
 using namespace bls;
 
@@ -290,6 +291,15 @@ struct blsgpu_fr_expr {
   int device = 0;
   FrxInfo info;
   u32* image = nullptr;
+};
+
+// an Fr lookup table resident on the device (api_aux.hip: blsgpu_fr_lookup_create / _from_device; fr_lookup.hip.h): the handle's own
+// row-major copy of the keys, the open-addressed slot array (row + 1 of a key's first row, 0 = empty) and one counter per table row,
+// the scratch of a count call (which is why a handle serves one stream at a time)
+struct blsgpu_fr_lookup {
+  int device = 0; int c = 0;
+  size_t rows = 0, slots = 0, distinct = 0;
+  u32* keys = nullptr; u32* slot = nullptr; u32* counters = nullptr;
 };
 
 // a sumcheck in progress (api_aux.hip: blsgpu_fr_sumcheck_begin*; fr_mle.hip.h): its own copy of the tables, which the rounds consume,

@@ -145,6 +145,38 @@ def lookup_instance(n, seed=SEED):
     return [t[i] for i in idx], t, m
 
 
+def lookup_tuple_instance(rows, n, c, seed=SEED, dup_every=0, miss_every=0):
+    """a seeded lookup instance over keys of c scalars: a table of `rows` keys and n looked-up keys, as COLUMN sets (table[j][i] is scalar
+    j of row i).  dup_every = d > 0: every d-th table row (i % d == d - 1, i >= d) repeats the key of an EARLIER row at a seeded,
+    scattered position; miss_every = m > 0: every m-th looked-up row (i % m == m - 1) is a fresh key that is in no table row.  The other
+    looked-up rows are drawn from the table rows (repeated ones included), a third of the rows far more often than the rest.
+    Returns (table, f, mult, index, missing) as Python ints: mult[j] = how often the key of row j occurs in f if j is the FIRST table
+    row with that key, else 0; index[i] = that first row for f's row i, or 0xFFFFFFFF for a miss; missing = the number of misses."""
+    vals = to_ints(scalars((rows + n) * c, seed ^ 0x7AB1E5))
+    keys = [tuple(vals[i * c:(i + 1) * c]) for i in range(rows)]
+    fresh = [tuple(vals[(rows + i) * c:(rows + i + 1) * c]) for i in range(n)]
+    picks = splitmix64(seed ^ 0x100C7, 0, rows + n)
+    if dup_every > 0:
+        for i in range(dup_every, rows):
+            if i % dup_every == dup_every - 1:
+                keys[i] = keys[int(picks[i] % np.uint64(i))]
+    first = {}
+    for j, k in enumerate(keys):
+        first.setdefault(k, j)
+    assert not any(k in first for k in fresh)
+    f, mult, index, missing = [], [0] * rows, [], 0
+    hot = max(rows // 3, 1)
+    for i in range(n):
+        if miss_every > 0 and i % miss_every == miss_every - 1:
+            f.append(fresh[i]); index.append(0xFFFFFFFF); missing += 1
+            continue
+        p = int(picks[rows + i])
+        j = (p >> 8) % hot if p & 3 else (p >> 8) % rows
+        f.append(keys[j]); index.append(first[keys[j]]); mult[first[keys[j]]] += 1
+    cols = lambda ks, m: [[k[j] for k in ks] for j in range(c)] if m else [[] for _ in range(c)]
+    return cols(keys, rows), cols(f, n), mult, index, missing
+
+
 # ---- a vanilla PLONK instance and its quotient expression (blsgpu_fr_expr_*) ---------------------------------------------------------
 # the column map of plonk_quotient_program: full-length columns first, then the periodic one, then the challenges (length 1)
 PLONK_COLS = {name: j for j, name in enumerate(

@@ -558,6 +558,51 @@ class FrExpr {
  private:
   blsgpu_fr_expr* e_ = nullptr;
 };
+// A lookup table over Fr resident on the device (include/bls12_381_hip.h: blsgpu_fr_lookup_*): an index over rows of c scalars, built
+// once by the constructor from c columns of equal length (a key is the tuple (columns[0][i], ..., columns[c - 1][i])).  count() gives
+// the logUp multiplicity column for the looked-up rows f (m[j] = how often row j's key occurs in f if j is the FIRST row with that key,
+// else 0; r - m with negate, ready for fr_frac_sum's mult), the first table row of every looked-up row (FrLookup::miss for none) and the
+// number of looked-up rows that are in no table row.  Keys are compared limb for limb: inputs are canonical Montgomery limbs.
+class FrLookup {
+ public:
+  static constexpr uint32_t miss = BLSGPU_FR_LOOKUP_MISS;
+  struct Counts { std::vector<FrLimbs> mult; std::vector<uint32_t> index; uint64_t missing = 0; };
+  explicit FrLookup(const std::vector<std::vector<FrLimbs>>& columns) {
+    const std::vector<uint64_t> t = pack(columns, "FrLookup");
+    check(blsgpu_fr_lookup_create(Context::instance().handle(), (int)columns.size(), t.data(), columns[0].size(), &h_), "fr_lookup_create");
+  }
+  ~FrLookup() { blsgpu_fr_lookup_free(h_); }
+  FrLookup(const FrLookup&) = delete;
+  FrLookup& operator=(const FrLookup&) = delete;
+  FrLookup(FrLookup&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  int cols() const { return blsgpu_fr_lookup_cols(h_); }
+  size_t rows() const { return blsgpu_fr_lookup_rows(h_); }
+  size_t distinct() const { return blsgpu_fr_lookup_distinct(h_); }
+  size_t slots() const { return blsgpu_fr_lookup_slots(h_); }
+  const blsgpu_fr_lookup* handle() const { return h_; }
+  Counts count(const std::vector<std::vector<FrLimbs>>& f, bool negate = false) const {
+    if (f.size() != (size_t)cols()) throw std::invalid_argument("FrLookup::count: one column per column of the table");
+    const std::vector<uint64_t> v = pack(f, "FrLookup::count");
+    const size_t n = f[0].size();
+    Counts r;
+    r.mult.resize(rows());
+    r.index.resize(n);
+    check(blsgpu_fr_lookup_count(Context::instance().handle(), h_, n ? v.data() : nullptr, n, negate ? 1 : 0, r.mult[0].data(), n ? r.index.data() : nullptr, &r.missing), "fr_lookup_count");
+    return r;
+  }
+ private:
+  static std::vector<uint64_t> pack(const std::vector<std::vector<FrLimbs>>& columns, const char* what) {
+    if (columns.empty()) throw std::invalid_argument(std::string(what) + ": at least one column");
+    std::vector<uint64_t> out;
+    out.reserve(columns.size() * columns[0].size() * 4);
+    for (const auto& col : columns) {
+      if (col.size() != columns[0].size()) throw std::invalid_argument(std::string(what) + ": the columns differ in length");
+      for (const auto& e : col) out.insert(out.end(), e.begin(), e.end());
+    }
+    return out;
+  }
+  blsgpu_fr_lookup* h_ = nullptr;
+};
 // Multilinear tables (include/bls12_381_hip.h): k tables of t.size() / k = 2^m scalars each, laid end to end; entry i is the value at the
 // point whose coordinate x_b is bit b of i.  fr_mle_fold binds the top variable at r (k x 2^(m-1) out), fr_eq_table is
 // eq(point)[i] = prod_b (bit b of i ? point[b] : 1 - point[b]), fr_mle_eval gives f_j(point) with point[b] the value of x_b.

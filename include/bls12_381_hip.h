@@ -804,6 +804,45 @@ uint32_t blsgpu_fr_expr_cols_read(const blsgpu_fr_expr* e);
 void blsgpu_fr_expr_free(blsgpu_fr_expr* e);
 int blsgpu_fr_expr_eval(blsgpu_ctx* ctx, const blsgpu_fr_expr* e, const uint64_t* const* cols, const uint8_t* col_log_len, int log_n, int log_stride, uint64_t* out);
 int blsgpu_fr_expr_eval_device(blsgpu_ctx* ctx, const blsgpu_fr_expr* e, const void* const* d_cols, const uint8_t* col_log_len, int log_n, int log_stride, void* d_out);
+/* Lookup tables: the multiplicity column of a log-derivative lookup argument (the `mult` of blsgpu_fr_frac_sum) and the table row
+ * every looked-up row hit, in ONE call on data that is already in device memory.  A prover commits to the multiplicities before it
+ * draws beta and gamma, so this is the first step of the lookup argument and cannot be folded into a challenge-dependent pass.
+ * A KEY is a row of c scalars, c in [1, BLSGPU_FR_FRAC_MAX_COLS].  The table t (`rows` keys) and the looked-up rows f (n keys) are
+ * column sets addressed exactly as blsgpu_fr_frac_sum's: column j starts j * pitch scalars behind the base pointer, pitch >= rows
+ * (>= n for f); the host forms are packed (pitch = rows, pitch = n).
+ * CONTRACT: two keys are equal when all 8 c 32-bit words of their limbs are equal.  Inputs are canonical Montgomery limbs, as
+ * everywhere in this library, so limb equality is field equality; a non-canonical limb pattern is a different key.
+ * blsgpu_fr_lookup_create / _from_device build the handle once per circuit: its own row-major copy of the keys (the caller's buffer may
+ * be freed or overwritten once the call returns), an open-addressed index of `slots` = the power of two >= 2 * rows 32-bit words, and
+ * `rows` 32-bit counters.  Both are setup calls and synchronise.  The accessors report c, rows, the number of distinct keys and slots.
+ * blsgpu_fr_lookup_free follows the rules of blsgpu_fr_matrix_free (it waits for the device; NULL is allowed).
+ * A count call writes any of three outputs (each may be NULL):
+ *   d_mult     `rows` scalars, canonical Montgomery: m[j] = #{i : f[i] == t[j]} if j is the FIRST row of t with that key, else 0 -- so
+ *              sum_j m[j] / (gamma + t[j]) is right for a table with repeated rows.  With negate = 1 the value is r - m[j] (0 stays 0):
+ *              the column goes straight into blsgpu_fr_frac_sum's mult.
+ *   d_index    n uint32: the first row of t equal to f[i], or BLSGPU_FR_LOOKUP_MISS.
+ *   d_missing  one uint64 in device memory: the number of looked-up rows that are in no table row, written by the call on the stream.
+ * The host form takes host pointers (mult: rows * 4 uint64; index: n uint32; missing: one uint64) and synchronises.
+ * rows in [1, 2^24]; n <= 2^28 and (c - 1) * pitch + n <= 2^28; n == 0 is valid (mult all zero, missing 0).  Counts stay below 2^32.
+ * Tables of at most BLSGPU_FR_LOOKUP_LDS_ROWS rows count in per-workgroup on-chip counters; larger ones behind a per-workgroup cache.
+ * The device forms are asynchronous on the context's stream and never synchronise.  The counters are the HANDLE's scratch, zeroed at
+ * the start of each count call: calls on one handle are ordered by the stream, and a handle serves ONE stream at a time.  Results are
+ * identical from run to run (integer sums only).  Device pointers must be 16-byte aligned (d_index: 4, d_missing: 8).
+ * BLSGPU_ERR_ARG (nothing staged or launched): c or rows out of range, negate not 0 or 1, a NULL context, handle, t, or f with n > 0,
+ * a handle created on another device, pitch < n (pitch < rows when building from device), a size out of range (64-bit overflow
+ * included), a misaligned device pointer, an output overlapping f or another output. */
+typedef struct blsgpu_fr_lookup blsgpu_fr_lookup;
+#define BLSGPU_FR_LOOKUP_LDS_ROWS 4096
+#define BLSGPU_FR_LOOKUP_MISS     0xFFFFFFFFu
+int blsgpu_fr_lookup_create(blsgpu_ctx* ctx, int c, const uint64_t* t, size_t rows, blsgpu_fr_lookup** out);
+int blsgpu_fr_lookup_from_device(blsgpu_ctx* ctx, int c, const void* d_t, size_t pitch, size_t rows, blsgpu_fr_lookup** out);
+int blsgpu_fr_lookup_cols(const blsgpu_fr_lookup* h);
+size_t blsgpu_fr_lookup_rows(const blsgpu_fr_lookup* h);
+size_t blsgpu_fr_lookup_distinct(const blsgpu_fr_lookup* h);
+size_t blsgpu_fr_lookup_slots(const blsgpu_fr_lookup* h);
+void blsgpu_fr_lookup_free(blsgpu_fr_lookup* h);
+int blsgpu_fr_lookup_count(blsgpu_ctx* ctx, const blsgpu_fr_lookup* h, const uint64_t* f, size_t n, int negate, uint64_t* mult, uint32_t* index, uint64_t* missing);
+int blsgpu_fr_lookup_count_device(blsgpu_ctx* ctx, const blsgpu_fr_lookup* h, const void* d_f, size_t pitch, size_t n, int negate, void* d_mult, void* d_index, void* d_missing);
 /* The same radix-2 transform over GROUP elements: k vectors of 2^log_n G1 (G2) points each, laid end to end, in place, natural order in
  * and out:
  *   forward  Y[m] = sum_j [w^(jm)] P[j],   inverse  P[j] = [n^-1] sum_m [w^(-jm)] Y[m],   w as for blsgpu_fr_ntt

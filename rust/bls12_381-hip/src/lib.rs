@@ -555,6 +555,56 @@ impl<'a> FrExpr<'a> {
 impl<'a> Drop for FrExpr<'a> {
     fn drop(&mut self) { unsafe { ffi::blsgpu_fr_expr_free(self.handle) } }
 }
+/// What `FrLookup::count` returns: the multiplicity column (`rows` scalars), the first table row of every looked-up row
+/// (`FrLookup::MISS` for none) and the number of looked-up rows that are in no table row.
+pub struct FrLookupCounts { pub mult: Vec<Scalar>, pub index: Vec<u32>, pub missing: u64 }
+/// A lookup table over `Scalar` keys resident on the GPU (`blsgpu_fr_lookup`): an index over rows of c scalars, built once; `count` gives
+/// the logUp multiplicity column a prover commits to before it draws its challenges (m[j] = how often row j's key is looked up if j is the
+/// FIRST row with that key, else 0; r - m with `negate`, ready for the fraction sum's `mult`).  The FFI layer sees the handle as an
+/// untyped pointer; this is its type.
+pub struct FrLookup<'a> { gpu: &'a Gpu, handle: *mut c_void }
+impl<'a> FrLookup<'a> {
+    pub const MISS: u32 = 0xFFFF_FFFF;
+    /// `columns[j][i]` is scalar j of table row i: c = `columns.len()` in 1..=8 columns of equal length.
+    ///
+    /// # Panics
+    /// If there is no column or the columns differ in length (the C ABI cannot see slice lengths).
+    pub fn new(gpu: &'a Gpu, columns: &[&[Scalar]]) -> Result<FrLookup<'a>, Error> {
+        let (limbs, rows) = Self::pack(gpu, columns)?;
+        let mut handle: *mut c_void = std::ptr::null_mut();
+        check(unsafe { ffi::blsgpu_fr_lookup_create(gpu.ctx, columns.len() as c_int, limbs.as_ptr(), rows, &mut handle as *mut *mut c_void as *mut c_void) })?;
+        Ok(FrLookup { gpu, handle })
+    }
+    fn pack(gpu: &Gpu, columns: &[&[Scalar]]) -> Result<(Vec<u64>, usize), Error> {
+        assert!(!columns.is_empty() && columns.iter().all(|c| c.len() == columns[0].len()));
+        let mut limbs = Vec::with_capacity(columns.len() * columns[0].len() * 4);
+        for c in columns { if !c.is_empty() { limbs.extend(scalar_limbs(gpu, c)?); } }
+        Ok((limbs, columns[0].len()))
+    }
+    pub fn cols(&self) -> usize { unsafe { ffi::blsgpu_fr_lookup_cols(self.handle as *const c_void) as usize } }
+    pub fn rows(&self) -> usize { unsafe { ffi::blsgpu_fr_lookup_rows(self.handle as *const c_void) } }
+    pub fn distinct(&self) -> usize { unsafe { ffi::blsgpu_fr_lookup_distinct(self.handle as *const c_void) } }
+    pub fn slots(&self) -> usize { unsafe { ffi::blsgpu_fr_lookup_slots(self.handle as *const c_void) } }
+    /// Counts the looked-up rows `f` (one slice per table column, equal lengths; empty slices are a valid, empty lookup).
+    ///
+    /// # Panics
+    /// If there is not one slice per table column or the slices differ in length.
+    pub fn count(&self, f: &[&[Scalar]], negate: bool) -> Result<FrLookupCounts, Error> {
+        assert!(f.len() == self.cols());
+        let (limbs, n) = Self::pack(self.gpu, f)?;
+        let mut mult = vec![0u64; self.rows() * 4];
+        let mut index = vec![0u32; n];
+        let mut missing = 0u64;
+        check(unsafe {
+            ffi::blsgpu_fr_lookup_count(self.gpu.ctx, self.handle as *const c_void, if n == 0 { std::ptr::null() } else { limbs.as_ptr() }, n, negate as c_int, mult.as_mut_ptr(),
+                                        if n == 0 { std::ptr::null_mut() } else { index.as_mut_ptr() }, &mut missing as *mut u64)
+        })?;
+        Ok(FrLookupCounts { mult: limbs_scalars(self.gpu, &mult)?, index, missing })
+    }
+}
+impl<'a> Drop for FrLookup<'a> {
+    fn drop(&mut self) { unsafe { ffi::blsgpu_fr_lookup_free(self.handle) } }
+}
 fn split72(flat: Vec<u64>) -> Vec<GtLimbs> {
     flat.chunks_exact(72).map(|c| { let mut a = [0u64; 72]; a.copy_from_slice(c); GtLimbs(a) }).collect()
 }

@@ -32,11 +32,12 @@ C_TO_RUST = {
 # Handle types the Rust side sees as UNTYPED pointers.  tests/test_host_cpu.py::test_rust_ffi_matches_header maps Rust types back to C
 # types through a closed table of the opaque structs that existed when it was written; a handle type added since is therefore declared
 # to Rust as `c_void` (a handle as `*mut c_void` / `*const c_void`, the slot an upload writes it to as `*mut c_void`), and the safe
-# wrapper in rust/bls12_381-hip/src/lib.rs gives it a type of its own (`FrMatrix`, `FrSumcheck`, `FrPoseidon`, `FrExpr`).  The C header keeps the typed declarations.
+# wrapper in rust/bls12_381-hip/src/lib.rs gives it a type of its own (`FrMatrix`, `FrSumcheck`, `FrPoseidon`, `FrExpr`, `FrLookup`).  The C header keeps the typed declarations.
 UNTYPED_FOR_RUST = {"blsgpu_fr_matrix*": "void*", "const blsgpu_fr_matrix*": "const void*", "blsgpu_fr_matrix**": "void*",
                     "blsgpu_fr_sumcheck*": "void*", "const blsgpu_fr_sumcheck*": "const void*", "blsgpu_fr_sumcheck**": "void*",
                     "blsgpu_fr_poseidon*": "void*", "const blsgpu_fr_poseidon*": "const void*", "blsgpu_fr_poseidon**": "void*",
                     "blsgpu_fr_expr*": "void*", "const blsgpu_fr_expr*": "const void*", "blsgpu_fr_expr**": "void*",
+                    "blsgpu_fr_lookup*": "void*", "const blsgpu_fr_lookup*": "const void*", "blsgpu_fr_lookup**": "void*",
                     # likewise an array of host pointers to scalars (an array of untyped pointers), and a 32-bit mask returned as `unsigned`
                     "const uint64_t*const*": "const void*const*", "uint32_t": "unsigned"}
 
