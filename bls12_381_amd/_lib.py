@@ -169,6 +169,12 @@ SIGNATURES = {
     "blsgpu_g2_sum": (c_int, [c_vp, c_vp, c_sz, c_vp]),
     "blsgpu_g1_sum_device": (c_int, [c_vp, c_vp, c_sz, c_vp]),
     "blsgpu_g2_sum_device": (c_int, [c_vp, c_vp, c_sz, c_vp]),
+    "blsgpu_g1_sum_segments": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_sz, c_vp]),
+    "blsgpu_g2_sum_segments": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_sz, c_vp]),
+    "blsgpu_g1_sum_segments_device": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_sz, c_vp]),
+    "blsgpu_g2_sum_segments_device": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_sz, c_vp]),
+    "blsgpu_bls_fast_aggregate_verify_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]),
+    "blsgpu_bls_fast_aggregate_verify_batch_device": (c_int, [c_vp, c_int, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]),
     "blsgpu_g1_batch_normalize": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
     "blsgpu_g2_batch_normalize": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
     "blsgpu_g1_from_bytes_batch": (c_int, [c_vp, c_vp, c_sz, c_int, c_int, c_vp, c_vp, c_vp]),

@@ -883,6 +883,35 @@ class Context:
         fn = self.lib.blsgpu_g1_sum_device if group == 1 else self.lib.blsgpu_g2_sum_device
         check(fn(self.h, ctypes.c_void_p(d_xyz), n, ctypes.c_void_p(d_out)), "sum_device")
 
+    def sum_segments(self, group, xy, infinity, offsets, idx=None):
+        """Segmented, gathered sums (blsgpu_g{1,2}_sum_segments): xy (npoints, 12 | 24) u64 affine wire points with their infinity bytes,
+        offsets (nseg + 1) u64 in CSR form, idx (offsets[-1],) u32 or None (term t is point t).  -> (nseg, 18 | 36) u64 projective
+        points, segment s the sum of the points idx[offsets[s]:offsets[s + 1]]; an empty segment gives the identity."""
+        w = 12 if group == 1 else 24
+        xy = _u64(xy, (-1, w))
+        npoints = xy.shape[0]
+        inf = np.zeros(npoints, dtype=np.uint8) if infinity is None else _flags(infinity, npoints)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError("sum_segments: offsets needs nseg + 1 entries")
+        nseg, total = off.shape[0] - 1, int(off[-1])
+        ix = None
+        if idx is not None:
+            ix = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+            if ix.shape[0] != total:
+                raise ValueError("sum_segments: idx needs offsets[-1] entries")
+        out = np.zeros((nseg, 18 if group == 1 else 36), dtype=np.uint64)
+        fn = self.lib.blsgpu_g1_sum_segments if group == 1 else self.lib.blsgpu_g2_sum_segments
+        check(fn(self.h, _ptr(xy) if npoints else None, _ptr(inf) if npoints else None, npoints, _ptr(ix) if total else None, _ptr(off), nseg, total,
+                 _ptr(out) if nseg else None), "sum_segments")
+        return out
+
+    def sum_segments_device(self, group, d_xy, d_inf, npoints, d_idx, d_offsets, nseg, total, d_out):
+        """device form of sum_segments: asynchronous on the context's stream; an index >= npoints is skipped and reported by synchronize()"""
+        fn = self.lib.blsgpu_g1_sum_segments_device if group == 1 else self.lib.blsgpu_g2_sum_segments_device
+        vp = lambda p: ctypes.c_void_p(p) if p else None
+        check(fn(self.h, vp(d_xy), vp(d_inf), npoints, vp(d_idx), vp(d_offsets), nseg, total, vp(d_out)), "sum_segments_device")
+
     def batch_normalize(self, group, xyz):
         w = 18 if group == 1 else 36
         xyz = _u64(xyz, (-1, w))
@@ -1545,6 +1574,34 @@ class Context:
     def bls_verify_batch_device(self, mode, d_pk, d_sig, d_msgs, d_offsets, n, d_dst, dst_len, d_verdict):
         check(self.lib.blsgpu_bls_verify_batch_device(self.h, mode, ctypes.c_void_p(d_pk), ctypes.c_void_p(d_sig), ctypes.c_void_p(d_msgs), ctypes.c_void_p(d_offsets), n,
                                                       ctypes.c_void_p(d_dst), dst_len, ctypes.c_void_p(d_verdict)), "bls_verify_batch_device")
+
+    def bls_fast_aggregate_verify(self, mode, d_keys_xy, d_keys_inf, nkeys, subsets, sig_bytes, msgs, dst):
+        """Aggregate BLS verification (blsgpu_bls_fast_aggregate_verify_batch): signature i over msgs[i] by the keys subsets[i] (a list of
+        index lists) of a key set RESIDENT on the device (d_keys_xy / d_keys_inf: device addresses of nkeys decoded affine points, G1 in
+        mode 0, G2 in mode 1).  -> (n,) uint8: 1 valid, 0 invalid, 3 bad signature"""
+        n = len(msgs)
+        if len(subsets) != n:
+            raise ValueError("bls_fast_aggregate_verify: one subset per message")
+        sg = np.ascontiguousarray(np.frombuffer(bytes(sig_bytes), dtype=np.uint8)) if not isinstance(sig_bytes, np.ndarray) else np.ascontiguousarray(sig_bytes, dtype=np.uint8).reshape(-1)
+        if sg.shape[0] != n * (96 if mode == 0 else 48):
+            raise ValueError("bls_fast_aggregate_verify: signature bytes do not match the number of messages")
+        koff = np.zeros(n + 1, dtype=np.uint64)
+        koff[1:] = np.cumsum([len(s) for s in subsets])
+        total = int(koff[-1])
+        idx = np.array([i for s in subsets for i in s], dtype=np.uint32) if total else np.zeros(1, dtype=np.uint32)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        blob = np.frombuffer(b"".join(bytes(m) for m in msgs), dtype=np.uint8).copy() if int(off[-1]) else np.zeros(1, dtype=np.uint8)
+        d = np.frombuffer(bytes(dst), dtype=np.uint8).copy() if len(dst) else np.zeros(1, dtype=np.uint8)
+        out = np.zeros(n, dtype=np.uint8)
+        check(self.lib.blsgpu_bls_fast_aggregate_verify_batch(self.h, mode, ctypes.c_void_p(d_keys_xy), ctypes.c_void_p(d_keys_inf), nkeys, _ptr(idx), _ptr(koff), total, _ptr(sg),
+                                                              _ptr(blob), _ptr(off), n, _ptr(d), len(dst), _ptr(out)), "bls_fast_aggregate_verify_batch")
+        return out
+
+    def bls_fast_aggregate_verify_device(self, mode, d_keys_xy, d_keys_inf, nkeys, d_idx, d_key_offsets, total_keys, d_sig, d_msgs, d_msg_offsets, n, d_dst, dst_len, d_verdict):
+        vp = lambda p: ctypes.c_void_p(p) if p else None
+        check(self.lib.blsgpu_bls_fast_aggregate_verify_batch_device(self.h, mode, vp(d_keys_xy), vp(d_keys_inf), nkeys, vp(d_idx), vp(d_key_offsets), total_keys, vp(d_sig),
+                                                                     vp(d_msgs), vp(d_msg_offsets), n, vp(d_dst), dst_len, vp(d_verdict)), "bls_fast_aggregate_verify_batch_device")
 
     # -- G2Prepared resident on the device (pairings.rs:487-546) and its consumers (:554-603) -----------------------
     def g2_prepare(self, g2_xy, g2_inf=None):

@@ -1759,33 +1759,39 @@ static int verify_check(blsgpu_ctx* c, int mode, const void* pk, const void* sig
   if (dst_len > dst_max) return bad("bls_verify_batch_device: reduce a DST longer than 255 bytes on the host first");
   return BLSGPU_OK;
 }
-extern "C" int blsgpu_bls_verify_batch_device(blsgpu_ctx* c, int mode, const void* d_pk, const void* d_sig, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst,
-                                              size_t dst_len, void* d_verdict) { CTX_CLAIM(c);
-  if (int rc = verify_check(c, mode, d_pk, d_sig, d_offsets, n, d_dst, dst_len, 255, d_verdict)) return rc;
-  if (!n) return BLSGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
+// where every intermediate of the chain lives in c->ver (the aggregate form appends the summed keys: the plain form's block is unchanged)
+struct VerifyLayout { size_t consts, a, b, hp, h, fl, g1t, g2t, tf, qi, off, gt, apk, bytes; };
+static VerifyLayout verify_layout(int mode, size_t n, bool aggregate) {
   // G1-side and G2-side points of the equation: mode 0 = (pk, sig), mode 1 = (sig, pk); the hash goes to the signature's group
   const size_t a_xy = n * 96, b_xy = n * 192, h_xyz = n * (mode == 0 ? 288 : 144), h_xy = n * (mode == 0 ? 192 : 96);
   const size_t al = 256;
   auto up = [&](size_t x) { return (x + al - 1) / al * al; };
+  VerifyLayout L;
   size_t o = 0;
-  const size_t o_consts = o; o += up(288);
-  const size_t o_a = o; o += up(a_xy);
-  const size_t o_b = o; o += up(b_xy);
-  const size_t o_hp = o; o += up(h_xyz);
-  const size_t o_h = o; o += up(h_xy);
-  const size_t o_fl = o; o += up(6 * n);                // a_inf a_ok b_inf b_ok h_inf is_one
-  const size_t o_g1t = o; o += up(2 * n * 96);
-  const size_t o_g2t = o; o += up(2 * n * 192);
-  const size_t o_tf = o; o += up(4 * n);                // g1f (2n) g2f (2n)
-  const size_t o_qi = o; o += up(2 * n * 4);
-  const size_t o_off = o; o += up((n + 1) * 8);
-  const size_t o_gt = o; o += up(n * 576);
-  const bool fresh = c->ver.cap < o;
-  if (c->ver.reserve(o)) { g_err = "hipMalloc(bulk verification) failed"; return BLSGPU_ERR_HIP; }
+  L.consts = o; o += up(288);
+  L.a = o; o += up(a_xy);
+  L.b = o; o += up(b_xy);
+  L.hp = o; o += up(h_xyz);
+  L.h = o; o += up(h_xy);
+  L.fl = o; o += up(6 * n);                // a_inf a_ok b_inf b_ok h_inf is_one
+  L.g1t = o; o += up(2 * n * 96);
+  L.g2t = o; o += up(2 * n * 192);
+  L.tf = o; o += up(4 * n);                // g1f (2n) g2f (2n)
+  L.qi = o; o += up(2 * n * 4);
+  L.off = o; o += up((n + 1) * 8);
+  L.gt = o; o += up(n * 576);
+  L.apk = o; if (aggregate) o += up(n * (mode == 0 ? 144 : 288));       // the n summed keys, projective
+  L.bytes = o;
+  return L;
+}
+// What both verifiers do before their keys and signatures are decoded: the scratch block, the constants, the resident -G2, and the
+// hash of the messages queued on the side stream.  Returns with c->stream the caller's stream again.
+static int verify_begin(blsgpu_ctx* c, int mode, size_t n, const VerifyLayout& L, const void* d_msgs, const void* d_offsets, const void* d_dst, size_t dst_len) {
+  const bool fresh = c->ver.cap < L.bytes;
+  if (c->ver.reserve(L.bytes)) { g_err = "hipMalloc(bulk verification) failed"; return BLSGPU_ERR_HIP; }
   uint8_t* base = c->ver.as<uint8_t>();
   if (fresh || !c->ver_consts_ready) {
-    KLAUNCH(k_bls_consts, dim3(1), dim3(64), 0, c->stream, (u32*)(base + o_consts));
+    KLAUNCH(k_bls_consts, dim3(1), dim3(64), 0, c->stream, (u32*)(base + L.consts));
     LAUNCHCHK();
     HIPCHK(hipEventRecord(c->ev_ver, c->stream));
     c->ver_consts_ready = true;
@@ -1793,11 +1799,10 @@ extern "C" int blsgpu_bls_verify_batch_device(blsgpu_ctx* c, int mode, const voi
   HIPCHK(hipStreamWaitEvent(c->stream, c->ev_ver, 0));
   if (mode == 1 && !c->ver_table) {
     // `G2Prepared::from(-G2Affine::generator())`, once per context (its own allocation: it outlives a regrown scratch block)
-    int rc = blsgpu_g2_prepare_device(c, base + o_consts + 96, nullptr, 1, &c->ver_table);
+    int rc = blsgpu_g2_prepare_device(c, base + L.consts + 96, nullptr, 1, &c->ver_table);
     if (rc) return rc;
   }
-  uint8_t* fl = base + o_fl;
-  uint8_t *a_inf = fl, *a_ok = fl + n, *b_inf = fl + 2 * n, *b_ok = fl + 3 * n, *h_inf = fl + 4 * n, *is_one = fl + 5 * n;
+  uint8_t* h_inf = base + L.fl + 4 * n;
   // 1.-3. independent, latency-shaped stages (one lane or lane pair per point, a few thousand field multiplications each): the two
   // checked decodings run on the context's stream, hash-to-curve + normalisation beside them on a side stream (ONE side stream: the
   // runtime multiplexes streams onto a few hardware queues, and two side streams created back to back shared one -- kernel trace of
@@ -1818,40 +1823,142 @@ extern "C" int blsgpu_bls_verify_batch_device(blsgpu_ctx* c, int mode, const voi
     // slower G2 decoder of before); BLSGPU_VERIFY_H2C_SPLIT=1 lets the batch-size rule apply here too, for re-measuring)
     const int keep_split = c->h2c_split;
     c->h2c_split = c->diag.verify_h2c_split ? keep_split : 0;
-    if (e == hipSuccess) rc = blsgpu_hash_to_curve_device(c, mode == 0 ? 2 : 1, d_msgs, d_offsets, n, d_dst, dst_len, 0, base + o_hp);
+    if (e == hipSuccess) rc = blsgpu_hash_to_curve_device(c, mode == 0 ? 2 : 1, d_msgs, d_offsets, n, d_dst, dst_len, 0, base + L.hp);
     c->h2c_split = keep_split;
     if (e == hipSuccess && !rc)
-      rc = mode == 0 ? blsgpu_g2_batch_normalize_device(c, base + o_hp, n, base + o_h, h_inf) : blsgpu_g1_batch_normalize_device(c, base + o_hp, n, base + o_h, h_inf);
+      rc = mode == 0 ? blsgpu_g2_batch_normalize_device(c, base + L.hp, n, base + L.h, h_inf) : blsgpu_g1_batch_normalize_device(c, base + L.hp, n, base + L.h, h_inf);
     if (e == hipSuccess && !rc) e = hipEventRecord(c->ev_ver_side[1], c->stream);
     c->stream = main_stream;
     if (e != hipSuccess) return fail("bls_verify_batch: side stream", e, __LINE__);
     if (rc) return rc;
   }
-  // checked decoding (`from_compressed`: on the curve, in the subgroup) of both point arrays on the context's stream, which then waits for the side stream
-  // (ONE launch for both arrays: k_point_decode_both)
-  KLAUNCH(k_point_decode_both, dim3(2 * nblk(n, 128)), dim3(128), 0, c->stream, (const uint8_t*)(mode == 0 ? d_sig : d_pk), (u32*)(base + o_b), b_inf, b_ok,
-                     (const uint8_t*)(mode == 0 ? d_pk : d_sig), (u32*)(base + o_a), a_inf, a_ok, n, 3);
-  LAUNCHCHK();
-  HIPCHK(hipStreamWaitEvent(main_stream, c->ev_ver_side[1], 0));
+  return BLSGPU_OK;
+}
+// What both verifiers do once their keys and signatures are decoded (xy, infinity and ok flags of both in the block): wait for the hashes,
+// assemble the terms, one multi_miller_loop + final exponentiation per equation, the verdicts.
+static int verify_finish(blsgpu_ctx* c, int mode, size_t n, const VerifyLayout& L, void* d_verdict) {
+  uint8_t* base = c->ver.as<uint8_t>();
+  uint8_t* fl = base + L.fl;
+  uint8_t *a_inf = fl, *a_ok = fl + n, *b_inf = fl + 2 * n, *b_ok = fl + 3 * n, *h_inf = fl + 4 * n, *is_one = fl + 5 * n;
+  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_ver_side[1], 0));
   // 4. the two terms of every equation
   const uint8_t *pk_inf = mode == 0 ? a_inf : b_inf, *pk_ok = mode == 0 ? a_ok : b_ok, *sig_inf = mode == 0 ? b_inf : a_inf, *sig_ok = mode == 0 ? b_ok : a_ok;
-  KLAUNCH(k_bls_assemble, dim3(nblk(n + 1, 256)), dim3(256), 0, c->stream, mode, (const u32*)(base + (mode == 0 ? o_a : o_b)), pk_inf, pk_ok,
-                     (const u32*)(base + (mode == 0 ? o_b : o_a)), sig_inf, sig_ok, (const u32*)(base + o_h), h_inf, (const u32*)(base + o_consts), n, (u32*)(base + o_g1t),
-                     base + o_tf, (u32*)(base + o_g2t), base + o_tf + 2 * n, (u32*)(base + o_qi), (unsigned long long*)(base + o_off));
+  KLAUNCH(k_bls_assemble, dim3(nblk(n + 1, 256)), dim3(256), 0, c->stream, mode, (const u32*)(base + (mode == 0 ? L.a : L.b)), pk_inf, pk_ok,
+                     (const u32*)(base + (mode == 0 ? L.b : L.a)), sig_inf, sig_ok, (const u32*)(base + L.h), h_inf, (const u32*)(base + L.consts), n, (u32*)(base + L.g1t),
+                     base + L.tf, (u32*)(base + L.g2t), base + L.tf + 2 * n, (u32*)(base + L.qi), (unsigned long long*)(base + L.off));
   LAUNCHCHK();
   // 5. one multi_miller_loop + final exponentiation per equation
+  int rc;
   if (mode == 0)
-    rc = blsgpu_multi_miller_loop_many_device(c, base + o_g1t, base + o_tf, base + o_g2t, base + o_tf + 2 * n, base + o_off, n, 2 * n, 2, 1, base + o_gt);
+    rc = blsgpu_multi_miller_loop_many_device(c, base + L.g1t, base + L.tf, base + L.g2t, base + L.tf + 2 * n, base + L.off, n, 2 * n, 2, 1, base + L.gt);
   else
-    rc = blsgpu_multi_miller_loop_prepared_many_device(c, base + o_g1t, base + o_tf, base + o_g2t, base + o_tf + 2 * n, base + o_qi, c->ver_table, base + o_off, n, 2 * n, 2, 1,
-                                                       base + o_gt);
+    rc = blsgpu_multi_miller_loop_prepared_many_device(c, base + L.g1t, base + L.tf, base + L.g2t, base + L.tf + 2 * n, base + L.qi, c->ver_table, base + L.off, n, 2 * n, 2, 1,
+                                                       base + L.gt);
   if (rc) return rc;
   // 6. == Gt::identity()?
-  rc = blsgpu_gt_is_identity_device(c, base + o_gt, n, is_one);
+  rc = blsgpu_gt_is_identity_device(c, base + L.gt, n, is_one);
   if (rc) return rc;
   KLAUNCH(k_bls_verdict, dim3(nblk(n, 256)), dim3(256), 0, c->stream, is_one, pk_ok, sig_ok, n, (uint8_t*)d_verdict);
   LAUNCHCHK();
   return BLSGPU_OK;
+}
+extern "C" int blsgpu_bls_verify_batch_device(blsgpu_ctx* c, int mode, const void* d_pk, const void* d_sig, const void* d_msgs, const void* d_offsets, size_t n, const void* d_dst,
+                                              size_t dst_len, void* d_verdict) { CTX_CLAIM(c);
+  if (int rc = verify_check(c, mode, d_pk, d_sig, d_offsets, n, d_dst, dst_len, 255, d_verdict)) return rc;
+  if (!n) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const VerifyLayout L = verify_layout(mode, n, false);
+  if (int rc = verify_begin(c, mode, n, L, d_msgs, d_offsets, d_dst, dst_len)) return rc;
+  uint8_t* base = c->ver.as<uint8_t>();
+  uint8_t* fl = base + L.fl;
+  uint8_t *a_inf = fl, *a_ok = fl + n, *b_inf = fl + 2 * n, *b_ok = fl + 3 * n;
+  // checked decoding (`from_compressed`: on the curve, in the subgroup) of both point arrays on the context's stream, which then waits for the side stream
+  // (ONE launch for both arrays: k_point_decode_both)
+  KLAUNCH(k_point_decode_both, dim3(2 * nblk(n, 128)), dim3(128), 0, c->stream, (const uint8_t*)(mode == 0 ? d_sig : d_pk), (u32*)(base + L.b), b_inf, b_ok,
+                     (const uint8_t*)(mode == 0 ? d_pk : d_sig), (u32*)(base + L.a), a_inf, a_ok, n, 3);
+  LAUNCHCHK();
+  return verify_finish(c, mode, n, L, d_verdict);
+}
+// Aggregate verification (blsgpu_bls_fast_aggregate_verify_batch): equation i takes the SUM of the keys of subset i where the plain form decodes one key.
+// The keys are decoded affine points the caller vouches for, so only the signatures are decoded here: on the second side stream, beside
+// the segmented sum on the context's stream (neither uses scratch of the other, nor of the hash).  The normalisation of the n sums shares
+// io_c / io_d with the normalisation of the hashes: it is queued behind the side stream's event.
+static int aggregate_check(blsgpu_ctx* c, int mode, const void* sig, const void* msg_offsets, size_t n, const void* dst, size_t dst_len, size_t dst_max, const void* verdict) {
+  if (!c || (n && (!sig || !msg_offsets || !verdict)) || (dst_len && !dst)) return bad("bls_fast_aggregate_verify_batch: NULL argument");
+  if (mode != 0 && mode != 1) return bad("bls_fast_aggregate_verify_batch: mode must be 0 (public keys in G1) or 1 (public keys in G2)");
+  if (dst_len > dst_max) return bad("bls_fast_aggregate_verify_batch_device: reduce a DST longer than 255 bytes on the host first");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_bls_fast_aggregate_verify_batch_device(blsgpu_ctx* c, int mode, const void* d_keys_xy, const void* d_keys_inf, size_t nkeys, const void* d_idx,
+                                                             const void* d_key_offsets, size_t total_keys, const void* d_sig, const void* d_msgs, const void* d_msg_offsets, size_t n,
+                                                             const void* d_dst, size_t dst_len, void* d_verdict) { CTX_CLAIM(c);
+  if (int rc = aggregate_check(c, mode, d_sig, d_msg_offsets, n, d_dst, dst_len, 255, d_verdict)) return rc;
+  {
+    GsumArgs a;
+    a.group = mode == 0 ? 1 : 2; a.xy = d_keys_xy; a.inf = d_keys_inf; a.npoints = nkeys; a.idx = d_idx; a.offsets = d_key_offsets; a.nseg = n; a.total = total_keys;
+    // (the sums go to the context's block, which is aligned: `out` is a stand-in here.  d_verdict is n bytes with no alignment rule, as in
+    // blsgpu_bls_verify_batch_device; aggregate_check has seen that it is not NULL.)
+    alignas(16) static const unsigned char aligned_stand_in[16] = {};
+    a.out = aligned_stand_in; a.device = true;
+    if (const char* why = gsum_check(a)) return bad(why);     // before anything is queued: the sum itself would refuse too late
+  }
+  if (!n) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const VerifyLayout L = verify_layout(mode, n, true);
+  if (int rc = verify_begin(c, mode, n, L, d_msgs, d_msg_offsets, d_dst, dst_len)) return rc;
+  uint8_t* base = c->ver.as<uint8_t>();
+  uint8_t* fl = base + L.fl;
+  uint8_t *a_inf = fl, *a_ok = fl + n, *b_inf = fl + 2 * n, *b_ok = fl + 3 * n;
+  uint8_t *pk_inf = mode == 0 ? a_inf : b_inf, *pk_ok = mode == 0 ? a_ok : b_ok, *sig_inf = mode == 0 ? b_inf : a_inf, *sig_ok = mode == 0 ? b_ok : a_ok;
+  void* pk_xy = base + (mode == 0 ? L.a : L.b);
+  void* sig_xy = base + (mode == 0 ? L.b : L.a);
+  hipStream_t main_stream = c->stream;
+  int rc;
+  {
+    // the signatures: `from_compressed` on the second side stream
+    c->stream = c->ver_stream[1];
+    hipError_t e = hipStreamWaitEvent(c->stream, c->ev_ver_side[0], 0);
+    rc = BLSGPU_OK;
+    if (e == hipSuccess) rc = mode == 0 ? point_decode_device<Fp2Policy>(c, d_sig, n, 1, 1, sig_xy, sig_inf, sig_ok) : point_decode_device<FpPolicy>(c, d_sig, n, 1, 1, sig_xy, sig_inf, sig_ok);
+    if (e == hipSuccess && !rc) e = hipEventRecord(c->ev_ver_side[2], c->stream);
+    c->stream = main_stream;
+    if (e != hipSuccess) return fail("bls_fast_aggregate_verify_batch: side stream", e, __LINE__);
+    if (rc) return rc;
+  }
+  // the aggregate keys: segmented sum, then (behind the hashes' normalisation) theirs; a summed key is always a valid key
+  rc = mode == 0 ? blsgpu_g1_sum_segments_device(c, d_keys_xy, d_keys_inf, nkeys, d_idx, d_key_offsets, n, total_keys, base + L.apk)
+                 : blsgpu_g2_sum_segments_device(c, d_keys_xy, d_keys_inf, nkeys, d_idx, d_key_offsets, n, total_keys, base + L.apk);
+  if (rc) return rc;
+  HIPCHK(hipMemsetAsync(pk_ok, 1, n, c->stream));
+  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_ver_side[1], 0));
+  rc = mode == 0 ? blsgpu_g1_batch_normalize_device(c, base + L.apk, n, pk_xy, pk_inf) : blsgpu_g2_batch_normalize_device(c, base + L.apk, n, pk_xy, pk_inf);
+  if (rc) return rc;
+  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_ver_side[2], 0));
+  return verify_finish(c, mode, n, L, d_verdict);
+}
+// host form: the key set stays where it is -- d_keys_xy / d_keys_inf are DEVICE pointers (a resident registry is the point of the call) --
+// and everything that changes from call to call comes from the host
+extern "C" int blsgpu_bls_fast_aggregate_verify_batch(blsgpu_ctx* c, int mode, const void* d_keys_xy, const void* d_keys_inf, size_t nkeys, const uint32_t* idx,
+                                                      const uint64_t* key_offsets, size_t total_keys, const uint8_t* sig, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n,
+                                                      const uint8_t* dst, size_t dst_len, uint8_t* verdict) { CTX_CLAIM(c);
+  if (int rc = aggregate_check(c, mode, sig, msg_offsets, n, dst, dst_len, (size_t)-1, verdict)) return rc;
+  {
+    GsumArgs a;
+    a.group = mode == 0 ? 1 : 2; a.xy = d_keys_xy; a.inf = d_keys_inf; a.npoints = nkeys; a.idx = idx; a.offsets = key_offsets; a.nseg = n; a.total = total_keys; a.out = verdict;
+    if (const char* why = gsum_check(a)) return bad(why);
+    if (const char* why = gsum_check_host(key_offsets, n, total_keys, idx, nkeys)) return bad(why);
+  }
+  if (!n) return BLSGPU_OK;
+  HostCall h(c);
+  void *m, *o, *d; u32 dlen;
+  if (int rc = stage_messages(h, "bls_fast_aggregate_verify_batch: message offsets must be non-decreasing", "bls_fast_aggregate_verify_batch: NULL argument", EXPAND_XMD_SHA256,
+                              msgs, msg_offsets, n, dst, dst_len, &m, &o, &d, &dlen)) return rc;
+  void* s = h.in(c->flags_b, sig, n * (mode == 0 ? 96 : 48));
+  void* ix = total_keys ? h.in(c->io_e, idx, total_keys * 4) : nullptr;
+  void* ko = h.in(c->io_out, key_offsets, (n + 1) * 8);
+  void* v = h.out(c->flags_a, verdict, n);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_bls_fast_aggregate_verify_batch_device(c, mode, d_keys_xy, d_keys_inf, nkeys, ix, ko, total_keys, s, m, o, n, d, dlen, v));
 }
 extern "C" int blsgpu_bls_verify_batch(blsgpu_ctx* c, int mode, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst,
                                        size_t dst_len, uint8_t* verdict) { CTX_CLAIM(c);

@@ -5,6 +5,7 @@
 #include "mulbatch.hip.h"
 #include "msm_seg.hip.h"
 #include "gntt.hip.h"
+#include "gsum.hip.h"
 
 // ---------------------------------------------------------------------------------------------------
 // bases
@@ -938,6 +939,58 @@ extern "C" int blsgpu_g1_sum_device(blsgpu_ctx* c, const void* xyz, size_t n, vo
 extern "C" int blsgpu_g2_sum_device(blsgpu_ctx* c, const void* xyz, size_t n, void* out) { CTX_CLAIM(c); return proj_sum_device<Fp2Policy>(c, xyz, n, out); }
 extern "C" int blsgpu_g1_sum(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint64_t* out) { CTX_CLAIM(c); return proj_sum<FpPolicy>(c, xyz, n, out); }
 extern "C" int blsgpu_g2_sum(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint64_t* out) { CTX_CLAIM(c); return proj_sum<Fp2Policy>(c, xyz, n, out); }
+
+// segmented, gathered sums (gsum.hip.h): the launches of gsum_plan.h on the context's stream, asynchronous
+template <class F>
+static int sum_segments_device(blsgpu_ctx* c, const void* d_xy, const void* d_inf, size_t npoints, const void* d_idx, const void* d_offsets, size_t nseg, size_t total,
+                               void* d_out) {
+  if (!c) return bad("sum_segments: ctx is NULL");
+  GsumArgs a;
+  a.group = GroupTag<F>::id; a.xy = d_xy; a.inf = d_inf; a.npoints = npoints; a.idx = d_idx; a.offsets = d_offsets; a.nseg = nseg; a.total = total; a.out = d_out; a.device = true;
+  if (const char* why = gsum_check(a)) return bad(why);
+  if (!nseg) return BLSGPU_OK;
+  const GsumPlan plan = gsum_plan(a.group, nseg, total);
+  if (!plan.ok) return bad("sum_segments: the sizes are out of range");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->gsum_part.reserve(plan.part_bytes + 16) || c->gsum_meta.reserve(plan.meta_bytes + 16)) { g_err = "hipMalloc failed"; return BLSGPU_ERR_HIP; }
+  const unsigned long long* off = (const unsigned long long*)d_offsets;
+  if (plan.chunks_grid)
+    KLAUNCH(k_gsum_chunks<F>, dim3(plan.chunks_grid), dim3(plan.block), plan.lds, c->stream, (const u32*)d_xy, (const uint8_t*)d_inf, (u32)npoints, (const u32*)d_idx, off,
+            (u32)nseg, (u32)total, plan.terms, (u32*)d_out, c->gsum_part.as<u32>(), c->gsum_meta.as<u32>(), c->status_word);
+  KLAUNCH(k_gsum_combine<F>, dim3(plan.combine_grid), dim3(plan.block), plan.lds, c->stream, off, (u32)nseg, (u32)total, plan.chunk, plan.nchunks,
+          (const u32*)c->gsum_part.as<u32>(), (const u32*)c->gsum_meta.as<u32>(), (u32*)d_out);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+template <class F>
+static int sum_segments(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t npoints, const uint32_t* idx, const uint64_t* offsets, size_t nseg, size_t total,
+                        uint64_t* out) {
+  if (!c) return bad("sum_segments: ctx is NULL");
+  GsumArgs a;
+  a.group = GroupTag<F>::id; a.xy = xy; a.inf = inf; a.npoints = npoints; a.idx = idx; a.offsets = offsets; a.nseg = nseg; a.total = total; a.out = out;
+  if (const char* why = gsum_check(a)) return bad(why);
+  if (const char* why = gsum_check_host(offsets, nseg, total, idx, npoints)) return bad(why);
+  if (!nseg) return BLSGPU_OK;
+  constexpr int WW = Wire<F>::WORDS;
+  HostCall h(c);
+  // (without idx only the first `total` points can be named)
+  const size_t used = total ? (idx ? npoints : total) : 0;
+  void* dxy = h.in(c->io_a, xy, used * 2 * WW * 4);
+  void* dinf = h.in(c->flags_a, inf, used);
+  void* didx = total ? h.in(c->io_b, idx, total * 4) : nullptr;
+  void* doff = h.in(c->io_e, offsets, (nseg + 1) * 8);
+  void* o = h.out(c->io_out, out, nseg * 3 * WW * 4);
+  if (h.rc) return h.rc;
+  return h.finish(sum_segments_device<F>(c, dxy, dinf, used, didx, doff, nseg, total, o));
+}
+extern "C" int blsgpu_g1_sum_segments_device(blsgpu_ctx* c, const void* xy, const void* inf, size_t npoints, const void* idx, const void* offsets, size_t nseg, size_t total,
+                                             void* out) { CTX_CLAIM(c); return sum_segments_device<FpPolicy>(c, xy, inf, npoints, idx, offsets, nseg, total, out); }
+extern "C" int blsgpu_g2_sum_segments_device(blsgpu_ctx* c, const void* xy, const void* inf, size_t npoints, const void* idx, const void* offsets, size_t nseg, size_t total,
+                                             void* out) { CTX_CLAIM(c); return sum_segments_device<Fp2Policy>(c, xy, inf, npoints, idx, offsets, nseg, total, out); }
+extern "C" int blsgpu_g1_sum_segments(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t npoints, const uint32_t* idx, const uint64_t* offsets, size_t nseg,
+                                      size_t total, uint64_t* out) { CTX_CLAIM(c); return sum_segments<FpPolicy>(c, xy, inf, npoints, idx, offsets, nseg, total, out); }
+extern "C" int blsgpu_g2_sum_segments(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t npoints, const uint32_t* idx, const uint64_t* offsets, size_t nseg,
+                                      size_t total, uint64_t* out) { CTX_CLAIM(c); return sum_segments<Fp2Policy>(c, xy, inf, npoints, idx, offsets, nseg, total, out); }
 
 // device core: projective wire records in device memory -> affine wire coordinates + infinity bytes in device memory (asynchronous)
 // (the host forms take no infinity array when the caller does not want one: inf_ok = true)

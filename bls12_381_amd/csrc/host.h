@@ -3,7 +3,7 @@
 //
 //   api_ctx.hip      contexts, streams, status, diagnostics, staged uploads, field / point self-test hooks
 //   api_msm.hip      resident bases, MSM, batched scalar multiplication, sums, batch_normalize,       (msm.hip.h, mulbatch.hip.h,
-//                    group transforms                                                                   gntt.hip.h)
+//                    group transforms, segmented point sums                                             gntt.hip.h, gsum.hip.h)
 //   api_pairing.hip  pairings, Miller loops, G2Prepared, final exponentiation, Gt, Fp6 / Fp12 hooks   (pairing / quad / prep / wide)
 //   api_aux.hip      Fr vectors and transform, hash-to-curve, point codecs, bulk BLS verification      (fr / h2c / codec)
 //   api_group.hip    device groups: one process driving several GPUs (host code only)
@@ -33,6 +33,7 @@
 #include "fr_poseidon_plan.h"
 #include "fr_expr_plan.h"
 #include "fr_lookup_plan.h"
+#include "gsum_plan.h"
 
 using namespace bls;
 
@@ -229,6 +230,7 @@ struct blsgpu_ctx {
   bool frm_lds_ready = false;           // ... and the round kernels' dynamic LDS
   DevBuf frb_rec, frb_rowrec;           // blsgpu_fr_bary_*: one record per tile of a row longer than a tile, one per such row (fr_bary_plan.h)
   bool frb_lds_ready = false;           // ... and the tile kernels' dynamic LDS
+  DevBuf gsum_part, gsum_meta;          // blsgpu_g{1,2}_sum_segments_device: two partial records and two segment numbers per chunk (gsum_plan.h)
   DevBuf frp_nodes;                     // blsgpu_fr_poseidon_merkle_device with nodes == NULL: the levels below the roots (fr_poseidon_plan.h)
 };
 

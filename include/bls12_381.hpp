@@ -123,6 +123,24 @@ template <int G> struct Projective {
   }
 };
 
+// subsets.iter().map(|s| s.iter().map(|&i| points[i]).sum()) in ONE call (blsgpu_g{1,2}_sum_segments; `Sum`, src/g1.rs:161-171): the
+// aggregate public keys of many subsets of one key set.  An empty subset gives the identity; an index may repeat.
+template <int G> std::vector<Projective<G>> sum_segments(const std::vector<Affine<G>>& points, const std::vector<std::vector<uint32_t>>& subsets) {
+  const size_t n = points.size(), nseg = subsets.size();
+  std::vector<Projective<G>> out(nseg);
+  if (!nseg) return out;
+  std::vector<uint64_t> xy(n * Affine<G>::W + 1), offs(nseg + 1, 0); std::vector<uint8_t> inf(n + 1); std::vector<uint32_t> idx;
+  for (size_t i = 0; i < n; i++) { std::memcpy(xy.data() + i * Affine<G>::W, points[i].xy.data(), Affine<G>::W * 8); inf[i] = points[i].infinity; }
+  for (size_t s = 0; s < nseg; s++) { idx.insert(idx.end(), subsets[s].begin(), subsets[s].end()); offs[s + 1] = idx.size(); }
+  const size_t total = idx.size();
+  idx.push_back(0);
+  std::vector<uint64_t> o(nseg * Projective<G>::W);
+  check((G == 1 ? blsgpu_g1_sum_segments : blsgpu_g2_sum_segments)(Context::instance().handle(), xy.data(), inf.data(), n, idx.data(), offs.data(), nseg, total, o.data()),
+        "sum_segments");
+  for (size_t s = 0; s < nseg; s++) std::memcpy(out[s].xyz.data(), o.data() + s * Projective<G>::W, Projective<G>::W * 8);
+  return out;
+}
+
 // bases.iter().zip(scalars).map(|(p, s)| p * s).sum()
 template <int G> Projective<G> msm(const std::vector<Affine<G>>& bases, const std::vector<Scalar>& scalars) {
   if (bases.size() != scalars.size()) throw std::invalid_argument("msm: bases and scalars differ in length");
@@ -156,6 +174,8 @@ using G1Affine = Affine<1>;
 using G2Affine = Affine<2>;
 using G1Projective = Projective<1>;
 using G2Projective = Projective<2>;
+inline std::vector<G1Projective> g1_sum_segments(const std::vector<G1Affine>& points, const std::vector<std::vector<uint32_t>>& subsets) { return sum_segments<1>(points, subsets); }
+inline std::vector<G2Projective> g2_sum_segments(const std::vector<G2Affine>& points, const std::vector<std::vector<uint32_t>>& subsets) { return sum_segments<2>(points, subsets); }
 
 // src/pairings.rs:204-337 -- written additively like the reference: + is the Fp12 product, unary - the conjugate
 struct Gt {
@@ -301,6 +321,26 @@ inline std::vector<uint8_t> bls_verify_batch(bool keys_in_g1, const std::vector<
   for (size_t i = 0; i < n; i++) { blob += msgs[i]; offs[i + 1] = blob.size(); }
   check(blsgpu_bls_verify_batch(Context::instance().handle(), keys_in_g1 ? 0 : 1, pk_bytes.data(), sig_bytes.data(), (const uint8_t*)blob.data(), offs.data(), n,
                                 (const uint8_t*)dst.data(), dst.size(), verdict.data()), "bls_verify_batch");
+  return verdict;
+}
+
+// Aggregate verification (blsgpu_bls_fast_aggregate_verify_batch): signature i over msgs[i] by the keys subsets[i] of a key set that is
+// RESIDENT on the device -- d_keys_xy / d_keys_infinity are device pointers to nkeys decoded affine points (G1 if keys_in_g1), decoded and
+// subgroup-checked once by the caller.  Verdicts: 1 valid, 0 invalid, 3 bad signature encoding.  An empty subset takes part as an identity key.
+inline std::vector<uint8_t> bls_fast_aggregate_verify(bool keys_in_g1, const void* d_keys_xy, const void* d_keys_infinity, size_t nkeys,
+                                                      const std::vector<std::vector<uint32_t>>& subsets, const std::vector<uint8_t>& sig_bytes,
+                                                      const std::vector<std::string>& msgs, const std::string& dst) {
+  const size_t n = msgs.size();
+  if (subsets.size() != n || sig_bytes.size() != n * (keys_in_g1 ? 96 : 48)) throw std::invalid_argument("bls_fast_aggregate_verify: lengths");
+  std::vector<uint8_t> verdict(n);
+  if (!n) return verdict;
+  std::vector<uint64_t> offs(n + 1, 0), koffs(n + 1, 0); std::string blob; std::vector<uint32_t> idx;
+  for (size_t i = 0; i < n; i++) { blob += msgs[i]; offs[i + 1] = blob.size(); idx.insert(idx.end(), subsets[i].begin(), subsets[i].end()); koffs[i + 1] = idx.size(); }
+  const size_t total = idx.size();
+  idx.push_back(0);
+  check(blsgpu_bls_fast_aggregate_verify_batch(Context::instance().handle(), keys_in_g1 ? 0 : 1, d_keys_xy, d_keys_infinity, nkeys, idx.data(), koffs.data(), total,
+                                               sig_bytes.data(), (const uint8_t*)blob.data(), offs.data(), n, (const uint8_t*)dst.data(), dst.size(), verdict.data()),
+        "bls_fast_aggregate_verify");
   return verdict;
 }
 

@@ -239,6 +239,35 @@ int blsgpu_g2_sum(blsgpu_ctx* ctx, const uint64_t* xyz, size_t n, uint64_t out_x
 /* Same with device pointers, asynchronous on the context's stream (no host round trip after the all-gather). */
 int blsgpu_g1_sum_device(blsgpu_ctx* ctx, const void* d_xyz, size_t n, void* d_out_xyz);
 int blsgpu_g2_sum_device(blsgpu_ctx* ctx, const void* d_xyz, size_t n, void* d_out_xyz);
+/* Segmented, gathered sums: out_xyz[s] = sum of the points idx[t], t in [offsets[s], offsets[s + 1]), for nseg segments in ONE call
+ * (`impl Sum for G1Projective` over `add_mixed`, src/g1.rs:161-171, 715-752; the same in g2.rs) -- the aggregate public keys of many
+ * subsets of a resident key set, the per-column sums of a gathered commitment.
+ *   points   npoints affine points in the wire format plus an infinity byte each: what `*_from_bytes_batch_device` and
+ *            `*_batch_normalize_device` write.  npoints < 2^32.
+ *   idx      `total` u32 indices into the points, or NULL: term t is then point t, and total <= npoints.  An index may repeat, within a
+ *            segment and across segments.
+ *   offsets  nseg + 1 u64 in CSR form: offsets[0] = 0, non-decreasing, offsets[nseg] = total; total <= 2^28, passed by value because
+ *            the device form cannot read it back without stalling the stream (as `total_terms` of multi_miller_loop_many_device).
+ *   out_xyz  nseg projective points (18 / 36 u64 each), the input form of `*_batch_normalize[_device]`.
+ * The result is the group element: identity entries are skipped, an empty segment gives `identity()` = (0 : 1 : 0), P + P doubles,
+ * P + (-P) is the identity, and a curve point outside the subgroup adds like any other (the complete formulas: no precondition).  The
+ * projective representative is unspecified; compare after batch_normalize, as for mul_batch.
+ * BLSGPU_ERR_ARG with nothing launched: a NULL array with work to do, total > 2^28, nseg > 2^28, npoints >= 2^32, total > npoints without
+ * idx; in the host forms also offsets that do not start at 0, decrease or do not end at total, and an index >= npoints.
+ * The device forms (8-byte aligned d_xy / d_offsets / d_out_xyz, 4-byte aligned d_idx) are asynchronous on the context's stream and use the
+ * context's scratch.  They cannot refuse what only the device sees: an offset beyond total is clamped to it (offsets[0] is read as 0,
+ * offsets[nseg] as total); offsets that DECREASE are not repaired -- nothing outside the caller's arrays is read or written, but the
+ * values of the segments involved are unspecified (two workgroups may write one of them); and an index >= npoints is NEVER
+ * dereferenced -- its term is skipped and a sticky flag is set, so that the next blsgpu_synchronize returns BLSGPU_ERR_ARG (as for a
+ * non-canonical scalar); that segment's value is unspecified, every other is right. */
+int blsgpu_g1_sum_segments(blsgpu_ctx* ctx, const uint64_t* xy, const uint8_t* infinity, size_t npoints, const uint32_t* idx, const uint64_t* offsets, size_t nseg,
+                           size_t total, uint64_t* out_xyz);
+int blsgpu_g2_sum_segments(blsgpu_ctx* ctx, const uint64_t* xy, const uint8_t* infinity, size_t npoints, const uint32_t* idx, const uint64_t* offsets, size_t nseg,
+                           size_t total, uint64_t* out_xyz);
+int blsgpu_g1_sum_segments_device(blsgpu_ctx* ctx, const void* d_xy, const void* d_infinity, size_t npoints, const void* d_idx, const void* d_offsets, size_t nseg,
+                                  size_t total, void* d_out_xyz);
+int blsgpu_g2_sum_segments_device(blsgpu_ctx* ctx, const void* d_xy, const void* d_infinity, size_t npoints, const void* d_idx, const void* d_offsets, size_t nseg,
+                                  size_t total, void* d_out_xyz);
 /* Projective -> affine for n points (`G1Projective::batch_normalize`, src/g1.rs:806-839; `G1Affine::from`,
  * :49-63).  Identity maps to x = 0, y = 1 (Montgomery one), infinity = 1. */
 int blsgpu_g1_batch_normalize(blsgpu_ctx* ctx, const uint64_t* xyz, size_t n, uint64_t* xy, uint8_t* infinity);
@@ -954,6 +983,27 @@ int blsgpu_bls_verify_batch(blsgpu_ctx* ctx, int mode, const uint8_t* pk_bytes, 
                             const uint8_t* dst, size_t dst_len, uint8_t* verdict);
 int blsgpu_bls_verify_batch_device(blsgpu_ctx* ctx, int mode, const void* d_pk_bytes, const void* d_sig_bytes, const void* d_msgs, const void* d_offsets, size_t n,
                                    const void* d_dst, size_t dst_len, void* d_verdict);
+/* Aggregate verification: signature i is ONE signature over ONE message by a SUBSET of a long-lived key set (the shape of
+ * FastAggregateVerify: consensus attestations, threshold committees).  Equation i is that of blsgpu_bls_verify_batch with
+ * apk_i = sum of the keys idx[t], t in [key_offsets[i], key_offsets[i + 1]), in place of pk_i:
+ *   mode 0:  e(apk_i, H(m_i)) == e(G1, sig_i)          mode 1:  e(sig_i, G2) == e(H(m_i), apk_i)
+ * The keys are DECODED affine points resident in device memory (d_keys_xy, d_keys_infinity: nkeys points of G1 in mode 0, of G2 in
+ * mode 1, as blsgpu_g{1,2}_from_bytes_batch_device writes them): the caller decodes and subgroup-checks a registry ONCE with
+ * checked = 1, keeps it, and vouches for it -- nothing about a key is re-checked per call.  idx / key_offsets / total_keys are those of
+ * blsgpu_g{1,2}_sum_segments (`impl Sum`, src/g1.rs:161-171), with the same refusals and, in the device form, the same sticky flag for an
+ * index outside the set (the key arrays, d_idx and d_key_offsets are aligned as there; d_verdict is n bytes at any address); signatures,
+ * messages, dst and the rest of the chain are those of blsgpu_bls_verify_batch (the two share every
+ * stage behind the decoding).  In the host form the key set STAYS a pair of device pointers; every other argument is a host pointer.
+ * verdict[i]: 1 = the equation holds, 0 = it does not, 3 = the signature is not a valid encoding of a subgroup point; 2 is never
+ * produced.  An EMPTY subset, or one whose keys sum to the identity, takes part as an identity public key does in
+ * blsgpu_bls_verify_batch: its pairing is Gt::identity(), so the equation holds exactly for the identity signature.  Rejecting such an
+ * aggregate is the caller's policy (`KeyValidate`), as is proof of possession against rogue keys. */
+int blsgpu_bls_fast_aggregate_verify_batch(blsgpu_ctx* ctx, int mode, const void* d_keys_xy, const void* d_keys_infinity, size_t nkeys, const uint32_t* idx,
+                                           const uint64_t* key_offsets, size_t total_keys, const uint8_t* sig_bytes, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n,
+                                           const uint8_t* dst, size_t dst_len, uint8_t* verdict);
+int blsgpu_bls_fast_aggregate_verify_batch_device(blsgpu_ctx* ctx, int mode, const void* d_keys_xy, const void* d_keys_infinity, size_t nkeys, const void* d_idx,
+                                                  const void* d_key_offsets, size_t total_keys, const void* d_sig_bytes, const void* d_msgs, const void* d_msg_offsets, size_t n,
+                                                  const void* d_dst, size_t dst_len, void* d_verdict);
 
 #ifdef __cplusplus
 }
