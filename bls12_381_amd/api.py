@@ -1120,6 +1120,79 @@ class Context:
     def fr_batch_invert_device(self, d_in, n, d_out, d_flags=None):
         check(self.lib.blsgpu_fr_batch_invert_device(self.h, d_in, n, d_out, d_flags), "fr_batch_invert_device")
 
+    def _fr_ids(self, v, n, what):
+        """n scalars as (n, 4) u64 Montgomery limbs: such an array as it is, or integers (participant ids) through fr_from_bytes"""
+        if isinstance(v, np.ndarray) and v.dtype == np.uint64 and v.ndim == 2 and v.shape[1] == 4:
+            a = np.ascontiguousarray(v)
+        else:
+            ints = [int(x) for x in np.asarray(v, dtype=object).reshape(-1)]
+            if any(x < 0 or x >= (1 << 256) for x in ints):
+                raise ValueError("%s: an integer does not fit 32 bytes" % what)
+            raw = np.frombuffer(b"".join(x.to_bytes(32, "little") for x in ints), dtype=np.uint8).reshape(-1, 32)
+            a, ok = self.fr_from_bytes(raw) if ints else (np.zeros((0, 4), dtype=np.uint64), np.ones(0, dtype=np.uint8))
+            if not ok.all():
+                raise ValueError("%s: an integer is not below r" % what)
+        if a.shape[0] != n:
+            raise ValueError("%s: expected %d scalars" % (what, n))
+        return a
+
+    @staticmethod
+    def _lagrange_offsets(offsets, what):
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError("%s: offsets needs nseg + 1 entries" % what)
+        return off, off.shape[0] - 1, int(off[-1])
+
+    def fr_lagrange_segments(self, nodes, offsets, points=None, values=None, want_lambda=True, want_y=None):
+        """Lagrange coefficients at arbitrary nodes (blsgpu_fr_lagrange_segments): nodes (total, 4) u64 Montgomery limbs or integers
+        (participant ids), offsets (nseg + 1) u32 in CSR form, points nseg scalars (limbs or integers) or None (every z = 0), values like
+        nodes or None.  -> (lambda (total, 4) or None, y (nseg, 4) or None, distinct flags (nseg,) u8): lambda_i = prod_{j != i}
+        (z - x_j) * inv0(prod_{j != i} (x_i - x_j)), y[s] = sum lambda_i values_i; want_y defaults to `values is not None`."""
+        off, nseg, total = self._lagrange_offsets(offsets, "fr_lagrange_segments")
+        x = self._fr_ids(nodes, total, "fr_lagrange_segments: nodes")
+        z = None if points is None else self._fr_ids(points, nseg, "fr_lagrange_segments: points")
+        v = None if values is None else self._fr_ids(values, total, "fr_lagrange_segments: values")
+        if want_y is None:
+            want_y = values is not None
+        lam = np.zeros((total, 4), dtype=np.uint64) if want_lambda else None
+        y = np.zeros((nseg, 4), dtype=np.uint64) if want_y else None
+        flags = np.ones(nseg, dtype=np.uint8)
+        check(self.lib.blsgpu_fr_lagrange_segments(self.h, _ptr(x) if total else None, _ptr(off), nseg, _ptr(z), _ptr(v) if total else None, _ptr(lam), _ptr(y),
+                                                   _ptr(flags) if nseg else None), "fr_lagrange_segments")
+        return lam, y, flags
+
+    def fr_lagrange_segments_device(self, d_nodes, d_offsets, nseg, total, d_points=None, d_values=None, d_lambda=None, d_y=None, d_flags=None):
+        """device form: asynchronous on the context's stream; a segment that breaks the offsets contract writes nothing and is reported
+        by synchronize()"""
+        vp = lambda p: ctypes.c_void_p(p) if p else None
+        check(self.lib.blsgpu_fr_lagrange_segments_device(self.h, vp(d_nodes), vp(d_offsets), nseg, total, vp(d_points), vp(d_values), vp(d_lambda), vp(d_y), vp(d_flags)),
+              "fr_lagrange_segments_device")
+
+    def lagrange_combine(self, group, xy, infinity, nodes, offsets, points=None):
+        """Interpolation in the exponent (blsgpu_g{1,2}_lagrange_combine): xy (total, 12 | 24) u64 affine wire shares with their infinity
+        bytes, nodes / offsets / points as for fr_lagrange_segments.  -> ((nseg, 18 | 36) u64 projective points, segment s the sum of
+        lambda_i * share_i, and the distinct flags)."""
+        w = 12 if group == 1 else 24
+        off, nseg, total = self._lagrange_offsets(offsets, "lagrange_combine")
+        xy = _u64(xy, (-1, w))
+        if xy.shape[0] != total:
+            raise ValueError("lagrange_combine: expected offsets[-1] shares")
+        inf = np.zeros(total, dtype=np.uint8) if infinity is None else _flags(infinity, total)
+        x = self._fr_ids(nodes, total, "lagrange_combine: nodes")
+        z = None if points is None else self._fr_ids(points, nseg, "lagrange_combine: points")
+        out = np.zeros((nseg, 18 if group == 1 else 36), dtype=np.uint64)
+        flags = np.ones(nseg, dtype=np.uint8)
+        fn = self.lib.blsgpu_g1_lagrange_combine if group == 1 else self.lib.blsgpu_g2_lagrange_combine
+        check(fn(self.h, _ptr(xy) if total else None, _ptr(inf) if total else None, _ptr(x) if total else None, _ptr(off), nseg, _ptr(z), _ptr(out) if nseg else None,
+                 _ptr(flags) if nseg else None), "lagrange_combine")
+        return out, flags
+
+    def lagrange_combine_device(self, group, d_xy, d_inf, d_nodes, d_offsets, nseg, total, d_points, d_out, d_flags=None):
+        """device form of lagrange_combine: three stages on the context's stream, no synchronisation"""
+        fn = self.lib.blsgpu_g1_lagrange_combine_device if group == 1 else self.lib.blsgpu_g2_lagrange_combine_device
+        vp = lambda p: ctypes.c_void_p(p) if p else None
+        check(fn(self.h, vp(d_xy), vp(d_inf), vp(d_nodes), vp(d_offsets), nseg, total, vp(d_points), vp(d_out), vp(d_flags)), "lagrange_combine_device")
+
     @staticmethod
     def _frac_set(what, name, s, shape=None):
         """a column set as a contiguous (c, k, len, 4) u64 array (a (c, len, 4) array is k = 1); None stays None"""

@@ -11,6 +11,7 @@
 #include "fr_poseidon.hip.h"
 #include "fr_expr.hip.h"
 #include "fr_lookup.hip.h"
+#include "fr_lagrange.hip.h"
 #include "h2c.hip.h"
 #include "expand_kernels.hip.h"
 #include "codec.hip.h"
@@ -575,6 +576,59 @@ extern "C" int blsgpu_fr_batch_invert(blsgpu_ctx* c, const uint64_t* values, siz
   void* f = nonzero_flags ? h.out(c->flags_a, nonzero_flags, n) : nullptr;
   if (h.rc) return h.rc;
   return h.finish(blsgpu_fr_batch_invert_device(c, di, n, o, f));
+}
+
+// ---- Lagrange coefficients at arbitrary nodes (fr_lagrange.hip.h; fr_lagrange_plan.h decides the launch) ------------------------------
+// ONE launch on the context's stream, a function of (nseg, total) alone; scratch of its own.  The caller has run flg_check.
+int fr_lagrange_launch(blsgpu_ctx* c, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total, const void* d_points, const void* d_values, void* d_lambda, void* d_y,
+                       void* d_flags) {
+  if (!nseg) return BLSGPU_OK;
+  const FlgPlan plan = flg_plan(nseg, total, d_lambda != nullptr, c->diag.flg_shape);
+  if (!plan.ok) return bad("fr_lagrange_segments: the sizes are out of range");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->flg_pre.reserve(plan.pre_bytes + 16) || c->flg_work.reserve(plan.work_bytes + 16)) { g_err = "hipMalloc(fr lagrange scratch) failed"; return BLSGPU_ERR_HIP; }
+  if (plan.shape == FLG_SHAPE_BLOCK)
+    KLAUNCH((k_flg_segments<FLG_R, true>), dim3(plan.grid), dim3(plan.block), plan.lds, c->stream, (const u32*)d_nodes, (const u32*)d_offsets, (u32)nseg, (u32)total,
+            (const u32*)d_points, (const u32*)d_values, (u32*)d_lambda, (u32*)d_y, (uint8_t*)d_flags, c->flg_work.as<u32>(), c->flg_pre.as<u32>(), plan.team, plan.tile, c->status_word);
+  else
+    KLAUNCH((k_flg_segments<FLG_R, false>), dim3(plan.grid), dim3(plan.block), plan.lds, c->stream, (const u32*)d_nodes, (const u32*)d_offsets, (u32)nseg, (u32)total,
+            (const u32*)d_points, (const u32*)d_values, (u32*)d_lambda, (u32*)d_y, (uint8_t*)d_flags, c->flg_work.as<u32>(), c->flg_pre.as<u32>(), plan.team, plan.tile, c->status_word);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+static FlgArgs flg_args(const void* nodes, const void* offsets, size_t nseg, size_t total, const void* points, const void* values, const void* lambda, const void* y,
+                        const void* flags, bool device) {
+  FlgArgs a;
+  a.nodes = nodes; a.offsets = offsets; a.nseg = nseg; a.total = total; a.points = points; a.values = values; a.lambda = lambda; a.y = y; a.flags = flags; a.device = device;
+  return a;
+}
+extern "C" int blsgpu_fr_lagrange_segments_device(blsgpu_ctx* c, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total, const void* d_points, const void* d_values,
+                                                  void* d_lambda, void* d_y, void* d_distinct_flags) { CTX_CLAIM(c);
+  if (!c) return bad("fr_lagrange_segments: NULL context");
+  if (const char* why = flg_check(flg_args(d_nodes, d_offsets, nseg, total, d_points, d_values, d_lambda, d_y, d_distinct_flags, true))) return bad(why);
+  return fr_lagrange_launch(c, d_nodes, d_offsets, nseg, total, d_points, d_values, d_lambda, d_y, d_distinct_flags);
+}
+extern "C" int blsgpu_fr_lagrange_segments(blsgpu_ctx* c, const uint64_t* nodes, const uint32_t* offsets, size_t nseg, const uint64_t* points, const uint64_t* values,
+                                           uint64_t* lambda, uint64_t* y, uint8_t* distinct_flags) { CTX_CLAIM(c);
+  if (!c) return bad("fr_lagrange_segments: NULL context");
+  if (nseg > FLG_MAX_SEGS) return bad("fr_lagrange_segments: nseg must not exceed 2^27");
+  if (nseg && !offsets) return bad("fr_lagrange_segments: NULL offsets with segments to do");
+  const size_t total = nseg ? offsets[nseg] : 0;
+  if (const char* why = flg_check(flg_args(nodes, offsets, nseg, total, points, values, lambda, y, distinct_flags, false))) return bad(why);
+  if (const char* why = flg_check_host(offsets, nseg, total)) return bad(why);
+  if (!nseg) return BLSGPU_OK;
+  HostCall h(c);
+  void* dn = h.in(c->io_a, nodes, total * 32);
+  void* dv = h.in(c->io_b, values, total * 32);
+  void* doff = h.in(c->io_e, offsets, (nseg + 1) * 4);
+  void* dp = h.in(c->io_f, points, nseg * 32);
+  // lambda and y share the output staging: total scalars, then nseg
+  u32* o = (u32*)h.out(c->io_out, nullptr, (total + nseg) * 32);
+  void* f = distinct_flags ? h.out(c->flags_a, distinct_flags, nseg) : nullptr;
+  if (h.rc) return h.rc;
+  if (lambda && total) h.back[h.nback++] = {lambda, o, total * 32};
+  if (y) h.back[h.nback++] = {y, o + total * 8, nseg * 32};
+  return h.finish(fr_lagrange_launch(c, dn, doff, nseg, total, dp, dv, lambda ? (void*)o : nullptr, y ? (void*)(o + total * 8) : nullptr, f));
 }
 
 // two byte ranges share a byte (the fraction scans and the openings refuse such outputs)

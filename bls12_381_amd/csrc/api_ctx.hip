@@ -205,7 +205,7 @@ extern "C" void blsgpu_destroy(blsgpu_ctx* c) {
   hipDeviceSynchronize();
   if (c->d_status) hipFree(c->d_status);
   if (c->d_wide) hipFree(c->d_wide);
-  DevBuf* bufs[] = {&c->result, &c->io_a, &c->io_b, &c->io_c, &c->io_d, &c->io_e, &c->io_f, &c->io_out, &c->flags_a, &c->flags_b, &c->mml_vals, &c->fr_tw[0], &c->fr_tw[1], &c->fr_tmp, &c->fr_ninv, &c->fr_cs[0], &c->fr_cs[1], &c->fb_table[0], &c->fb_table[1], &c->fb_stage, &c->mmlp_work, &c->mmlp_out, &c->gt_one, &c->ver, &c->fold_c, &c->fold_d, &c->fold_result, &c->h2c_uniform, &c->seg_wsum, &c->seg_rec, &c->frs_agg[0], &c->frs_agg[1], &c->frs_carry[0], &c->frs_carry[1], &c->frs_lane, &c->frsp_head, &c->frsp_tail, &c->frsp_meta, &c->frm_rec, &c->frm_scratch, &c->frb_rec, &c->frb_rowrec, &c->frp_nodes, &c->gsum_part, &c->gsum_meta};
+  DevBuf* bufs[] = {&c->result, &c->io_a, &c->io_b, &c->io_c, &c->io_d, &c->io_e, &c->io_f, &c->io_out, &c->flags_a, &c->flags_b, &c->mml_vals, &c->fr_tw[0], &c->fr_tw[1], &c->fr_tmp, &c->fr_ninv, &c->fr_cs[0], &c->fr_cs[1], &c->fb_table[0], &c->fb_table[1], &c->fb_stage, &c->mmlp_work, &c->mmlp_out, &c->gt_one, &c->ver, &c->fold_c, &c->fold_d, &c->fold_result, &c->h2c_uniform, &c->seg_wsum, &c->seg_rec, &c->frs_agg[0], &c->frs_agg[1], &c->frs_carry[0], &c->frs_carry[1], &c->frs_lane, &c->frsp_head, &c->frsp_tail, &c->frsp_meta, &c->frm_rec, &c->frm_scratch, &c->frb_rec, &c->frb_rowrec, &c->frp_nodes, &c->gsum_part, &c->gsum_meta, &c->flg_pre, &c->flg_work, &c->flg_lambda, &c->flg_prod};
   for (auto b : bufs) b->release();
   for (auto& sl : c->slot) {
     DevBuf* sb[] = {&sl.ent, &sl.sorted, &sl.hist, &sl.offs, &sl.cursor, &sl.bsum, &sl.items, &sl.heavy, &sl.ctrl, &sl.glv,
@@ -250,6 +250,7 @@ static int take_status(blsgpu_ctx* c) {
     if (st & 2u) return bad("multi_miller_loop_many_device: a segment is longer than the max_seg_terms the caller passed (its value is unspecified)");
     if (st & 4u) return bad("multi_miller_loop_prepared: a q_index lies outside the prepared table (the term was skipped)");
     if (st & GSUM_STATUS_BAD) return bad("sum_segments_device: an index lies outside the point set (the term was skipped, that segment's value is unspecified)");
+    if (st & FLG_STATUS_BAD) return bad("fr_lagrange_segments_device / lagrange_combine_device: a segment has decreasing offsets, more than BLSGPU_FR_LAGRANGE_LEN_MAX nodes or ends beyond total (nothing of it was written)");
     if (st & 8u) return bad("msm_segments_device: a segment has decreasing offsets, more than SEG_LEN_MAX points or bases outside the resident set (its value is unspecified)");
     return bad("msm: a scalar is not canonical (>= r); Scalar::to_bytes never produces such bytes (scalar.rs:284-296)");
   }

@@ -6,6 +6,7 @@
 #include "msm_seg.hip.h"
 #include "gntt.hip.h"
 #include "gsum.hip.h"
+#include "lagrange_combine.hip.h"
 
 // ---------------------------------------------------------------------------------------------------
 // bases
@@ -991,6 +992,73 @@ extern "C" int blsgpu_g1_sum_segments(blsgpu_ctx* c, const uint64_t* xy, const u
                                       size_t total, uint64_t* out) { CTX_CLAIM(c); return sum_segments<FpPolicy>(c, xy, inf, npoints, idx, offsets, nseg, total, out); }
 extern "C" int blsgpu_g2_sum_segments(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t npoints, const uint32_t* idx, const uint64_t* offsets, size_t nseg,
                                       size_t total, uint64_t* out) { CTX_CLAIM(c); return sum_segments<Fp2Policy>(c, xy, inf, npoints, idx, offsets, nseg, total, out); }
+
+// interpolation in the exponent: out[s] = sum_i lambda_i P_i over segment s, lambda the Lagrange coefficients of the segment's nodes at
+// its point.  Three stages on the context's stream, no synchronisation: the coefficients into scratch (fr_lagrange.hip.h, launched by
+// api_aux.hip), the products lambda_i P_i (mulbatch.hip.h: exact for every curve point, the endomorphism split only under
+// assume_subgroup), the segment sums (lagrange_combine.hip.h).  F: the group; FM: the policy mul_batch runs it under.
+template <class F, class FM>
+static int lagrange_combine_device(blsgpu_ctx* c, const void* d_xy, const void* d_inf, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total, const void* d_points,
+                                   void* d_out, void* d_flags) {
+  if (!c) return bad("lagrange_combine: ctx is NULL");
+  FlgcArgs a;
+  a.group = GroupTag<F>::id; a.xy = d_xy; a.inf = d_inf; a.nodes = d_nodes; a.offsets = d_offsets; a.nseg = nseg; a.total = total; a.points = d_points; a.out = d_out;
+  a.flags = d_flags; a.device = true;
+  if (const char* why = flgc_check(a)) return bad(why);
+  if (!nseg) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  constexpr int WW = Wire<F>::WORDS, PW = Store<F>::PROJ_WORDS;
+  if (c->flg_lambda.reserve(total * 32 + 16) || c->flg_prod.reserve(total * 3 * WW * 4 + 16)) { g_err = "hipMalloc(lagrange_combine scratch) failed"; return BLSGPU_ERR_HIP; }
+  // a segment that breaks the offsets contract writes no coefficient: its shares, and those no segment covers, are multiplied by 0
+  if (total) HIPCHK(hipMemsetAsync(c->flg_lambda.p, 0, total * 32, c->stream));
+  if (int rc = fr_lagrange_launch(c, d_nodes, d_offsets, nseg, total, d_points, nullptr, c->flg_lambda.p, nullptr, d_flags)) return rc;
+  {
+    ScalarFormScope mont(c, SCALAR_MONT);               // the coefficients are Montgomery limbs whatever the context's setting
+    if (int rc = mul_batch_device<FM>(c, d_xy, d_inf, c->flg_lambda.p, total, c->flg_prod.p)) return rc;
+  }
+  const unsigned block = flgc_block(a.group, nseg, total);
+  KLAUNCH(k_flg_point_sums<F>, dim3((unsigned)nseg), dim3(block), (size_t)block * PW * 4, c->stream, (const u32*)c->flg_prod.as<u32>(), (const u32*)d_offsets, (u32)nseg, (u32)total,
+          (u32*)d_out);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+template <class F, class FM>
+static int lagrange_combine(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, const uint64_t* nodes, const uint32_t* offsets, size_t nseg, const uint64_t* points,
+                            uint64_t* out, uint8_t* flags) {
+  if (!c) return bad("lagrange_combine: ctx is NULL");
+  if (nseg > FLG_MAX_SEGS) return bad("fr_lagrange_segments: nseg must not exceed 2^27");
+  if (nseg && !offsets) return bad("fr_lagrange_segments: NULL offsets with segments to do");
+  const size_t total = nseg ? offsets[nseg] : 0;
+  FlgcArgs a;
+  a.group = GroupTag<F>::id; a.xy = xy; a.inf = inf; a.nodes = nodes; a.offsets = offsets; a.nseg = nseg; a.total = total; a.points = points; a.out = out; a.flags = flags;
+  if (const char* why = flgc_check(a)) return bad(why);
+  if (const char* why = flg_check_host(offsets, nseg, total)) return bad(why);
+  if (!nseg) return BLSGPU_OK;
+  constexpr int WW = Wire<F>::WORDS;
+  HostCall h(c);
+  h.report_status();
+  void* dxy = h.in(c->io_a, xy, total * 2 * WW * 4);
+  void* dinf = h.in(c->flags_a, inf, total);
+  void* dn = h.in(c->io_b, nodes, total * 32);
+  void* doff = h.in(c->io_e, offsets, (nseg + 1) * 4);
+  void* dp = h.in(c->io_f, points, nseg * 32);
+  void* o = h.out(c->io_out, out, nseg * 3 * WW * 4);
+  void* f = flags ? h.out(c->flags_b, flags, nseg) : nullptr;
+  if (h.rc) return h.rc;
+  return h.finish(lagrange_combine_device<F, FM>(c, dxy, dinf, dn, doff, nseg, total, dp, o, f));
+}
+extern "C" int blsgpu_g1_lagrange_combine_device(blsgpu_ctx* c, const void* xy, const void* inf, const void* nodes, const void* offsets, size_t nseg, size_t total,
+                                                 const void* points, void* out, void* flags) { CTX_CLAIM(c);
+  return lagrange_combine_device<FpPolicy, FpPolicy>(c, xy, inf, nodes, offsets, nseg, total, points, out, flags); }
+extern "C" int blsgpu_g2_lagrange_combine_device(blsgpu_ctx* c, const void* xy, const void* inf, const void* nodes, const void* offsets, size_t nseg, size_t total,
+                                                 const void* points, void* out, void* flags) { CTX_CLAIM(c);
+  return lagrange_combine_device<Fp2Policy, Fp2PairPolicy>(c, xy, inf, nodes, offsets, nseg, total, points, out, flags); }
+extern "C" int blsgpu_g1_lagrange_combine(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, const uint64_t* nodes, const uint32_t* offsets, size_t nseg,
+                                          const uint64_t* points, uint64_t* out, uint8_t* flags) { CTX_CLAIM(c);
+  return lagrange_combine<FpPolicy, FpPolicy>(c, xy, inf, nodes, offsets, nseg, points, out, flags); }
+extern "C" int blsgpu_g2_lagrange_combine(blsgpu_ctx* c, const uint64_t* xy, const uint8_t* inf, const uint64_t* nodes, const uint32_t* offsets, size_t nseg,
+                                          const uint64_t* points, uint64_t* out, uint8_t* flags) { CTX_CLAIM(c);
+  return lagrange_combine<Fp2Policy, Fp2PairPolicy>(c, xy, inf, nodes, offsets, nseg, points, out, flags); }
 
 // device core: projective wire records in device memory -> affine wire coordinates + infinity bytes in device memory (asynchronous)
 // (the host forms take no infinity array when the caller does not want one: inf_ok = true)

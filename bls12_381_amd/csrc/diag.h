@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <string>
 #include "gntt_plan.h"
+#include "fr_lagrange_plan.h"
 
 struct BlsDiag {
   bool force_slow_sort = false;     // BLSGPU_FORCE_SLOW_SORT        the global-atomic sort used beyond 2^24 points, at every size (tests)
@@ -19,6 +20,7 @@ struct BlsDiag {
   int fr_cols_want = 1;             // BLSGPU_NTT_IMPL=stage|cols    column-tile passes of the transform: 0 never, 1 from 2^20 elements, 2 always
   int ntt_cols[3] = {0, 0, 0};      // BLSGPU_NTT_COLS=t,s,l         tile log2, stages per pass, lanes per workgroup of those passes (0 = built-in 11,7,512)
   size_t gntt_team_max = bls::GNTT_TEAM_MAX_B;   // BLSGPU_GNTT_TEAM_MAX=<B>  group transforms: the most lane-shape lanes per stage (B for G1, 2 B for G2) that take the team shape (0 = always the lane shape)
+  int flg_shape = bls::FLG_AUTO;    // BLSGPU_LAGRANGE_SHAPE=block|wave  Lagrange coefficients: one workgroup or one wavefront team per segment, whatever the lengths (tests, A/B)
   unsigned item_cap = 0;            // BLSGPU_ITEM_CAP               entries per work item of the bucket accumulation (0 = automatic)
   char prio[4] = "nhl";             // BLSGPU_PRIO                   stream priorities of accumulation / tail / front: h, n or l each
   std::string wide_prog;            // BLSGPU_WIDE_PROG              path of wide_prog.bin (default: next to the library)
@@ -48,6 +50,7 @@ static inline BlsDiag diag_read(int mmlp_max_k, int item_cap_max, int cols_log_m
     if (sscanf(v, "%d,%d,%d", &a, &b, &cc) == 3 && a >= 6 && a <= cols_log_max && b >= 1 && b <= a && cc >= 64 && cc <= 1024) { d.ntt_cols[0] = a; d.ntt_cols[1] = b; d.ntt_cols[2] = cc; }
   }
   d.gntt_team_max = bls::gntt_team_max_from(getenv("BLSGPU_GNTT_TEAM_MAX"));
+  d.flg_shape = bls::flg_shape_from(getenv("BLSGPU_LAGRANGE_SHAPE"));
   if (const char* v = getenv("BLSGPU_ITEM_CAP")) { long k = atol(v); if (k >= 8 && k <= item_cap_max) d.item_cap = (unsigned)k; }
   if (const char* v = getenv("BLSGPU_PRIO")) for (int i = 0; i < 3 && v[i]; i++) d.prio[i] = (v[i] == 'h' || v[i] == 'l') ? v[i] : 'n';
   if (const char* v = getenv("BLSGPU_WIDE_PROG")) d.wide_prog = v;

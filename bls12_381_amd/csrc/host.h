@@ -3,7 +3,8 @@
 //
 //   api_ctx.hip      contexts, streams, status, diagnostics, staged uploads, field / point self-test hooks
 //   api_msm.hip      resident bases, MSM, batched scalar multiplication, sums, batch_normalize,       (msm.hip.h, mulbatch.hip.h,
-//                    group transforms, segmented point sums                                             gntt.hip.h, gsum.hip.h)
+//                    group transforms, segmented point sums, Lagrange combines                          gntt.hip.h, gsum.hip.h,
+//                                                                                                       lagrange_combine.hip.h)
 //   api_pairing.hip  pairings, Miller loops, G2Prepared, final exponentiation, Gt, Fp6 / Fp12 hooks   (pairing / quad / prep / wide)
 //   api_aux.hip      Fr vectors and transform, hash-to-curve, point codecs, bulk BLS verification      (fr / h2c / codec)
 //   api_group.hip    device groups: one process driving several GPUs (host code only)
@@ -34,6 +35,7 @@
 #include "fr_expr_plan.h"
 #include "fr_lookup_plan.h"
 #include "gsum_plan.h"
+#include "fr_lagrange_plan.h"
 
 using namespace bls;
 
@@ -231,6 +233,8 @@ struct blsgpu_ctx {
   DevBuf frb_rec, frb_rowrec;           // blsgpu_fr_bary_*: one record per tile of a row longer than a tile, one per such row (fr_bary_plan.h)
   bool frb_lds_ready = false;           // ... and the tile kernels' dynamic LDS
   DevBuf gsum_part, gsum_meta;          // blsgpu_g{1,2}_sum_segments_device: two partial records and two segment numbers per chunk (gsum_plan.h)
+  DevBuf flg_pre, flg_work;             // blsgpu_fr_lagrange_segments_device: the running products of the batch inversion, the factors when the caller takes no lambda (fr_lagrange_plan.h)
+  DevBuf flg_lambda, flg_prod;          // blsgpu_g{1,2}_lagrange_combine_device: the coefficients and the products lambda_i P_i between its stages
   DevBuf frp_nodes;                     // blsgpu_fr_poseidon_merkle_device with nodes == NULL: the levels below the roots (fr_poseidon_plan.h)
 };
 
@@ -323,6 +327,9 @@ struct blsgpu_fr_sumcheck {
 int staged_upload(blsgpu_ctx* c, void* dst, const void* src, size_t bytes);      // api_ctx.hip
 void acc_harvest(blsgpu_ctx* c, bool wait);                                       // api_ctx.hip (MSM accumulation timings)
 int fr_twiddles_ready(blsgpu_ctx* c, int log_n, int dir);                        // api_aux.hip: the Fr twiddle table of (log_n, direction) in fr_tw[dir], which the caller reserved
+// api_aux.hip: the device form of blsgpu_fr_lagrange_segments behind its argument check (the combines of api_msm.hip run their own, wider check first)
+int fr_lagrange_launch(blsgpu_ctx* c, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total, const void* d_points, const void* d_values, void* d_lambda, void* d_y,
+                       void* d_flags);
 int fr_ninv_ready(blsgpu_ctx* c, int log_n);                                      // api_aux.hip: 2^5 n^-1 in fr_ninv, likewise
 
 // ---- host-pointer entry points ------------------------------------------------------------------------------------------------

@@ -401,6 +401,63 @@ inline std::vector<FrLimbs> fr_batch_invert(const std::vector<FrLimbs>& v, std::
   check(blsgpu_fr_batch_invert(Context::instance().handle(), v[0].data(), v.size(), out[0].data(), nonzero ? nonzero->data() : nullptr), "fr_batch_invert");
   return out;
 }
+// Lagrange coefficients at arbitrary nodes for many subsets in one call (include/bls12_381_hip.h: blsgpu_fr_lagrange_segments):
+// lambda_i = prod_{j != i} (z - x_j) * inv0(prod_{j != i} (x_i - x_j)) for subset s = nodes[s] at the point points[s] (points empty:
+// every z = 0).  values, if given, has the shape of nodes and y gets sum_i lambda_i values_i per subset; distinct gets 1 per subset whose
+// nodes are pairwise distinct.  Returns the coefficients in the shape of nodes.
+struct FrLagrange { std::vector<std::vector<FrLimbs>> lambda; std::vector<FrLimbs> y; std::vector<uint8_t> distinct; };
+namespace detail {
+inline size_t lagrange_flatten(const std::vector<std::vector<FrLimbs>>& nodes, std::vector<FrLimbs>& flat, std::vector<uint32_t>& offs) {
+  offs.assign(nodes.size() + 1, 0);
+  for (size_t s = 0; s < nodes.size(); s++) { flat.insert(flat.end(), nodes[s].begin(), nodes[s].end()); offs[s + 1] = (uint32_t)flat.size(); }
+  const size_t total = flat.size();
+  flat.push_back(FrLimbs{});
+  return total;
+}
+}  // namespace detail
+inline FrLagrange fr_lagrange_segments(const std::vector<std::vector<FrLimbs>>& nodes, const std::vector<FrLimbs>& points = {},
+                                       const std::vector<std::vector<FrLimbs>>& values = {}) {
+  const size_t nseg = nodes.size();
+  FrLagrange r;
+  r.lambda.resize(nseg); r.distinct.assign(nseg, 1);
+  if (!nseg) return r;
+  if (!points.empty() && points.size() != nseg) throw std::invalid_argument("fr_lagrange_segments: one point per subset");
+  std::vector<FrLimbs> x, v; std::vector<uint32_t> offs, voffs;
+  const size_t total = detail::lagrange_flatten(nodes, x, offs);
+  if (!values.empty() && (detail::lagrange_flatten(values, v, voffs) != total || voffs != offs)) throw std::invalid_argument("fr_lagrange_segments: values must have the shape of nodes");
+  std::vector<FrLimbs> lam(total + 1);
+  if (!values.empty()) r.y.resize(nseg);
+  check(blsgpu_fr_lagrange_segments(Context::instance().handle(), x[0].data(), offs.data(), nseg, points.empty() ? nullptr : points[0].data(), values.empty() ? nullptr : v[0].data(),
+                                    lam[0].data(), values.empty() ? nullptr : r.y[0].data(), r.distinct.data()), "fr_lagrange_segments");
+  for (size_t s = 0; s < nseg; s++) r.lambda[s].assign(lam.begin() + offs[s], lam.begin() + offs[s + 1]);
+  return r;
+}
+// Interpolation in the exponent (blsgpu_g{1,2}_lagrange_combine): out[s] = sum_i lambda_i * shares[s][i], lambda as above -- t partial
+// signatures into the group's.  shares has the shape of nodes; an empty subset gives the identity.
+template <int G> std::vector<Projective<G>> lagrange_combine(const std::vector<std::vector<Affine<G>>>& shares, const std::vector<std::vector<FrLimbs>>& nodes,
+                                                             const std::vector<FrLimbs>& points = {}, std::vector<uint8_t>* distinct = nullptr) {
+  const size_t nseg = nodes.size();
+  std::vector<Projective<G>> out(nseg);
+  if (distinct) distinct->assign(nseg, 1);
+  if (!nseg) return out;
+  if (shares.size() != nseg || (!points.empty() && points.size() != nseg)) throw std::invalid_argument("lagrange_combine: one subset of shares and one point per subset of nodes");
+  std::vector<FrLimbs> x; std::vector<uint32_t> offs;
+  const size_t total = detail::lagrange_flatten(nodes, x, offs);
+  std::vector<uint64_t> xy((total + 1) * Affine<G>::W), o(nseg * Projective<G>::W); std::vector<uint8_t> inf(total + 1);
+  for (size_t s = 0, t = 0; s < nseg; s++) {
+    if (shares[s].size() != nodes[s].size()) throw std::invalid_argument("lagrange_combine: shares must have the shape of nodes");
+    for (const auto& p : shares[s]) { std::memcpy(xy.data() + t * Affine<G>::W, p.xy.data(), Affine<G>::W * 8); inf[t++] = p.infinity; }
+  }
+  check((G == 1 ? blsgpu_g1_lagrange_combine : blsgpu_g2_lagrange_combine)(Context::instance().handle(), xy.data(), inf.data(), x[0].data(), offs.data(), nseg,
+                                                                          points.empty() ? nullptr : points[0].data(), o.data(), distinct ? distinct->data() : nullptr),
+        "lagrange_combine");
+  for (size_t s = 0; s < nseg; s++) std::memcpy(out[s].xyz.data(), o.data() + s * Projective<G>::W, Projective<G>::W * 8);
+  return out;
+}
+inline std::vector<G1Projective> g1_lagrange_combine(const std::vector<std::vector<G1Affine>>& shares, const std::vector<std::vector<FrLimbs>>& nodes,
+                                                     const std::vector<FrLimbs>& points = {}, std::vector<uint8_t>* distinct = nullptr) { return lagrange_combine<1>(shares, nodes, points, distinct); }
+inline std::vector<G2Projective> g2_lagrange_combine(const std::vector<std::vector<G2Affine>>& shares, const std::vector<std::vector<FrLimbs>>& nodes,
+                                                     const std::vector<FrLimbs>& points = {}, std::vector<uint8_t>* distinct = nullptr) { return lagrange_combine<2>(shares, nodes, points, distinct); }
 // Fraction scans (include/bls12_381_hip.h: blsgpu_fr_grand_product / blsgpu_fr_frac_sum): a column set is c tables of k rows, packed --
 // set.size() = c * k * len -- and an empty set stands for NULL (num_b, den_b: no beta term; mult: every multiplicity is 1).
 // fr_grand_product: f[i] = prod_j (num_a_j + beta num_b_j + gamma)[i] * inv0(prod_j (den_a_j + beta den_b_j + gamma)[i]), the PRODUCT scan

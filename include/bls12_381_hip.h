@@ -571,6 +571,59 @@ int blsgpu_fr_scan_many_device(blsgpu_ctx* ctx, int op, int exclusive, const voi
  * out == in, asynchrony and refusals as for blsgpu_fr_scan_many. */
 int blsgpu_fr_batch_invert(blsgpu_ctx* ctx, const uint64_t* values, size_t n, uint64_t* out, uint8_t* nonzero_flags);
 int blsgpu_fr_batch_invert_device(blsgpu_ctx* ctx, const void* d_in, size_t n, void* d_out, void* d_nonzero_flags);
+/* Lagrange coefficients at ARBITRARY nodes, for many subsets in ONE call, and optionally the interpolated value: what turns a threshold
+ * committee's partial results into the group's (threshold signatures and decryption, Shamir reconstruction, DKG share derivation, KZG
+ * multi-point verifiers).  Everything else polynomial here (fr_ntt*, fr_bary_*) lives on the roots of unity.
+ *   offsets  nseg + 1 non-decreasing u32 with offsets[0] = 0 and offsets[nseg] = total: exactly the array of `*_msm_segments`.  Segment s
+ *            owns the nodes x_i = nodes[offsets[s] + i], i < t_s = offsets[s + 1] - offsets[s]; t_s <= BLSGPU_FR_LAGRANGE_LEN_MAX,
+ *            total <= 2^27, nseg <= 2^27.  The device form takes total by value (it cannot read it back without stalling the stream).
+ *   points   nseg scalars, z_s the point of segment s; NULL: every z_s = 0, the recovery of a shared secret.  A DEVICE pointer in the
+ *            device form (a challenge computed on the device needs no synchronisation), as for HORNER.
+ * All scalars are canonical Montgomery limbs.  With inv0(x) = x^-1 and inv0(0) = 0 (blsgpu_fr_batch_invert's convention) the results
+ * are DEFINED by
+ *     N_i = prod_{j != i} (z_s - x_j)      D_i = prod_{j != i} (x_i - x_j)      lambda_i = N_i * inv0(D_i)
+ *     lambda[offsets[s] + i] = lambda_i           y[s] = sum_i lambda_i * values[offsets[s] + i]
+ *     distinct_flags[s] = 1 if every D_i != 0 (the nodes of s are pairwise distinct), else 0
+ * and by nothing else: an empty segment writes no lambda, y[s] = 0 and flag 1; one node gives lambda = 1 for every z; z_s on a node x_m
+ * gives lambda_m = 1 and 0 elsewhere; a repeated node gives lambda = 0 at exactly the repeated positions and flag 0, the other
+ * positions keeping the formula's value (meaningless as an interpolation, but the same from run to run); z_s on a repeated node gives 0
+ * everywhere.  Field elements are canonical, so the limbs are the formula's whatever order the device evaluates it in: t_s^2 + O(t_s)
+ * products and ONE field inversion per segment.
+ * values, lambda, y and distinct_flags may each be NULL; y needs values; at least one of lambda and y must be given when nseg > 0.
+ * lambda == NULL with y is a reconstruction without the coefficient traffic.  nseg == 0 is a no-op.
+ * The device form is asynchronous on the context's stream and never synchronises; its one launch depends on (nseg, total) alone; its
+ * scratch (32 bytes per node, 64 without lambda) is the context's own, not shared with pipelined *_msm_device calls in flight.  Scalar
+ * arrays are 16-byte aligned, d_offsets 4-byte, the flags any.
+ * BLSGPU_ERR_ARG with nothing staged or launched: a NULL required pointer with work to do, y without values, neither lambda nor y, nseg
+ * or total out of range, a misaligned device pointer, an output that overlaps an input or another output (there is no in-place form);
+ * in the host form also offsets that do not start at 0, decrease, or hold a segment over the limit.  The device form cannot see the
+ * offsets: a segment that decreases, is longer than the limit or ends beyond total is never used as an address, writes NOTHING (no
+ * lambda, no y, no flag) and sets a sticky flag, so that the next blsgpu_synchronize returns BLSGPU_ERR_ARG; every other segment is
+ * right. */
+#define BLSGPU_FR_LAGRANGE_LEN_MAX 4096      /* = BLSGPU_SEG_LEN_MAX: the same offsets array feeds *_msm_segments */
+int blsgpu_fr_lagrange_segments(blsgpu_ctx* ctx, const uint64_t* nodes, const uint32_t* offsets, size_t nseg, const uint64_t* points, const uint64_t* values,
+                                uint64_t* lambda, uint64_t* y, uint8_t* distinct_flags);
+int blsgpu_fr_lagrange_segments_device(blsgpu_ctx* ctx, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total, const void* d_points, const void* d_values,
+                                       void* d_lambda, void* d_y, void* d_distinct_flags);
+/* Interpolation in the exponent: out_xyz[s] = sum_i lambda_i * P[offsets[s] + i], lambda exactly the coefficients above (so a flagged
+ * segment has a defined value too) -- t partial BLS signatures into the group's signature, t decryption shares into the plaintext
+ * mask, f(id') H for a new participant.  The shares are `total` affine wire points plus infinity bytes, as
+ * `*_from_bytes_batch_device` writes them; share t belongs to node t.  out_xyz: nseg projective points (18 / 36 u64), the input form of
+ * `*_batch_normalize`.  An empty segment gives `identity()`; identities among the shares are ordinary terms; the projective
+ * representative is unspecified (compare after batch_normalize).  Exact for every curve point; the endomorphism split of the scalar
+ * multiplications only under blsgpu_set_assume_subgroup, as for `*_mul_batch`.  The coefficients are Montgomery limbs whatever
+ * blsgpu_set_scalar_form says.  The device forms never synchronise: coefficients, products and sums are three stages on the context's
+ * stream with scratch of their own (64 + 144 / 288 bytes per share).  d_xy and d_out_xyz are 8-byte aligned; refusals and the sticky
+ * flag are those of blsgpu_fr_lagrange_segments (a segment that breaks the offsets contract writes no point), plus NULL shares or
+ * output with work to do and an output that overlaps an input. */
+int blsgpu_g1_lagrange_combine(blsgpu_ctx* ctx, const uint64_t* xy, const uint8_t* infinity, const uint64_t* nodes, const uint32_t* offsets, size_t nseg,
+                               const uint64_t* points, uint64_t* out_xyz, uint8_t* distinct_flags);
+int blsgpu_g2_lagrange_combine(blsgpu_ctx* ctx, const uint64_t* xy, const uint8_t* infinity, const uint64_t* nodes, const uint32_t* offsets, size_t nseg,
+                               const uint64_t* points, uint64_t* out_xyz, uint8_t* distinct_flags);
+int blsgpu_g1_lagrange_combine_device(blsgpu_ctx* ctx, const void* d_xy, const void* d_infinity, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total,
+                                      const void* d_points, void* d_out_xyz, void* d_distinct_flags);
+int blsgpu_g2_lagrange_combine_device(blsgpu_ctx* ctx, const void* d_xy, const void* d_infinity, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total,
+                                      const void* d_points, void* d_out_xyz, void* d_distinct_flags);
 /* Fraction scans: the accumulator column of a permutation argument (grand product) and of a log-derivative lookup argument (logUp)
  * from their c column sets in ONE call.  Rows as for blsgpu_fr_scan_many: k rows of `len` scalars laid end to end.  A column SET is c
  * tables of k * len scalars each, table j starting j * pitch scalars behind the set's base pointer, pitch >= k * len (the addressing
