@@ -65,6 +65,7 @@ def _flags(f, n):
 FR_SCAN_SUM, FR_SCAN_PRODUCT, FR_SCAN_HORNER = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_SCAN_*
 FR_FRAC_MAX_COLS, FR_FRAC_TILE = 8, 1024                   # include/bls12_381_hip.h: BLSGPU_FR_FRAC_*
 FR_ORDER_NATURAL, FR_ORDER_BITREV = 0, 1                    # include/bls12_381_hip.h: BLSGPU_FR_ORDER_*
+KZG_FORM_COEFFS, KZG_FORM_EVALS = 0, 1                      # include/bls12_381_hip.h: BLSGPU_KZG_FORM_*
 FR_POSEIDON_AUTO, FR_POSEIDON_DENSE, FR_POSEIDON_SPARSE = 0, 1, 2      # include/bls12_381_hip.h: BLSGPU_FR_POSEIDON_*
 FR_EXPR_ADD, FR_EXPR_SUB, FR_EXPR_MUL, FR_EXPR_MAD, FR_EXPR_MOV = 0, 1, 2, 3, 4      # include/bls12_381_hip.h: BLSGPU_FR_EXPR_*
 FR_EXPR_MAX_COLS, FR_EXPR_MAX_REGS, FR_EXPR_MAX_CONSTS, FR_EXPR_MAX_INSTR = 32, 8, 32, 256
@@ -319,6 +320,69 @@ class FrLookup:
             self.close()
         except Exception:
             pass
+
+
+class KzgMultiproof:
+    """The circulant form of an SRS prefix resident on the device (`blsgpu_kzg_multiproof`), built once by Context.kzg_multiproof_create:
+    .proofs gives all 2c cell proofs of many polynomials in one call (include/bls12_381_hip.h)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    @property
+    def log_n(self):
+        return int(self.ctx.lib.blsgpu_kzg_multiproof_log_n(self.handle))
+
+    @property
+    def log_l(self):
+        return int(self.ctx.lib.blsgpu_kzg_multiproof_log_l(self.handle))
+
+    @property
+    def cells(self):
+        """2c, the number of cells (and proofs) per polynomial"""
+        return int(self.ctx.lib.blsgpu_kzg_multiproof_cells(self.handle))
+
+    def proofs(self, polys, form=KZG_FORM_COEFFS, order=FR_ORDER_NATURAL):
+        """polys: count polynomials of n scalars as a (count, n, 4) u64 array of Montgomery limbs or Python ints in [0, r) nested the same
+        way: coefficients, or (KZG_FORM_EVALS) the values on the domain of fr_bary_* in `order`.  Returns the (count, 2c, 18) projective
+        wire points of the proofs, numbered by `order`; compare after batch_normalize."""
+        v = _kzg_polys(polys, 1 << self.log_n, "kzg_multiproof.proofs")
+        out = np.zeros((v.shape[0], self.cells, 18), dtype=np.uint64)
+        check(self.ctx.lib.blsgpu_kzg_multiproof_proofs(self.ctx.h, self.handle, _ptr(v) if v.shape[0] else None, v.shape[0], int(form), int(order),
+                                                        _ptr(out) if v.shape[0] else None), "kzg_multiproof_proofs")
+        return out
+
+    def proofs_device(self, d_polys, count, d_out_xyz, form=KZG_FORM_COEFFS, order=FR_ORDER_NATURAL):
+        """the same on count * n scalars in device memory -> count * 2c wire points in device memory (device pointers as ints, 16-byte
+        aligned, no overlap); asynchronous on the context's stream"""
+        check(self.ctx.lib.blsgpu_kzg_multiproof_proofs_device(self.ctx.h, self.handle, d_polys, int(count), int(form), int(order), d_out_xyz), "kzg_multiproof_proofs_device")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_kzg_multiproof_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _kzg_polys(polys, n, what):
+    """count polynomials of n scalars -> a contiguous (count, n, 4) u64 array of Montgomery limbs ((n, 4) / a flat list of n ints: count = 1)"""
+    if isinstance(polys, np.ndarray):
+        v = np.ascontiguousarray(polys, dtype=np.uint64)
+        if v.ndim == 2:
+            v = v.reshape((1,) + v.shape)
+    else:
+        rows = list(polys)
+        if rows and not isinstance(rows[0], (list, tuple, np.ndarray)):
+            rows = [rows]
+        v = _fr_limbs(rows, (len(rows), n), what) if rows else np.zeros((0, n, 4), dtype=np.uint64)
+    if v.ndim != 3 or v.shape[1] != n or v.shape[2] != 4:
+        raise ValueError("%s: expected a (count, %d, 4) array" % (what, n))
+    return v
 
 
 def _fr_lookup_set(values, c, what):
@@ -1520,6 +1584,37 @@ class Context:
         mul_batch_device -> g_ntt_many_device -> batch_normalize_device -> bases_from_device needs no host copy"""
         fn = self.lib.blsgpu_g1_ntt_many_device if group == 1 else self.lib.blsgpu_g2_ntt_many_device
         check(fn(self.h, ctypes.c_void_p(d_ptr) if d_ptr else None, log_n, k, 1 if inverse else 0), "g_ntt_many_device")
+
+    def kzg_multiproof_create(self, srs_g1, log_n, log_l):
+        """amortised KZG openings (include/bls12_381_hip.h): the handle for polynomials of 2^log_n coefficients opened on cosets of
+        2^log_l points over the first 2^log_n points of the resident G1 bases `srs_g1`.  A setup call; the handle keeps no reference to
+        the SRS."""
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_kzg_multiproof_create(self.h, srs_g1.handle if srs_g1 is not None else None, int(log_n), int(log_l), ctypes.byref(h)), "kzg_multiproof_create")
+        return KzgMultiproof(self, h)
+
+    def kzg_cells(self, polys, log_l, form=KZG_FORM_COEFFS, order=FR_ORDER_NATURAL):
+        """the 2c cells of l = 2^log_l evaluations of every polynomial: polys as for KzgMultiproof.proofs (n a power of two); returns a
+        (count, 2c, l, 4) array of Montgomery limbs, cells numbered by `order`"""
+        if isinstance(polys, np.ndarray):
+            n = polys.shape[-2]
+        else:
+            rows = list(polys)
+            n = len(rows[0]) if rows and isinstance(rows[0], (list, tuple, np.ndarray)) else len(rows)
+        if n == 0 or n & (n - 1):
+            raise ValueError("kzg_cells: the number of scalars per polynomial must be a power of two")
+        v = _kzg_polys(polys, n, "kzg_cells")
+        log_n = n.bit_length() - 1
+        if not 0 <= log_l <= log_n:
+            raise ValueError("kzg_cells: log_l must be in [0, log_n]")
+        out = np.zeros((v.shape[0], 2 * (n >> log_l), 1 << log_l, 4), dtype=np.uint64)
+        check(self.lib.blsgpu_kzg_cells(self.h, _ptr(v) if v.shape[0] else None, log_n, int(log_l), v.shape[0], int(form), int(order), _ptr(out) if v.shape[0] else None), "kzg_cells")
+        return out
+
+    def kzg_cells_device(self, d_polys, log_n, log_l, count, d_cells, form=KZG_FORM_COEFFS, order=FR_ORDER_NATURAL):
+        """the same on count * 2^log_n scalars in device memory -> count * 2^(log_n + 1) scalars (16-byte aligned, no overlap);
+        asynchronous on the context's stream"""
+        check(self.lib.blsgpu_kzg_cells_device(self.h, d_polys, int(log_n), int(log_l), int(count), int(form), int(order), d_cells), "kzg_cells_device")
 
     def fr_to_bytes(self, limbs, return_flags=False):
         """`Scalar::to_bytes` (scalar.rs:284-296) over (n, 4) u64 Montgomery limbs -> (n, 32) uint8; flags: limbs below r"""

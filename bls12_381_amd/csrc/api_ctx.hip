@@ -205,7 +205,7 @@ extern "C" void blsgpu_destroy(blsgpu_ctx* c) {
   hipDeviceSynchronize();
   if (c->d_status) hipFree(c->d_status);
   if (c->d_wide) hipFree(c->d_wide);
-  DevBuf* bufs[] = {&c->result, &c->io_a, &c->io_b, &c->io_c, &c->io_d, &c->io_e, &c->io_f, &c->io_out, &c->flags_a, &c->flags_b, &c->mml_vals, &c->fr_tw[0], &c->fr_tw[1], &c->fr_tmp, &c->fr_ninv, &c->fr_cs[0], &c->fr_cs[1], &c->fb_table[0], &c->fb_table[1], &c->fb_stage, &c->mmlp_work, &c->mmlp_out, &c->gt_one, &c->ver, &c->fold_c, &c->fold_d, &c->fold_result, &c->h2c_uniform, &c->seg_wsum, &c->seg_rec, &c->frs_agg[0], &c->frs_agg[1], &c->frs_carry[0], &c->frs_carry[1], &c->frs_lane, &c->frsp_head, &c->frsp_tail, &c->frsp_meta, &c->frm_rec, &c->frm_scratch, &c->frb_rec, &c->frb_rowrec, &c->frp_nodes, &c->gsum_part, &c->gsum_meta, &c->flg_pre, &c->flg_work, &c->flg_lambda, &c->flg_prod};
+  DevBuf* bufs[] = {&c->result, &c->io_a, &c->io_b, &c->io_c, &c->io_d, &c->io_e, &c->io_f, &c->io_out, &c->flags_a, &c->flags_b, &c->mml_vals, &c->fr_tw[0], &c->fr_tw[1], &c->fr_tmp, &c->fr_ninv, &c->fr_cs[0], &c->fr_cs[1], &c->fb_table[0], &c->fb_table[1], &c->fb_stage, &c->mmlp_work, &c->mmlp_out, &c->gt_one, &c->ver, &c->fold_c, &c->fold_d, &c->fold_result, &c->h2c_uniform, &c->seg_wsum, &c->seg_rec, &c->frs_agg[0], &c->frs_agg[1], &c->frs_carry[0], &c->frs_carry[1], &c->frs_lane, &c->frsp_head, &c->frsp_tail, &c->frsp_meta, &c->frm_rec, &c->frm_scratch, &c->frb_rec, &c->frb_rowrec, &c->frp_nodes, &c->gsum_part, &c->gsum_meta, &c->flg_pre, &c->flg_work, &c->flg_lambda, &c->flg_prod, &c->kzg_coeff, &c->kzg_rows, &c->kzg_seg, &c->kzg_pts, &c->kzg_off};
   for (auto b : bufs) b->release();
   for (auto& sl : c->slot) {
     DevBuf* sb[] = {&sl.ent, &sl.sorted, &sl.hist, &sl.offs, &sl.cursor, &sl.bsum, &sl.items, &sl.heavy, &sl.ctrl, &sl.glv,

@@ -7,6 +7,7 @@
 #include "gntt.hip.h"
 #include "gsum.hip.h"
 #include "lagrange_combine.hip.h"
+#include "kzg.hip.h"
 
 // ---------------------------------------------------------------------------------------------------
 // bases
@@ -55,7 +56,7 @@ static int bases_make_endo(blsgpu_ctx* c, blsgpu_bases* b, bool trusted) {
 // unless the caller vouches for the set it is NOT tested and keeps no images: the call runs on plain 256-bit windows, which are the
 // complete-formula bucket method and exact for every curve point (state 3).  Resident uploads amortise the test over their MSMs.
 template <class F>
-static int bases_import(blsgpu_ctx* c, const void* d_xy, const void* d_inf, size_t n, blsgpu_bases** out, bool oneshot = false) {
+static int bases_import(blsgpu_ctx* c, const void* d_xy, const void* d_inf, size_t n, blsgpu_bases** out, bool oneshot = false, bool trusted = false) {
   blsgpu_bases* b = new blsgpu_bases();
   b->group = GroupTag<F>::id; b->n = n; b->device = c->device;
   size_t bytes = (n ? n : 1) * Store<F>::AFF_WORDS * 4;
@@ -68,7 +69,7 @@ static int bases_import(blsgpu_ctx* c, const void* d_xy, const void* d_inf, size
     if (e != hipSuccess) { bases_drop(b); return fail("k_bases_import", e, __LINE__); }
   }
   if (oneshot && !c->assume_subgroup) { b->subgroup = 3; *out = b; return BLSGPU_OK; }
-  if (int rc = bases_make_endo(c, b, false)) { bases_drop(b); return rc; }
+  if (int rc = bases_make_endo(c, b, trusted)) { bases_drop(b); return rc; }      // trusted: in the subgroup by construction (the transform of an SRS)
   *out = b;
   return BLSGPU_OK;
 }
@@ -1097,6 +1098,172 @@ extern "C" int blsgpu_g1_batch_normalize_device(blsgpu_ctx* c, const void* xyz, 
 extern "C" int blsgpu_g2_batch_normalize_device(blsgpu_ctx* c, const void* xyz, size_t n, void* xy, void* inf) { CTX_CLAIM(c); return batch_normalize_device<Fp2Policy>(c, xyz, n, xy, inf); }
 extern "C" int blsgpu_g1_batch_normalize(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint64_t* xy, uint8_t* inf) { CTX_CLAIM(c); return batch_normalize<FpPolicy>(c, xyz, n, xy, inf); }
 extern "C" int blsgpu_g2_batch_normalize(blsgpu_ctx* c, const uint64_t* xyz, size_t n, uint64_t* xy, uint8_t* inf) { CTX_CLAIM(c); return batch_normalize<Fp2Policy>(c, xyz, n, xy, inf); }
+
+// ---------------------------------------------------------------------------------------------------
+// amortised KZG openings (kzg.hip.h; kzg_plan.h holds the checks, the index maps and the launch shapes): every cell proof of many
+// polynomials by the circulant route -- Fr transforms (api_aux.hip, through the public entry point), ONE segmented MSM over the
+// handle's own bases, two group transforms -- and the cells themselves
+// ---------------------------------------------------------------------------------------------------
+namespace {
+struct KzgTmp {                      // device memory of blsgpu_kzg_multiproof_create, freed when the call has synchronised
+  void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~KzgTmp() { for (void* q : p) if (q) hipFree(q); }
+};
+}  // namespace
+extern "C" int blsgpu_kzg_multiproof_create(blsgpu_ctx* c, const blsgpu_bases* srs, int log_n, int log_l, blsgpu_kzg_multiproof** out) { CTX_CLAIM(c);
+  if (!c) return bad("kzg_multiproof_create: ctx is NULL");
+  KzgCreateArgs a;
+  a.srs_given = srs != nullptr; a.out_given = out != nullptr; a.log_n = log_n; a.log_l = log_l;
+  if (srs) { a.srs_group = srs->group; a.srs_len = srs->n; a.srs_subgroup = srs->subgroup; }
+  if (const char* why = kzg_check_create(a)) return bad(why);
+  if (srs->device != c->device) return bad("kzg_multiproof_create: the SRS lives on another device than the context");
+  const KzgCreatePlan plan = kzg_plan_create(log_n, log_l);
+  HIPCHK(hipSetDevice(c->device));
+  blsgpu_kzg_multiproof* h = new blsgpu_kzg_multiproof();
+  h->device = c->device; h->log_n = log_n; h->log_l = log_l;
+  if (!plan.msm) { *out = h; return BLSGPU_OK; }                 // c = 1: every proof is the identity, nothing is resident
+  KzgTmp tmp;
+  if (hipMalloc(&tmp.p[0], plan.xy_bytes) != hipSuccess || hipMalloc(&tmp.p[1], plan.inf_bytes) != hipSuccess || hipMalloc(&tmp.p[2], plan.point_bytes) != hipSuccess ||
+      hipMalloc(&tmp.p[3], plan.point_bytes) != hipSuccess) { (void)hipGetLastError(); delete h; g_err = "hipMalloc(kzg_multiproof_create) failed"; return BLSGPU_ERR_HIP; }
+  auto run = [&]() -> int {
+    if (!srs->ready_seen) {
+      if (hipEventQuery(srs->ev_ready) == hipSuccess) srs->ready_seen = true;
+      else HIPCHK(hipStreamWaitEvent(c->stream, srs->ev_ready, 0));
+    }
+    // the prefix in wire form -> S^ [t][j] -> X^ = its l transforms of size 2c -> [m][t] -> affine -> a base set with its images
+    if (int rc = bases_export<FpPolicy>(c, srs, 0, plan.n, tmp.p[0], tmp.p[1])) return rc;
+    KLAUNCH(k_kzg_srs_rows, dim3(plan.gather_grid), dim3(KZG_BLOCK), 0, c->stream, (const uint4*)tmp.p[0], (const uint8_t*)tmp.p[1], (uint4*)tmp.p[2], plan.log_c, log_l);
+    LAUNCHCHK();
+    if (int rc = g_ntt_many_device<GnG1Lane, GnG1Team>(c, tmp.p[2], plan.log_c + 1, plan.l, 0)) return rc;
+    KLAUNCH(k_kzg_point_permute, dim3(plan.permute_grid), dim3(KZG_BLOCK), 0, c->stream, (const uint4*)tmp.p[2], (uint4*)tmp.p[3], (size_t)1, log_n + 1, 2, plan.log_c, log_l);
+    LAUNCHCHK();
+    if (int rc = batch_normalize_device<FpPolicy>(c, tmp.p[3], plan.points, tmp.p[0], tmp.p[1])) return rc;
+    if (int rc = bases_import<FpPolicy>(c, tmp.p[0], tmp.p[1], plan.points, &h->xhat, false, true)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));                     // a setup call: the temporaries go, and the handle keeps no reference to the SRS
+    return BLSGPU_OK;
+  };
+  if (int rc = run()) {
+    (void)hipStreamSynchronize(c->stream);
+    if (h->xhat) bases_drop(h->xhat);
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_kzg_multiproof_log_n(const blsgpu_kzg_multiproof* h) { return h ? h->log_n : -1; }
+extern "C" int blsgpu_kzg_multiproof_log_l(const blsgpu_kzg_multiproof* h) { return h ? h->log_l : -1; }
+extern "C" size_t blsgpu_kzg_multiproof_cells(const blsgpu_kzg_multiproof* h) { return h ? (size_t)2 << (h->log_n - h->log_l) : 0; }
+extern "C" void blsgpu_kzg_multiproof_free(blsgpu_kzg_multiproof* h) {
+  if (!h) return;
+  if (h->xhat) blsgpu_bases_free(h->xhat);                       // waits for the device: an asynchronous call may still be reading the bases
+  delete h;
+}
+// the coefficients of `count` polynomials as the later stages read them: the caller's array (FORM_COEFFS), or a copy in scratch that went
+// through the inverse transform (FORM_EVALS: bit-reversed on the way for ORDER_BITREV); the caller's array is never written
+static int kzg_coeffs(blsgpu_ctx* c, const void* d_polys, int log_n, size_t count, int form, int order, unsigned copy_grid, size_t coeff_bytes, const uint4** coeffs) {
+  *coeffs = (const uint4*)d_polys;
+  if (form != KZG_FORM_EVALS) return BLSGPU_OK;
+  if (c->kzg_coeff.reserve(coeff_bytes)) { g_err = "hipMalloc(kzg scratch) failed"; return BLSGPU_ERR_HIP; }
+  KLAUNCH(k_kzg_scalar_copy, dim3(copy_grid), dim3(KZG_BLOCK), 0, c->stream, (const uint4*)d_polys, c->kzg_coeff.as<uint4>(), count, log_n, log_n, order == KZG_ORDER_BITREV ? 1 : 0);
+  LAUNCHCHK();
+  if (int rc = blsgpu_fr_ntt_many_device(c, c->kzg_coeff.p, log_n, count, 1, nullptr)) return rc;
+  *coeffs = c->kzg_coeff.as<uint4>();
+  return BLSGPU_OK;
+}
+static int kzg_proofs_device(blsgpu_ctx* c, const blsgpu_kzg_multiproof* h, const void* d_polys, size_t count, int form, int order, void* d_out) {
+  if (!c) return bad("kzg_multiproof_proofs: ctx is NULL");
+  KzgProofsArgs a;
+  a.handle_given = h != nullptr; a.polys = d_polys; a.count = count; a.form = form; a.order = order; a.out = d_out; a.device = true;
+  if (h) { a.log_n = h->log_n; a.log_l = h->log_l; }
+  if (const char* why = kzg_check_proofs(a)) return bad(why);
+  if (h->device != c->device) return bad("kzg_multiproof_proofs: the handle lives on another device than the context");
+  if (!count) return BLSGPU_OK;
+  const KzgPlan p = kzg_plan_proofs(h->log_n, h->log_l, count, form);
+  if (!p.ok) return bad("kzg_multiproof_proofs: the plan refuses the shape");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const int log_v = p.log_c + 1;                                 // a polynomial's 2c proofs
+  if (!p.msm) {                                                  // c = 1: two identities per polynomial
+    KLAUNCH(k_kzg_identity_fill, dim3(p.fill_grid), dim3(KZG_BLOCK), 0, st, (uint4*)d_out, count, log_v, (size_t)0, log_v);
+    LAUNCHCHK();
+    return BLSGPU_OK;
+  }
+  if (c->kzg_rows.reserve(p.rows_bytes) || c->kzg_seg.reserve(p.seg_bytes) || c->kzg_pts.reserve(p.point_bytes) || c->kzg_off.reserve(p.offset_bytes + p.base_first_bytes)) {
+    g_err = "hipMalloc(kzg scratch) failed"; return BLSGPU_ERR_HIP;
+  }
+  const uint4* coeffs = nullptr;
+  if (int rc = kzg_coeffs(c, d_polys, p.log_n, count, form, order, p.copy_grid, p.coeff_bytes, &coeffs)) return rc;
+  uint4 *rows = c->kzg_rows.as<uint4>(), *seg = c->kzg_seg.as<uint4>(), *pts = c->kzg_pts.as<uint4>();
+  u32 *off = c->kzg_off.as<u32>(), *bf = off + p.points + 1;
+  KLAUNCH(k_kzg_coeff_rows, dim3(p.rows_grid), dim3(KZG_BLOCK), 0, st, coeffs, rows, count, p.log_c, p.log_l);
+  LAUNCHCHK();
+  if (int rc = blsgpu_fr_ntt_many_device(c, rows, log_v, p.vectors, 0, nullptr)) return rc;
+  KLAUNCH(k_kzg_transpose<KZG_TILE>, dim3(p.transpose.grid), dim3(p.transpose.block), 0, st, (const uint4*)rows, seg, count, p.log_l, log_v, 0);
+  KLAUNCH(k_kzg_segments, dim3(p.seg_grid), dim3(KZG_BLOCK), 0, st, off, bf, (size_t)p.points, p.log_c, p.log_l);
+  LAUNCHCHK();
+  {
+    ScalarFormScope mont(c, SCALAR_MONT);                        // the transform's output is Montgomery limbs whatever the context's setting
+    if (int rc = msm_segments_device<FpPolicy>(c, h->xhat, bf, off, seg, p.points, p.scalars, pts)) return rc;
+  }
+  if (int rc = g_ntt_many_device<GnG1Lane, GnG1Team>(c, pts, log_v, count, 1)) return rc;
+  KLAUNCH(k_kzg_identity_fill, dim3(p.fill_grid), dim3(KZG_BLOCK), 0, st, pts, count, log_v, (size_t)p.c, p.log_c);
+  LAUNCHCHK();
+  if (int rc = g_ntt_many_device<GnG1Lane, GnG1Team>(c, pts, log_v, count, 0)) return rc;
+  KLAUNCH(k_kzg_point_permute, dim3(p.permute_grid), dim3(KZG_BLOCK), 0, st, (const uint4*)pts, (uint4*)d_out, count, log_v, order == KZG_ORDER_BITREV ? 1 : 0, p.log_c, p.log_l);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+static int kzg_cells_device(blsgpu_ctx* c, const void* d_polys, int log_n, int log_l, size_t count, int form, int order, void* d_cells) {
+  if (!c) return bad("kzg_cells: ctx is NULL");
+  KzgCellsArgs a;
+  a.polys = d_polys; a.log_n = log_n; a.log_l = log_l; a.count = count; a.form = form; a.order = order; a.cells = d_cells; a.device = true;
+  if (const char* why = kzg_check_cells(a)) return bad(why);
+  if (!count) return BLSGPU_OK;
+  const KzgCellsPlan p = kzg_plan_cells(log_n, log_l, count, form);
+  if (!p.ok) return bad("kzg_cells: the plan refuses the shape");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->kzg_rows.reserve(p.ext_bytes)) { g_err = "hipMalloc(kzg scratch) failed"; return BLSGPU_ERR_HIP; }
+  const uint4* coeffs = nullptr;
+  if (int rc = kzg_coeffs(c, d_polys, log_n, count, form, order, p.copy_grid, p.coeff_bytes, &coeffs)) return rc;
+  uint4* ext = c->kzg_rows.as<uint4>();
+  KLAUNCH(k_kzg_scalar_copy, dim3(p.extend_grid), dim3(KZG_BLOCK), 0, c->stream, coeffs, ext, count, log_n, log_n + 1, 0);
+  LAUNCHCHK();
+  if (int rc = blsgpu_fr_ntt_many_device(c, ext, log_n + 1, count, 0, nullptr)) return rc;
+  KLAUNCH(k_kzg_transpose<KZG_TILE>, dim3(p.map.grid), dim3(p.map.block), 0, c->stream, (const uint4*)ext, (uint4*)d_cells, count, log_l, p.log_c + 1, order == KZG_ORDER_BITREV ? 1 : 0);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_kzg_multiproof_proofs_device(blsgpu_ctx* c, const blsgpu_kzg_multiproof* h, const void* polys, size_t count, int form, int order, void* out) { CTX_CLAIM(c);
+  return kzg_proofs_device(c, h, polys, count, form, order, out); }
+extern "C" int blsgpu_kzg_cells_device(blsgpu_ctx* c, const void* polys, int log_n, int log_l, size_t count, int form, int order, void* cells) { CTX_CLAIM(c);
+  return kzg_cells_device(c, polys, log_n, log_l, count, form, order, cells); }
+extern "C" int blsgpu_kzg_multiproof_proofs(blsgpu_ctx* c, const blsgpu_kzg_multiproof* hd, const uint64_t* polys, size_t count, int form, int order, uint64_t* out) { CTX_CLAIM(c);
+  if (!c) return bad("kzg_multiproof_proofs: ctx is NULL");
+  KzgProofsArgs a;
+  a.handle_given = hd != nullptr; a.polys = polys; a.count = count; a.form = form; a.order = order; a.out = out;
+  if (hd) { a.log_n = hd->log_n; a.log_l = hd->log_l; }
+  if (const char* why = kzg_check_proofs(a)) return bad(why);
+  if (!count) return BLSGPU_OK;
+  HostCall h(c);
+  h.report_status();
+  void* dp = h.in(c->io_a, polys, (count << hd->log_n) * 32);
+  void* o = h.out(c->io_out, out, (count << (hd->log_n - hd->log_l + 1)) * 144);
+  if (h.rc) return h.rc;
+  return h.finish(kzg_proofs_device(c, hd, dp, count, form, order, o));
+}
+extern "C" int blsgpu_kzg_cells(blsgpu_ctx* c, const uint64_t* polys, int log_n, int log_l, size_t count, int form, int order, uint64_t* cells) { CTX_CLAIM(c);
+  if (!c) return bad("kzg_cells: ctx is NULL");
+  KzgCellsArgs a;
+  a.polys = polys; a.log_n = log_n; a.log_l = log_l; a.count = count; a.form = form; a.order = order; a.cells = cells;
+  if (const char* why = kzg_check_cells(a)) return bad(why);
+  if (!count) return BLSGPU_OK;
+  HostCall h(c);
+  void* dp = h.in(c->io_a, polys, (count << log_n) * 32);
+  void* o = h.out(c->io_out, cells, (count << (log_n + 1)) * 32);
+  if (h.rc) return h.rc;
+  return h.finish(kzg_cells_device(c, dp, log_n, log_l, count, form, order, o));
+}
 
 // ---------------------------------------------------------------------------------------------------
 // pairings

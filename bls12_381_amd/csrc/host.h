@@ -3,8 +3,8 @@
 //
 //   api_ctx.hip      contexts, streams, status, diagnostics, staged uploads, field / point self-test hooks
 //   api_msm.hip      resident bases, MSM, batched scalar multiplication, sums, batch_normalize,       (msm.hip.h, mulbatch.hip.h,
-//                    group transforms, segmented point sums, Lagrange combines                          gntt.hip.h, gsum.hip.h,
-//                                                                                                       lagrange_combine.hip.h)
+//                    group transforms, segmented point sums, Lagrange combines, amortised KZG openings         gntt.hip.h, gsum.hip.h,
+//                                                                                                       lagrange_combine.hip.h, kzg.hip.h)
 //   api_pairing.hip  pairings, Miller loops, G2Prepared, final exponentiation, Gt, Fp6 / Fp12 hooks   (pairing / quad / prep / wide)
 //   api_aux.hip      Fr vectors and transform, hash-to-curve, point codecs, bulk BLS verification      (fr / h2c / codec)
 //   api_group.hip    device groups: one process driving several GPUs (host code only)
@@ -36,6 +36,7 @@
 #include "fr_lookup_plan.h"
 #include "gsum_plan.h"
 #include "fr_lagrange_plan.h"
+#include "kzg_plan.h"
 
 using namespace bls;
 
@@ -235,6 +236,9 @@ struct blsgpu_ctx {
   DevBuf gsum_part, gsum_meta;          // blsgpu_g{1,2}_sum_segments_device: two partial records and two segment numbers per chunk (gsum_plan.h)
   DevBuf flg_pre, flg_work;             // blsgpu_fr_lagrange_segments_device: the running products of the batch inversion, the factors when the caller takes no lambda (fr_lagrange_plan.h)
   DevBuf flg_lambda, flg_prod;          // blsgpu_g{1,2}_lagrange_combine_device: the coefficients and the products lambda_i P_i between its stages
+  DevBuf kzg_coeff, kzg_rows, kzg_seg;  // blsgpu_kzg_multiproof_proofs_device / blsgpu_kzg_cells_device: the coefficients of an evaluation-form input, the rows c^_t (cells: the
+                                        // zero-extended rows), the segment-order copy (kzg_plan.h)
+  DevBuf kzg_pts, kzg_off;              // ... the points between the MSM and the caller's array, the offsets and base_first of the Toeplitz MSM
   DevBuf frp_nodes;                     // blsgpu_fr_poseidon_merkle_device with nodes == NULL: the levels below the roots (fr_poseidon_plan.h)
 };
 
@@ -306,6 +310,13 @@ struct blsgpu_fr_lookup {
   int device = 0; int c = 0;
   size_t rows = 0, slots = 0, distinct = 0;
   u32* keys = nullptr; u32* slot = nullptr; u32* counters = nullptr;
+};
+
+// the circulant form of an SRS prefix for amortised KZG openings (api_msm.hip: blsgpu_kzg_multiproof_create; kzg.hip.h): X^ as a
+// resident base set of its own, laid out [m][t] with its endomorphism images (NULL for c = 1, where every proof is the identity)
+struct blsgpu_kzg_multiproof {
+  int device = 0; int log_n = 0, log_l = 0;
+  blsgpu_bases* xhat = nullptr;
 };
 
 // a sumcheck in progress (api_aux.hip: blsgpu_fr_sumcheck_begin*; fr_mle.hip.h): its own copy of the tables, which the rounds consume,

@@ -799,6 +799,56 @@ inline void g2_ntt_many(std::vector<G2Projective>& p, size_t k, bool inverse = f
 inline std::vector<G1Projective> g1_ntt_many(const std::vector<G1Affine>& a, size_t k, bool inverse = false) { return g_ntt_many<1>(a, k, inverse); }
 inline std::vector<G2Projective> g2_ntt_many(const std::vector<G2Affine>& a, size_t k, bool inverse = false) { return g_ntt_many<2>(a, k, inverse); }
 
+// Amortised KZG openings (include/bls12_381_hip.h: blsgpu_kzg_multiproof_*): all 2c = 2n / l cell proofs of many polynomials in one call.
+// The constructor uploads the first n = 2^log_n points of `srs` (S[m] meant as [tau^m] G1), builds the handle's own resident tables
+// and lets the upload go; proofs() takes count polynomials of n scalars laid end to end -- coefficients, or (form = BLSGPU_KZG_FORM_EVALS)
+// values on the domain of fr_bary_* in `order` -- and returns count x 2c points numbered by `order`.  kzg_cells gives the cells.
+class KzgMultiproof {
+ public:
+  KzgMultiproof(const std::vector<G1Affine>& srs, int log_n, int log_l) {
+    if (log_n < 0 || log_n > 23 || srs.size() < ((size_t)1 << log_n)) throw std::invalid_argument("KzgMultiproof: the SRS holds fewer than 2^log_n points");
+    const size_t n = (size_t)1 << log_n;
+    std::vector<uint64_t> xy(n * G1Affine::W);
+    std::vector<uint8_t> inf(n);
+    for (size_t i = 0; i < n; i++) { std::memcpy(xy.data() + i * G1Affine::W, srs[i].xy.data(), G1Affine::W * 8); inf[i] = srs[i].infinity ? 1 : 0; }
+    blsgpu_bases* b = nullptr;
+    check(blsgpu_g1_bases_upload(Context::instance().handle(), xy.data(), inf.data(), n, &b), "g1_bases_upload");
+    const int rc = blsgpu_kzg_multiproof_create(Context::instance().handle(), b, log_n, log_l, &h_);
+    blsgpu_bases_free(b);
+    check(rc, "kzg_multiproof_create");
+  }
+  ~KzgMultiproof() { blsgpu_kzg_multiproof_free(h_); }
+  KzgMultiproof(const KzgMultiproof&) = delete;
+  KzgMultiproof& operator=(const KzgMultiproof&) = delete;
+  KzgMultiproof(KzgMultiproof&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  int log_n() const { return blsgpu_kzg_multiproof_log_n(h_); }
+  int log_l() const { return blsgpu_kzg_multiproof_log_l(h_); }
+  size_t cells() const { return blsgpu_kzg_multiproof_cells(h_); }
+  const blsgpu_kzg_multiproof* handle() const { return h_; }
+  std::vector<G1Projective> proofs(const std::vector<FrLimbs>& polys, int form = BLSGPU_KZG_FORM_COEFFS, int order = BLSGPU_FR_ORDER_NATURAL) const {
+    const size_t n = (size_t)1 << log_n();
+    if (polys.size() % n) throw std::invalid_argument("KzgMultiproof::proofs: the length must be polynomials of 2^log_n scalars");
+    const size_t count = polys.size() / n;
+    std::vector<G1Projective> out(count * cells());
+    if (!count) return out;
+    std::vector<uint64_t> xyz(out.size() * G1Projective::W);
+    check(blsgpu_kzg_multiproof_proofs(Context::instance().handle(), h_, polys[0].data(), count, form, order, xyz.data()), "kzg_multiproof_proofs");
+    for (size_t i = 0; i < out.size(); i++) std::memcpy(out[i].xyz.data(), xyz.data() + i * G1Projective::W, G1Projective::W * 8);
+    return out;
+  }
+ private:
+  blsgpu_kzg_multiproof* h_ = nullptr;
+};
+// cells[v][i][t] of count = polys.size() / 2^log_n polynomials: count x 2c x l scalars laid end to end
+inline std::vector<FrLimbs> kzg_cells(const std::vector<FrLimbs>& polys, int log_n, int log_l, int form = BLSGPU_KZG_FORM_COEFFS, int order = BLSGPU_FR_ORDER_NATURAL) {
+  if (log_n < 0 || log_n > 27 || polys.size() % ((size_t)1 << log_n)) throw std::invalid_argument("kzg_cells: the length must be polynomials of 2^log_n scalars");
+  const size_t count = polys.size() >> log_n;
+  std::vector<FrLimbs> out(polys.size() * 2);
+  if (!count) return out;
+  check(blsgpu_kzg_cells(Context::instance().handle(), polys[0].data(), log_n, log_l, count, form, order, out[0].data()), "kzg_cells");
+  return out;
+}
+
 // The same operations sharded over several GPUs of one node from this process (blsgpu_group: one context + one host thread per
 // listed device; partial results folded with `Sum` / `MillerLoopResult + MillerLoopResult`, src/g1.rs:161-171, src/pairings.rs:179-186)
 class Group {

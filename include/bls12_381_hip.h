@@ -947,6 +947,52 @@ int blsgpu_g1_ntt_many(blsgpu_ctx* ctx, uint64_t* xyz, int log_n, size_t k, int 
 int blsgpu_g2_ntt_many(blsgpu_ctx* ctx, uint64_t* xyz, int log_n, size_t k, int inverse);
 int blsgpu_g1_ntt_many_device(blsgpu_ctx* ctx, void* d_xyz, int log_n, size_t k, int inverse);
 int blsgpu_g2_ntt_many_device(blsgpu_ctx* ctx, void* d_xyz, int log_n, size_t k, int inverse);
+/* Amortised KZG openings: ALL 2c coset openings ("cell proofs") of many polynomials in one call, and the cells themselves -- with
+ * n = 4096 and l = 64 the 128 cells and 128 cell proofs of a data-availability blob.  The circulant route (Feist-Khovratovich) turns
+ * the 2c quotient MSMs of about n points per polynomial into one segmented MSM of 2n terms and two G1 transforms of 2c points.
+ * Notation: n = 2^log_n coefficients, l = 2^log_l points per cell, c = n / l; w the root blsgpu_fr_ntt uses for log_n + 1 (order 2n; w^2
+ * is the root for log_n, the domain of blsgpu_fr_bary_*); the SRS is the first n points S[0..n) of a resident G1 base set, S[m] meant as
+ * [tau^m] G1.  Cell i of 2c is a coset h_i <w^(2c)> of l points, numbered by `order` (BLSGPU_FR_ORDER_*):
+ *   NATURAL  h_i = w^i, entry t of cell i is the point w^(i + 2c t)
+ *   BITREV   entry t of cell i is the point w^bitrev(i l + t, log_n + 1): the coset of h_i = w^bitrev(i, log_n + 1 - log_l) walked in
+ *            bit-reversed order, the cell numbering of blob formats
+ *   cells[v][i][t]  = p_v at that point
+ *   proofs[v][i]    = sum_{u < n - l} q_i[u] S[u],  q_i = floor(p_v / (X^l - h_i^l)),  i.e.  q_i[u] = p[u + l] + h_i^l q_i[u + l]
+ * The definition is linear in S and holds for ANY subgroup points S[m], not only powers of one tau.  Proofs are group elements: count x 2c
+ * projective wire points of 18 u64 (the input form of blsgpu_g1_batch_normalize / _to_bytes_batch), the representative is not pinned,
+ * compare after batch_normalize.  A polynomial of degree < l gives 2c identities; c = 1 gives two identities without any MSM.
+ *   polys   count x n scalars, canonical Montgomery limbs (a precondition, as for the other Fr calls).  BLSGPU_KZG_FORM_COEFFS: the
+ *           coefficients, X^0 first.  BLSGPU_KZG_FORM_EVALS: the n values on <w^2> in `order`, exactly as blsgpu_fr_bary_* reads them.
+ *   order   the numbering of the outputs (cells and proofs) and, for FORM_EVALS, of the input.
+ *   cells   count x 2c x l scalars.
+ * blsgpu_kzg_multiproof_create is a setup call, as blsgpu_fr_matrix_upload is, and synchronises: it builds the transforms of the reversed
+ * SRS strides (2n points: a gather, blsgpu_g1_ntt_many of l vectors of 2c, batch_normalize) as a resident base set of its own with its
+ * endomorphism images, and keeps no reference to srs_g1.  _log_n / _log_l / _cells (= 2c) report the handle's shape;
+ * blsgpu_kzg_multiproof_free follows the rules of blsgpu_fr_matrix_free (it waits for the device; NULL is allowed).
+ * Limits: log_n in [0, 23], log_l in [0, min(log_n, 12)] (l <= BLSGPU_SEG_LEN_MAX), count * 2n <= 2^27 (the total of msm_segments),
+ * count * 2c <= 2^24 (the group transform's limit); for blsgpu_kzg_cells* alone log_n in [0, 27] and count * 2n <= 2^28.  count == 0 is a
+ * no-op.  Device pointers must be 16-byte aligned.  There is no in-place form: any overlap of an output with an input is refused.
+ * The device forms are asynchronous on the context's stream and never synchronise; their launches depend on the shape alone; their
+ * scratch (about 2 x 64 n + 288 c bytes per polynomial) is the context's own and is not shared with pipelined *_msm_device calls in
+ * flight.  The caller's polynomials are never written.  The internal MSM reads Montgomery limbs whatever blsgpu_set_scalar_form says
+ * (as the Lagrange combines do) and uses the endomorphism split: the handle's points are in the subgroup by construction.
+ * BLSGPU_ERR_ARG with nothing staged or launched: a NULL pointer with work to do; a G2 or too-short SRS (blsgpu_bases_len < n); an SRS
+ * whose subgroup state is 0 (a point outside the subgroup); log_n, log_l, count, form or order out of range, 64-bit overflow of the
+ * products included; a misaligned device pointer; an overlap.
+ * Not in scope: verification of cells, recovery from half the cells, G2, a Lagrange-form SRS, window-table precomputation for the
+ * Toeplitz MSM. */
+typedef struct blsgpu_kzg_multiproof blsgpu_kzg_multiproof;
+#define BLSGPU_KZG_FORM_COEFFS 0   /* n coefficients, X^0 first */
+#define BLSGPU_KZG_FORM_EVALS  1   /* n values on <w^2> in `order` (BLSGPU_FR_ORDER_*), as fr_bary_* reads them */
+int blsgpu_kzg_multiproof_create(blsgpu_ctx* ctx, const blsgpu_bases* srs_g1, int log_n, int log_l, blsgpu_kzg_multiproof** out);
+int blsgpu_kzg_multiproof_log_n(const blsgpu_kzg_multiproof* h);
+int blsgpu_kzg_multiproof_log_l(const blsgpu_kzg_multiproof* h);
+size_t blsgpu_kzg_multiproof_cells(const blsgpu_kzg_multiproof* h);
+void blsgpu_kzg_multiproof_free(blsgpu_kzg_multiproof* h);
+int blsgpu_kzg_multiproof_proofs(blsgpu_ctx* ctx, const blsgpu_kzg_multiproof* h, const uint64_t* polys, size_t count, int form, int order, uint64_t* out_xyz);
+int blsgpu_kzg_multiproof_proofs_device(blsgpu_ctx* ctx, const blsgpu_kzg_multiproof* h, const void* d_polys, size_t count, int form, int order, void* d_out_xyz);
+int blsgpu_kzg_cells(blsgpu_ctx* ctx, const uint64_t* polys, int log_n, int log_l, size_t count, int form, int order, uint64_t* cells);
+int blsgpu_kzg_cells_device(blsgpu_ctx* ctx, const void* d_polys, int log_n, int log_l, size_t count, int form, int order, void* d_cells);
 
 /* ---- hash-to-curve (the step in front of multi_miller_loop in bulk signature checks) ---- */
 /* `<G as HashToCurve<ExpandMsgXmd<Sha256>>>::hash_to_curve(msg, dst)` / `encode_to_curve` (encode_only != 0) for n
