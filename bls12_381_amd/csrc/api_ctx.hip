@@ -205,12 +205,7 @@ extern "C" void blsgpu_destroy(blsgpu_ctx* c) {
   hipDeviceSynchronize();
   if (c->d_status) hipFree(c->d_status);
   if (c->d_wide) hipFree(c->d_wide);
-  DevBuf* bufs[] = {&c->result, &c->io_a, &c->io_b, &c->io_c, &c->io_d, &c->io_e, &c->io_f, &c->io_out, &c->flags_a, &c->flags_b, &c->mml_vals, &c->fr_tw[0], &c->fr_tw[1], &c->fr_tmp, &c->fr_ninv, &c->fr_cs[0], &c->fr_cs[1], &c->fb_table[0], &c->fb_table[1], &c->fb_stage, &c->mmlp_work, &c->mmlp_out, &c->gt_one, &c->ver, &c->fold_c, &c->fold_d, &c->fold_result, &c->h2c_uniform, &c->seg_wsum, &c->seg_rec, &c->frs_agg[0], &c->frs_agg[1], &c->frs_carry[0], &c->frs_carry[1], &c->frs_lane, &c->frsp_head, &c->frsp_tail, &c->frsp_meta, &c->frm_rec, &c->frm_scratch, &c->frb_rec, &c->frb_rowrec, &c->frp_nodes, &c->gsum_part, &c->gsum_meta, &c->flg_pre, &c->flg_work, &c->flg_lambda, &c->flg_prod, &c->kzg_coeff, &c->kzg_rows, &c->kzg_seg, &c->kzg_pts, &c->kzg_off};
-  for (auto b : bufs) b->release();
   for (auto& sl : c->slot) {
-    DevBuf* sb[] = {&sl.ent, &sl.sorted, &sl.hist, &sl.offs, &sl.cursor, &sl.bsum, &sl.items, &sl.heavy, &sl.ctrl, &sl.glv,
-                    &sl.buckets, &sl.lvlR[0], &sl.lvlR[1], &sl.lvlT, &sl.tsum[0], &sl.tsum[1], &sl.wacc[0], &sl.wacc[1], &sl.wsums, &sl.result};
-    for (auto b : sb) b->release();
     hipEvent_t evs[] = {sl.ev_in, sl.ev_front, sl.ev_acc, sl.ev_tail, sl.ev_k0, sl.ev_k1, sl.ev_tree};
     for (auto e : evs) if (e) hipEventDestroy(e);
     for (auto& e : sl.ev_lvl) if (e) hipEventDestroy(e);
@@ -233,7 +228,7 @@ extern "C" void blsgpu_destroy(blsgpu_ctx* c) {
   c->ktimer.destroy();
   if (c->acc_stream) hipStreamDestroy(c->acc_stream);
   if (c->own_stream) hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;                  // every DevBuf of the context and its slots frees itself here (host.h)
 }
 extern "C" int blsgpu_set_stream(blsgpu_ctx* c, void* s) { CTX_CLAIM(c);
   if (!c) return bad("ctx is NULL");

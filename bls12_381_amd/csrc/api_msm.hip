@@ -873,7 +873,7 @@ static int g_ntt_many_device(blsgpu_ctx* c, void* d_xyz, int log_n, size_t k, in
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const int dir = inverse ? 1 : 0;
-  // the tables are the Fr transform's own (api_aux.hip), cached per (log_n, direction); the points are transformed in place, so the
+  // the tables are the Fr transform's own (api_fr.hip), cached per (log_n, direction); the points are transformed in place, so the
   // call shares no scratch with an MSM in flight
   if (c->fr_tw[dir].reserve(((size_t)1 << log_n) * 32) || c->fr_ninv.reserve(64)) { g_err = "hipMalloc(fr scratch) failed"; return BLSGPU_ERR_HIP; }
   if (int rc = fr_twiddles_ready(c, log_n, dir)) return rc;
@@ -996,7 +996,7 @@ extern "C" int blsgpu_g2_sum_segments(blsgpu_ctx* c, const uint64_t* xy, const u
 
 // interpolation in the exponent: out[s] = sum_i lambda_i P_i over segment s, lambda the Lagrange coefficients of the segment's nodes at
 // its point.  Three stages on the context's stream, no synchronisation: the coefficients into scratch (fr_lagrange.hip.h, launched by
-// api_aux.hip), the products lambda_i P_i (mulbatch.hip.h: exact for every curve point, the endomorphism split only under
+// api_fr.hip), the products lambda_i P_i (mulbatch.hip.h: exact for every curve point, the endomorphism split only under
 // assume_subgroup), the segment sums (lagrange_combine.hip.h).  F: the group; FM: the policy mul_batch runs it under.
 template <class F, class FM>
 static int lagrange_combine_device(blsgpu_ctx* c, const void* d_xy, const void* d_inf, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total, const void* d_points,
@@ -1101,7 +1101,7 @@ extern "C" int blsgpu_g2_batch_normalize(blsgpu_ctx* c, const uint64_t* xyz, siz
 
 // ---------------------------------------------------------------------------------------------------
 // amortised KZG openings (kzg.hip.h; kzg_plan.h holds the checks, the index maps and the launch shapes): every cell proof of many
-// polynomials by the circulant route -- Fr transforms (api_aux.hip, through the public entry point), ONE segmented MSM over the
+// polynomials by the circulant route -- Fr transforms (api_fr.hip, through the public entry point), ONE segmented MSM over the
 // handle's own bases, two group transforms -- and the cells themselves
 // ---------------------------------------------------------------------------------------------------
 namespace {

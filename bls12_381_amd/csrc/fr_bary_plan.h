@@ -1,6 +1,6 @@
 // fr_bary_plan.h -- the launch plan of the evaluation-form openings (blsgpu_fr_bary_eval_many* / blsgpu_fr_bary_open_many*) as plain host
 // code: which kernels of fr_bary.hip.h run, in which order, with which grid / block / dynamic LDS, on which buffers.  No HIP calls here:
-// api_aux.hip walks the plan and launches, tests/simt/emu_fr_bary.cpp walks the same plan on the host -- with a small tile, so that both
+// api_fr.hip walks the plan and launches, tests/simt/emu_fr_bary.cpp walks the same plan on the host -- with a small tile, so that both
 // shapes are reached at a few hundred elements.
 //
 // k rows of n = 2^log_n evaluations lie end to end; a tile is `block` lanes x `chunk` consecutive elements.  Rows and tiles are powers of

@@ -1,5 +1,5 @@
 // fr_expr_plan.h -- the Fr expression programs (blsgpu_fr_expr_*) as plain host code: the limits, the validation of a caller's program
-// with the image the kernel reads (frx_prog_build), and the launch plan of an evaluation.  No HIP calls here: api_aux.hip builds the
+// with the image the kernel reads (frx_prog_build), and the launch plan of an evaluation.  No HIP calls here: api_fr.hip builds the
 // image once per handle and launches from the plan, tests/simt/emu_fr_expr.cpp walks the same plan on the host,
 // tests/cpp/fr_expr_plan_main.cpp sweeps both under sanitizers.
 //

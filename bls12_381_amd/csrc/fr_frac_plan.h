@@ -1,5 +1,5 @@
 // fr_frac_plan.h -- the launch plan of the Fr fraction scans (blsgpu_fr_grand_product*, blsgpu_fr_frac_sum*) as plain host code: which
-// kernels run, in which order, with which grid / block / dynamic LDS, on which buffers.  No HIP calls here: api_aux.hip walks the plan
+// kernels run, in which order, with which grid / block / dynamic LDS, on which buffers.  No HIP calls here: api_fr.hip walks the plan
 // and launches, tests/simt/emu_fr_frac.cpp walks the same plan on the host, tests/cpp/fr_frac_plan_main.cpp sweeps it under sanitizers.
 //
 // A call is fr_scan_plan.h's reduce-then-scan with ONE change: the first pass over the elements is k_frf_front (fr_frac.hip.h), which

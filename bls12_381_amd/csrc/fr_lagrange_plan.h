@@ -1,7 +1,7 @@
 // fr_lagrange_plan.h -- Lagrange coefficients at arbitrary nodes (blsgpu_fr_lagrange_segments[_device], and the coefficient stage of
 // blsgpu_g{1,2}_lagrange_combine) as plain host code: the limits, the two launch shapes and the choice between them, which lanes own
 // which nodes, the tiles the nodes pass through LDS in, the LDS and scratch bytes, the status bit and every argument check.  No HIP
-// calls here: api_aux.hip launches from the plan, fr_lagrange.hip.h reads the cut through the FLG_HD functions below,
+// calls here: api_fr.hip launches from the plan, fr_lagrange.hip.h reads the cut through the FLG_HD functions below,
 // tests/simt/emu_fr_lagrange.cpp walks the same plan on the host and tests/cpp/fr_lagrange_plan_main.cpp sweeps it under sanitizers.
 //
 // The cut.  A TEAM of `team` lanes owns one segment from its first node to its results; segment s belongs to team s % teams of

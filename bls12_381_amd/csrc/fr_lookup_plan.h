@@ -1,6 +1,6 @@
 // fr_lookup_plan.h -- the Fr lookup tables (blsgpu_fr_lookup_*) as plain host code: the limits, the key hash, the size of the slot
 // array, the launch shapes of the three kernels, which of the two counting paths a table takes, and every argument check.  No HIP calls
-// here: api_aux.hip launches from the plan, tests/simt/emu_fr_lookup.cpp walks the same plan on the host,
+// here: api_fr.hip launches from the plan, tests/simt/emu_fr_lookup.cpp walks the same plan on the host,
 // tests/cpp/fr_lookup_plan_main.cpp sweeps it under sanitizers.
 //
 // The index.  A key is a row of c scalars = 8 c 32-bit words.  The handle keeps the keys row-major and an open-addressed array of

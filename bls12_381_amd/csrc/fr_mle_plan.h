@@ -1,6 +1,6 @@
 // fr_mle_plan.h -- the launch plans of the multilinear operations over Fr (blsgpu_fr_mle_fold*, blsgpu_fr_eq_table*, blsgpu_fr_mle_eval*,
 // blsgpu_fr_sumcheck_round_device) as plain host code: which kernels of fr_mle.hip.h run, in which order, with which grid / block /
-// dynamic LDS, on which buffers, and how large the scratch is.  No HIP calls here: api_aux.hip walks a plan and launches,
+// dynamic LDS, on which buffers, and how large the scratch is.  No HIP calls here: api_fr.hip walks a plan and launches,
 // tests/simt/emu_fr_mle.cpp walks the same plan on the host -- with a small shape, so that the multi-workgroup paths are reached at a few
 // hundred elements.  The term program of a sumcheck is validated here as well (host data in, the kernels' FrmProg out).
 //

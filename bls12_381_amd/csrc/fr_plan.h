@@ -1,6 +1,6 @@
 // fr_plan.h -- the launch plan of the batched Fr transform (blsgpu_fr_ntt_many*) as plain host code: which kernels of fr.hip.h run, in
 // which order, with which grid / block / dynamic LDS and arguments, for k vectors of 2^log_n scalars laid end to end.  No HIP calls
-// here: api_aux.hip walks the plan and launches, tests/simt/emu_fr.cpp walks the same plan on the host.
+// here: api_fr.hip walks the plan and launches, tests/simt/emu_fr.cpp walks the same plan on the host.
 //
 //   log_n <= FR_TILE_LOG   one launch of k_fr_tile<true>, IN PLACE: a workgroup takes a tile of 2^tile_log consecutive elements of the
 //                          concatenated array, i.e. whole vectors, and has read all of them into LDS before its first store.
@@ -34,7 +34,7 @@ struct FrPlan {
   size_t total = 0;            // k * 2^log_n
   bool needs_tmp = false;      // a scratch buffer of total * 32 bytes
 };
-// the shape of the column-tile passes: tile log2, stages per pass, lanes (api_aux.hip: 11, 7, 512 measured; BLSGPU_NTT_COLS overrides)
+// the shape of the column-tile passes: tile log2, stages per pass, lanes (api_fr.hip: 11, 7, 512 measured; BLSGPU_NTT_COLS overrides)
 struct FrColsShape { int tlog = 11, dmax = 7, block = 512; };
 
 // log_n in [0, 28], k * 2^log_n <= 2^28.  use_cols: the column-tile passes are usable AND wanted for this log_n.

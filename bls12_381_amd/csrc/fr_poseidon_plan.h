@@ -1,6 +1,6 @@
 // fr_poseidon_plan.h -- Poseidon over Fr (blsgpu_fr_poseidon_*) as plain host code: the validation of an instance, the derivation of the
 // sparse form of its partial rounds, the constant image the kernels of fr_poseidon.hip.h read, and the launch plans of permute / hash_many /
-// merkle.  No HIP calls here: api_aux.hip builds a handle and walks a plan, tests/simt/emu_fr_poseidon.cpp walks the same plan on the host
+// merkle.  No HIP calls here: api_fr.hip builds a handle and walks a plan, tests/simt/emu_fr_poseidon.cpp walks the same plan on the host
 // with a small block, tests/cpp/fr_poseidon_plan_main.cpp runs the derivation against the textbook rounds on the host arithmetic below.
 //
 // The library ships NO standard parameter set: the caller passes round constants and matrix of the instance it uses (canonical Montgomery

@@ -1,6 +1,6 @@
 // fr_scan_plan.h -- the launch plan of the Fr scans (blsgpu_fr_scan_many*) and of the batch inversion (blsgpu_fr_batch_invert*) as plain
 // host code: which kernels of fr_scan.hip.h run, in which order, with which grid / block / dynamic LDS, on which buffers.  No HIP calls
-// here: api_aux.hip walks the plan and launches, tests/simt/emu_fr_scan.cpp walks the same plan on the host -- with a small tile and
+// here: api_fr.hip walks the plan and launches, tests/simt/emu_fr_scan.cpp walks the same plan on the host -- with a small tile and
 // chunk, so that the multi-tile and aggregate-level paths are reached at a few hundred elements.
 //
 // The k x len array is ONE flat sequence of `total` = k len elements with segment heads at the multiples of len.  A tile is `block` lanes

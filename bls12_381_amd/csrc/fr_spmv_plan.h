@@ -1,6 +1,6 @@
 // fr_spmv_plan.h -- the launch plan of the sparse matrix-vector product over Fr (blsgpu_fr_spmv*) as plain host code: which kernels of
 // fr_spmv.hip.h run, in which order, with which grid / block / dynamic LDS, and how large the scratch records are.  No HIP calls here:
-// api_aux.hip walks the plan and launches, tests/simt/emu_fr_spmv.cpp walks the same plan on the host -- with a small tile, so that rows
+// api_fr.hip walks the plan and launches, tests/simt/emu_fr_spmv.cpp walks the same plan on the host -- with a small tile, so that rows
 // crossing several tiles are reached at a few hundred non-zeros.
 //
 // The NON-ZEROS of the CSR matrix, not its rows, are cut into tiles of `block` lanes x `chunk` consecutive entries, so the work of a

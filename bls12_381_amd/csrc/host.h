@@ -6,7 +6,9 @@
 //                    group transforms, segmented point sums, Lagrange combines, amortised KZG openings         gntt.hip.h, gsum.hip.h,
 //                                                                                                       lagrange_combine.hip.h, kzg.hip.h)
 //   api_pairing.hip  pairings, Miller loops, G2Prepared, final exponentiation, Gt, Fp6 / Fp12 hooks   (pairing / quad / prep / wide)
-//   api_aux.hip      Fr vectors and transform, hash-to-curve, point codecs, bulk BLS verification      (fr / h2c / codec)
+//   api_aux.hip      hash-to-curve, expanders and hash-to-scalar, point codecs, bulk BLS verification   (h2c / expand_kernels / codec / generators)
+//   api_fr.hip       Fr vectors, transforms, scans, Lagrange, fraction scans, openings, SpMV, Poseidon,  (fr*.hip.h)
+//                    expression programs, lookup tables, multilinear folds and sumcheck
 //   api_group.hip    device groups: one process driving several GPUs (host code only)
 //
 // Every kernel header is compiled into exactly ONE of them (a non-template __global__ function has one host-side stub per library).
@@ -24,6 +26,7 @@
 #include <mutex>
 #include <condition_variable>
 #include <functional>
+#include <initializer_list>
 #include <dlfcn.h>
 
 #include "../../include/bls12_381_hip.h"
@@ -31,6 +34,7 @@
 #include "scalar.hip.h"
 #include "limits.h"
 #include "diag.h"
+#include "ranges.h"
 #include "fr_poseidon_plan.h"
 #include "fr_expr_plan.h"
 #include "fr_lookup_plan.h"
@@ -112,8 +116,14 @@ struct KtScope {
 #define KLAUNCH(kern, grid, block, lds, stream, ...) \
   do { KtScope kt_(#kern, (stream)); hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__); } while (0)
 
+// a device allocation that grows on demand and frees itself: the context's buffers go with `delete c`, after blsgpu_destroy has
+// synchronised the device.  Held by pointer or reference only.
 struct DevBuf {
   void* p = nullptr; size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   int reserve(size_t bytes) {
     if (bytes <= cap) return 0;
     if (p) {
@@ -276,7 +286,7 @@ struct ScalarFormScope {
 // G2Prepared resident on the device (api_pairing.hip; the bulk verification of api_aux.hip keeps one)
 struct blsgpu_g2_prepared { int device = 0; size_t n = 0; u32* tab = nullptr; uint8_t* inf = nullptr; hipEvent_t ev_ready = nullptr; };
 
-// a CSR matrix over Fr resident on the device (api_aux.hip: blsgpu_fr_matrix_upload / _from_device; fr_spmv.hip.h)
+// a CSR matrix over Fr resident on the device (api_fr.hip: blsgpu_fr_matrix_upload / _from_device; fr_spmv.hip.h)
 struct blsgpu_fr_matrix {
   int device = 0; size_t n_rows = 0, n_cols = 0, nnz = 0;
   u32* row_ptr = nullptr; u32* col = nullptr;      // the caller's arrays, validated
@@ -286,7 +296,7 @@ struct blsgpu_fr_matrix {
   bool has_empty = false;                          // a row without entries: the product zeroes its output first
 };
 
-// a Poseidon instance resident on the device (api_aux.hip: blsgpu_fr_poseidon_create; fr_poseidon.hip.h): the shape, the offsets of the
+// a Poseidon instance resident on the device (api_fr.hip: blsgpu_fr_poseidon_create; fr_poseidon.hip.h): the shape, the offsets of the
 // constant image's sections and the image itself, built once by fr_poseidon_plan.h
 struct blsgpu_fr_poseidon {
   int device = 0; int t = 0, r_full = 0, r_partial = 0, form = 0;
@@ -295,7 +305,7 @@ struct blsgpu_fr_poseidon {
   u32* image = nullptr;
 };
 
-// an Fr expression program resident on the device (api_aux.hip: blsgpu_fr_expr_create; fr_expr.hip.h): what the accessors report and
+// an Fr expression program resident on the device (api_fr.hip: blsgpu_fr_expr_create; fr_expr.hip.h): what the accessors report and
 // the image frx_prog_build made of the validated program (fr_expr_plan.h)
 struct blsgpu_fr_expr {
   int device = 0;
@@ -303,7 +313,7 @@ struct blsgpu_fr_expr {
   u32* image = nullptr;
 };
 
-// an Fr lookup table resident on the device (api_aux.hip: blsgpu_fr_lookup_create / _from_device; fr_lookup.hip.h): the handle's own
+// an Fr lookup table resident on the device (api_fr.hip: blsgpu_fr_lookup_create / _from_device; fr_lookup.hip.h): the handle's own
 // row-major copy of the keys, the open-addressed slot array (row + 1 of a key's first row, 0 = empty) and one counter per table row,
 // the scratch of a count call (which is why a handle serves one stream at a time)
 struct blsgpu_fr_lookup {
@@ -319,7 +329,7 @@ struct blsgpu_kzg_multiproof {
   blsgpu_bases* xhat = nullptr;
 };
 
-// a sumcheck in progress (api_aux.hip: blsgpu_fr_sumcheck_begin*; fr_mle.hip.h): its own copy of the tables, which the rounds consume,
+// a sumcheck in progress (api_fr.hip: blsgpu_fr_sumcheck_begin*; fr_mle.hip.h): its own copy of the tables, which the rounds consume,
 // and the term program as the caller gave it (validated once at begin; the round entry point it is passed to builds the kernels' form)
 struct blsgpu_fr_sumcheck {
   int device = 0; int m = 0; size_t k = 0, pitch = 0;
@@ -334,14 +344,36 @@ struct blsgpu_fr_sumcheck {
   u32* small = nullptr;                            // the challenge (8 words), then deg + 1 evaluations
 };
 
+// ---- scaffolding the families share ------------------------------------------------------------------------------------------------
+// more than the 64 KB of dynamic LDS a kernel gets unasked has to be asked for, kernel by kernel: once per context (*ready is the
+// context's flag of the family).  A failure here is reported under the calling unit's name with a line number of THIS header.
+static inline int lds_grant(bool* ready, size_t bytes, std::initializer_list<const void*> kernels) {
+  if (*ready) return BLSGPU_OK;
+  for (const void* k : kernels) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  *ready = true;
+  return BLSGPU_OK;
+}
+// resident handles: a host image in a fresh device allocation (a setup call: synchronous); *image stays NULL when it fails
+static inline hipError_t device_image(u32** image, const void* src, size_t bytes) {
+  hipError_t e = hipMalloc((void**)image, bytes);
+  if (e == hipSuccess) e = hipMemcpy(*image, src, bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess && *image) { hipFree(*image); *image = nullptr; }
+  return e;
+}
+// ... and the preamble of their *_free: asynchronous work queued on any stream may still be using the handle's memory
+static inline void handle_quiesce(int device) {
+  hipSetDevice(device);
+  hipDeviceSynchronize();
+}
+
 // ---- functions that cross translation units -------------------------------------------------------------------------------------
 int staged_upload(blsgpu_ctx* c, void* dst, const void* src, size_t bytes);      // api_ctx.hip
 void acc_harvest(blsgpu_ctx* c, bool wait);                                       // api_ctx.hip (MSM accumulation timings)
-int fr_twiddles_ready(blsgpu_ctx* c, int log_n, int dir);                        // api_aux.hip: the Fr twiddle table of (log_n, direction) in fr_tw[dir], which the caller reserved
-// api_aux.hip: the device form of blsgpu_fr_lagrange_segments behind its argument check (the combines of api_msm.hip run their own, wider check first)
+int fr_twiddles_ready(blsgpu_ctx* c, int log_n, int dir);                        // api_fr.hip: the Fr twiddle table of (log_n, direction) in fr_tw[dir], which the caller reserved
+// api_fr.hip: the device form of blsgpu_fr_lagrange_segments behind its argument check (the combines of api_msm.hip run their own, wider check first)
 int fr_lagrange_launch(blsgpu_ctx* c, const void* d_nodes, const void* d_offsets, size_t nseg, size_t total, const void* d_points, const void* d_values, void* d_lambda, void* d_y,
                        void* d_flags);
-int fr_ninv_ready(blsgpu_ctx* c, int log_n);                                      // api_aux.hip: 2^5 n^-1 in fr_ninv, likewise
+int fr_ninv_ready(blsgpu_ctx* c, int log_n);                                      // api_fr.hip: 2^5 n^-1 in fr_ninv, likewise
 
 // ---- host-pointer entry points ------------------------------------------------------------------------------------------------
 // Every host-pointer entry point is  check -> stage -> device core -> finish:  it runs the argument check of its operation, stages its

@@ -1,6 +1,6 @@
 // tests/simt/emu_fr.cpp -- the Fr transform kernels of bls12_381_amd/csrc/fr.hip.h compiled for the HOST (test infrastructure only).
 // emu_fr_ntt_many builds the tables with the device kernels (k_fr_twiddles, k_fr_tw_levels, k_fr_ninv, k_fr_coset_table) and then WALKS
-// THE PLAN of csrc/fr_plan.h -- the function api_aux.hip::blsgpu_fr_ntt_many_device launches from -- step by step, so the CPU suite
+// THE PLAN of csrc/fr_plan.h -- the function api_fr.hip::blsgpu_fr_ntt_many_device launches from -- step by step, so the CPU suite
 // runs the launch sequence the GPU runs, with its grids, blocks and arguments (tests/test_simt_fr.py).
 //
 // The transform kernels stride their loops by blockDim.x and use no cross-lane operation but the workgroup barrier, so they compute
@@ -39,7 +39,7 @@ int emu_fr_ntt_many(u32* data, u32* tmp, u32* tw, u32* cs, u32* ninv, int log_n,
   if (!fr_plan_many(log_n, k, inverse != 0, coset != nullptr, cols != 0).n_steps) { kernels_out[0] = -1; return 0; }      // no launch, no table
   const int dir = inverse ? 1 : 0;
   const size_t n = (size_t)1 << log_n, half = n >> 1;
-  // api_aux.hip fr_twiddles_ready / fr_ninv_ready / the coset table of blsgpu_fr_ntt_many_device
+  // api_fr.hip fr_twiddles_ready / fr_ninv_ready / the coset table of blsgpu_fr_ntt_many_device
   launch_loop(nblk((half + FR_TW_RUN - 1) / FR_TW_RUN, 256), 256, [=] { k_fr_twiddles(tw, log_n, dir); });
   if (log_n > 1) launch_loop(nblk(half, 256), 256, [=] { k_fr_tw_levels(tw, log_n); });
   if (coset) {

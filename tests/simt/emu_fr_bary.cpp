@@ -1,6 +1,6 @@
 // tests/simt/emu_fr_bary.cpp -- the evaluation-form opening kernels of bls12_381_amd/csrc/fr_bary.hip.h compiled for the HOST (test
 // infrastructure only).  emu_fr_bary builds the forward twiddle table with the transform's own kernels (k_fr_twiddles, k_fr_tw_levels:
-// what fr_twiddles_ready launches) and then WALKS THE PLAN of csrc/fr_bary_plan.h -- the function api_aux.hip launches from -- step by
+// what fr_twiddles_ready launches) and then WALKS THE PLAN of csrc/fr_bary_plan.h -- the function api_fr.hip launches from -- step by
 // step, with its grids, blocks, LDS sizes and buffer roles, at whatever (block, chunk) the test asks for: a tile of 64 x 2 elements
 // reaches the row-over-tiles shape at 256 elements.
 //

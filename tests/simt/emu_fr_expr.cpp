@@ -1,5 +1,5 @@
 // tests/simt/emu_fr_expr.cpp -- the Fr expression interpreter (bls12_381_amd/csrc/fr_expr.hip.h) compiled for the HOST (test
-// infrastructure only).  emu_fr_expr_eval launches k_frx_eval FROM THE PLAN of csrc/fr_expr_plan.h -- the function api_aux.hip launches
+// infrastructure only).  emu_fr_expr_eval launches k_frx_eval FROM THE PLAN of csrc/fr_expr_plan.h -- the function api_fr.hip launches
 // from -- with its grid, block, dynamic LDS and rows per lane, at whatever (block, chunk) the test asks for: at 64 x 2 a table of 512 rows
 // is four workgroups.  emu_fr_expr_build is frx_prog_build, the validation and the image the handle uploads.
 //

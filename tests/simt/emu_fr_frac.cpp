@@ -1,5 +1,5 @@
 // tests/simt/emu_fr_frac.cpp -- the fused front of the Fr fraction scans (bls12_381_amd/csrc/fr_frac.hip.h) and the scan kernels behind
-// it compiled for the HOST (test infrastructure only).  emu_fr_frac WALKS THE PLAN of csrc/fr_frac_plan.h -- the function api_aux.hip
+// it compiled for the HOST (test infrastructure only).  emu_fr_frac WALKS THE PLAN of csrc/fr_frac_plan.h -- the function api_fr.hip
 // launches from -- step by step, with its grids, blocks, LDS sizes and buffer roles, at whatever (block, chunk) the test asks for: a tile
 // of 64 x 2 elements reaches the multi-tile path at 129 elements and the second aggregate level at 128 * 128 + 1.
 //

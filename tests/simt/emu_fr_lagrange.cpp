@@ -1,5 +1,5 @@
 // tests/simt/emu_fr_lagrange.cpp -- the Lagrange-coefficient kernel of bls12_381_amd/csrc/fr_lagrange.hip.h compiled for the HOST (test
-// infrastructure only).  emu_flg WALKS THE PLAN of csrc/fr_lagrange_plan.h -- the function api_aux.hip launches from -- with its grid,
+// infrastructure only).  emu_flg WALKS THE PLAN of csrc/fr_lagrange_plan.h -- the function api_fr.hip launches from -- with its grid,
 // block, team, tile and LDS size, at whatever shape the test asks for: 4 lanes with a tile of 4 nodes and 2 nodes per lane and pass make
 // a pass of 8 nodes, so a few dozen nodes reach every path (several passes, several tiles, a repeat across tiles, the trees); 8 lanes in
 // two teams of 4 are the WAVE shape with two segments per workgroup.  block == 0 takes the shipped shape, `which` choosing between the

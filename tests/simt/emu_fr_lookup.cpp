@@ -1,6 +1,6 @@
 // tests/simt/emu_fr_lookup.cpp -- the Fr lookup kernels (bls12_381_amd/csrc/fr_lookup.hip.h) compiled for the HOST (test
 // infrastructure only).  emu_fr_lookup_run builds a table and counts against it with k_frl_build, k_frl_count and k_frl_finish launched
-// FROM THE PLAN of csrc/fr_lookup_plan.h -- the function api_aux.hip launches from -- at whatever block and path threshold the test asks
+// FROM THE PLAN of csrc/fr_lookup_plan.h -- the function api_fr.hip launches from -- at whatever block and path threshold the test asks
 // for: at block 64 a table of 1000 rows is built by sixteen workgroups, and with the threshold lowered to 64 a table of 65 rows takes the
 // cache path.
 //

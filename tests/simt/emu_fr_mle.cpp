@@ -1,6 +1,6 @@
 // tests/simt/emu_fr_mle.cpp -- the multilinear kernels of bls12_381_amd/csrc/fr_mle.hip.h (fold, eq table, sumcheck round and its finish)
 // compiled for the HOST (test infrastructure only).  Every entry point here WALKS A PLAN of csrc/fr_mle_plan.h -- the functions
-// api_aux.hip launches from -- step by step, with its grids, blocks, LDS sizes, buffer roles and pitches, at whatever (block, chunk) the
+// api_fr.hip launches from -- step by step, with its grids, blocks, LDS sizes, buffer roles and pitches, at whatever (block, chunk) the
 // test asks for: a tile of 64 x 1 positions reaches the multi-workgroup path and the finish kernel at m = 8.
 //
 // The kernels add across lanes with __shfl_down and meet at the workgroup barrier, so every launch runs its block on one host thread per
@@ -22,7 +22,7 @@ namespace {
 
 FrMleShape shape_of(int block, int chunk) { FrMleShape s; s.block = block; s.chunk = chunk; return s; }
 
-// api_aux.hip's frmle_launch with the launches replaced by the lane pool
+// api_fr.hip's frmle_launch with the launches replaced by the lane pool
 int walk(const FrMlePlan& plan, FrMleShape shape, const u32* in, size_t pitch_in, u32* out, size_t pitch_out, const u32* r, const u32* point, size_t k, const FrmProg* prog,
          u32* scratch, u32* rec, int* kernels_out) {
   if (plan.n_steps < 0) return -1;

@@ -1,5 +1,5 @@
 // tests/simt/emu_fr_spmv.cpp -- the sparse matrix-vector product kernels of bls12_381_amd/csrc/fr_spmv.hip.h compiled for the HOST (test
-// infrastructure only).  emu_fr_spmv WALKS THE PLAN of csrc/fr_spmv_plan.h -- the function api_aux.hip launches from -- step by step,
+// infrastructure only).  emu_fr_spmv WALKS THE PLAN of csrc/fr_spmv_plan.h -- the function api_fr.hip launches from -- step by step,
 // with its grids, blocks, LDS sizes and record sizes, at whatever (block, chunk) the test asks for: with a tile of 64 x 2 entries a row
 // of 300 non-zeros already spans three tiles.  emu_fr_spmv_prepare / emu_fr_spmv_validate run the two upload kernels.
 //

@@ -2,7 +2,7 @@
 
 What runs here is the code the GPU runs: `k_fr_twiddles`, `k_fr_tw_levels`, `k_fr_ninv`, `k_fr_coset_table`, `k_fr_stage1`, `k_fr_stage2`,
 `k_fr_cols` (each with and without the coset load) and `k_fr_tile<true>`, launched step by step from the plan of csrc/fr_plan.h -- the
-function api_aux.hip launches from -- with its grids, blocks and arguments; `k_fr_tile<false>`, the single transform's twin, once.
+function api_fr.hip launches from -- with its grids, blocks and arguments; `k_fr_tile<false>`, the single transform's twin, once.
 Every expectation comes from oracle/bls12_381_ref.py (`fr_ntt`, `FR_GENERATOR`, Montgomery conversion): the coset expectation is
 `fr_ntt([x_j g^j])` and, for the inverse, `fr_ntt(y, inverse=True)[j] g^-j`, in Python integers.  Results are compared limb for limb.
 

@@ -2,7 +2,7 @@
 (tests/simt/emu_fr_bary.cpp), against Python integers mod r.
 
 What runs here is the code the GPU runs: `k_frb_tile<eval | open>` in its two modes, `k_frb_row<...>` and `k_frb_quot`, launched step by
-step from the plan of csrc/fr_bary_plan.h -- the function api_aux.hip launches from -- with its grids, blocks, LDS sizes and buffer roles,
+step from the plan of csrc/fr_bary_plan.h -- the function api_fr.hip launches from -- with its grids, blocks, LDS sizes and buffer roles,
 on a twiddle table built by the transform's own kernels.  The plan is driven at the shipped shape (256 lanes x 8 elements) and at small
 ones (64 x 2, 128 x 2), where rows of 256 / 512 elements already lie over several tiles.  Every expectation is computed by the definition
 in Python integers (tests/fr_bary_ref.py: interpolate, Horner, synthetic division, transform back -- not the barycentric formula);

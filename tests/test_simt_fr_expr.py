@@ -2,7 +2,7 @@
 Python-integer interpreter of the program format (tests/fr_expr_ref.py).
 
 What runs here is the code the GPU runs: the image frx_prog_build makes of a validated program, and `k_frx_eval` launched from the plan of
-csrc/fr_expr_plan.h -- the function api_aux.hip launches from -- with its grid, block, LDS size and rows per lane, at the shape
+csrc/fr_expr_plan.h -- the function api_fr.hip launches from -- with its grid, block, LDS size and rows per lane, at the shape
 {block 64, chunk 2}: 128 rows are exactly one tile, 512 four workgroups.  Results are compared limb for limb on the raw 256-bit
 integers, so a non-canonical output does not compare equal.  Every column has exactly the length its col_log_len states and ends
 against an inaccessible page, `out` is pre-filled with a pattern no result has, and everything runs in a child process under a time

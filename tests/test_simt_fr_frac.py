@@ -2,7 +2,7 @@
 (tests/simt/emu_fr_frac.cpp), against Python integers mod r (tests/fr_frac_ref.py).
 
 What runs here is the code the GPU runs: `k_frf_front<GRAND_PRODUCT | FRAC_SUM>` in both modes, then `k_frs_agg` and `k_frs_tile` in SCAN
-mode on the fused output, launched step by step from the plan of csrc/fr_frac_plan.h -- the function api_aux.hip launches from -- with
+mode on the fused output, launched step by step from the plan of csrc/fr_frac_plan.h -- the function api_fr.hip launches from -- with
 its grids, blocks, LDS sizes and buffer roles.  The plan is driven at the shipped shape and at small ones (128 x 2, 64 x 3, 64 x 2),
 where 129 elements already take the multi-tile path and 64 * 2 * 128 + 1 the second aggregate level.  Every expectation is computed in
 Python integers with pow(x, -1, r) (0 for 0); results are compared limb for limb on the raw 256-bit integers, so a non-canonical output

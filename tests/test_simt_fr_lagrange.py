@@ -1,5 +1,5 @@
 """The Lagrange-coefficient kernel (bls12_381_amd/csrc/fr_lagrange.hip.h) on the host: compiled for the CPU through tests/simt_harness.py /
-tests/simt/emu_harness.h, one thread per lane, launched from the plan of csrc/fr_lagrange_plan.h exactly as api_aux.hip launches it, in
+tests/simt/emu_harness.h, one thread per lane, launched from the plan of csrc/fr_lagrange_plan.h exactly as api_fr.hip launches it, in
 BOTH shapes, at a tiny shape (teams of 4 lanes, an LDS tile of 4 nodes, 2 nodes per lane and pass) and at the shipped ones.  Every
 expectation is the formula of tests/fr_lagrange_ref.py in Python integers, compared limb for limb.
 

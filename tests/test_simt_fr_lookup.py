@@ -2,7 +2,7 @@
 dict over key tuples (tests/fr_lookup_ref.py).
 
 What runs here is the code the GPU runs: `k_frl_build`, `k_frl_count` and `k_frl_finish` launched from the plan of
-csrc/fr_lookup_plan.h -- the function api_aux.hip launches from -- with the lanes of a workgroup as threads, at block 64 (a table of
+csrc/fr_lookup_plan.h -- the function api_fr.hip launches from -- with the lanes of a workgroup as threads, at block 64 (a table of
 1000 rows is built by sixteen workgroups, 4096 looked-up rows are 64 batches) and at the shipped 256.  mult is compared limb for limb on
 the raw 256-bit integers (a non-canonical output does not compare equal), index, missing and distinct as integers.  The table, the
 looked-up rows, every output and the handle's own arrays end against an inaccessible page, outputs and counters are pre-filled with

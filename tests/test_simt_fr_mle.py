@@ -2,7 +2,7 @@
 device code compiled for the HOST (tests/simt/emu_fr_mle.cpp), against Python integers mod r.
 
 What runs here is the code the GPU runs: `k_frm_fold`, `k_frm_eq`, `k_frm_round<plain | fused>` and `k_frm_round_finish`, launched step by
-step from the plans of csrc/fr_mle_plan.h -- the functions api_aux.hip launches from -- with their grids, blocks, LDS sizes, buffer roles
+step from the plans of csrc/fr_mle_plan.h -- the functions api_fr.hip launches from -- with their grids, blocks, LDS sizes, buffer roles
 and pitches, and the term program through the same validation (frm_prog_build), which folds the 2^5 bookkeeping into the coefficients.
 The plans are driven at the shipped shape (256 lanes x 4 positions) and at small ones (64 x 1, 64 x 3: a ragged last tile), where a few
 hundred elements already take several workgroups and the finish kernel.  Every expectation is computed here in Python integers from the

@@ -2,7 +2,7 @@
 (tests/simt/emu_fr_scan.cpp), against Python integers mod r.
 
 What runs here is the code the GPU runs: `k_frs_tile<SUM | PRODUCT | HORNER>` in its three modes, `k_frs_agg<...>` in its two and
-`k_frs_invert`, launched step by step from the plan of csrc/fr_scan_plan.h -- the function api_aux.hip launches from -- with its grids,
+`k_frs_invert`, launched step by step from the plan of csrc/fr_scan_plan.h -- the function api_fr.hip launches from -- with its grids,
 blocks, LDS sizes and buffer roles.  The plan is driven at the shipped shape (256 lanes x 8 elements) and at small ones (128 x 2,
 64 x 3, 64 x 2), where 129 elements already take the multi-tile path and 64 * 2 * 128 + 1 the second aggregate level.  Every
 expectation is computed here in Python integers (the defining recurrences); results are compared limb for limb, so a non-canonical

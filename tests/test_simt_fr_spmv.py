@@ -2,7 +2,7 @@
 Python integers mod r.
 
 What runs here is the code the GPU runs: the upload kernels `k_frsp_prepare` / `k_frsp_validate`, then `k_frsp_tile` and `k_frsp_fixup`
-launched step by step from the plan of csrc/fr_spmv_plan.h -- the function api_aux.hip launches from -- with its grids, blocks, LDS sizes
+launched step by step from the plan of csrc/fr_spmv_plan.h -- the function api_fr.hip launches from -- with its grids, blocks, LDS sizes
 and record sizes.  The plan is driven at small tiles (64 lanes x 2 entries = 128, 128 x 2 = 256), where a row of 300 entries spans three
 tiles, and once at the shipped shape (256 x 8 = 2048).  Every expectation is out[v][i] = sum val[p] x[v][col[p]] in Python integers;
 results are compared limb for limb, so a non-canonical output does not compare equal.  The output buffer is pre-filled with a

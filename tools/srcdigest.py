@@ -10,7 +10,7 @@ _FAMILY = {
     "msm": ["msm.hip.h", "team.hip.h", "abi_kernels.hip.h", "api_msm.hip"],
     "mul": ["mulbatch.hip.h", "msm.hip.h", "api_msm.hip"],
     "pairing": ["pairing.hip.h", "quad.hip.h", "prep.hip.h", "api_pairing.hip"],
-    "aux": ["codec.hip.h", "h2c.hip.h", "expand.hip.h", "fr.hip.h", "api_aux.hip"],
+    "aux": ["codec.hip.h", "h2c.hip.h", "expand.hip.h", "fr.hip.h", "api_aux.hip", "api_fr.hip"],       # the ntt legs launch from api_fr.hip
 }
 _TAG = {"msm": "msm", "g2_msm": "msm", "g1_mul_batch": "mul", "g2_mul_batch": "mul", "pairing": "pairing", "mml": "pairing", "equations": "pairing",
         "equations_prepared": "pairing", "mml_prepared": "pairing", "pairing_wide": "pairing", "ntt": "aux", "hash_to_g1": "aux", "hash_to_g2": "aux",
