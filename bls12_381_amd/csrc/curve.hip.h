@@ -187,13 +187,15 @@ DEV Xyzz<F> xyzz_add_mixed(const Xyzz<F>& p, bool& inf, const XT& qx, const YT& 
   auto ZZZ3 = mul(p.zzz, PPP);
   Xyzz<F> r; r.x = F::st(X3); r.y = F::st(Y3); r.zz = F::st(ZZ3); r.zzz = F::st(ZZZ3); return r;
 }
-// G1 variant with the ten field products inlined (one straight-line ~35 KB body, no call overhead)
-template <class XT, class YT>
+// G1 variant with the ten field products inlined (one straight-line ~35 KB body, no call overhead).  SEQ: every column sum of the
+// products is one multiply-add chain that starts from the previous column's carry (mac() in fe.hip.h) -- the form of the bucket
+// accumulation of the large MSM; the segmented accumulation, which has no register to give, keeps the free order.
+template <bool SEQ = false, class XT, class YT>
 DEV Xyzz<FpPolicy> xyzz_add_mixed_inl(const Xyzz<FpPolicy>& p, bool& inf, const XT& qx, const YT& qy) {
   typedef FpPolicy F;
   if (inf) { inf = false; return xyzz_from_affine<F>(qx, qy); }
-  auto U2 = mul_inl(qx, p.zz);
-  auto S2 = mul_inl(qy, p.zzz);
+  auto U2 = mul_inl<SEQ>(qx, p.zz);
+  auto S2 = mul_inl<SEQ>(qy, p.zzz);
   auto P = sub(U2, p.x);          // limbs <= 3 * 2^28: still inside the multiplier's column bound
   auto R = sub(S2, p.y);
   if (is_zero_fast(P)) {
@@ -201,13 +203,13 @@ DEV Xyzz<FpPolicy> xyzz_add_mixed_inl(const Xyzz<FpPolicy>& p, bool& inf, const 
     inf = true;
     return p;
   }
-  auto PP = sqr_inl(P);
-  auto PPP = mul_inl(P, PP);
-  auto Q = mul_inl(p.x, PP);
-  auto X3 = norm(sub(sqr_inl(R), add(PPP, dbl(Q))));
-  auto Y3 = sop2_inl(R, norm(sub(Q, X3)), neg(p.y), PPP);       // R (Q - X3) - Y1 PPP with one reduction
-  auto ZZ3 = mul_inl(p.zz, PP);
-  auto ZZZ3 = mul_inl(p.zzz, PPP);
+  auto PP = sqr_inl<SEQ>(P);
+  auto PPP = mul_inl<SEQ>(P, PP);
+  auto Q = mul_inl<SEQ>(p.x, PP);
+  auto X3 = norm(sub(sqr_inl<SEQ>(R), add(PPP, dbl(Q))));
+  auto Y3 = sop2_inl<SEQ>(R, sub(Q, X3), neg(p.y), PPP);             // R (Q - X3) - Y1 PPP with one reduction; limbs 3 * 3 + 2 * 1 + 1 <= 18
+  auto ZZ3 = mul_inl<SEQ>(p.zz, PP);
+  auto ZZZ3 = mul_inl<SEQ>(p.zzz, PPP);
   Xyzz<F> r; r.x = F::st(X3); r.y = F::st(Y3); r.zz = F::st(ZZ3); r.zzz = F::st(ZZZ3); return r;
 }
 // XYZZ -> homogeneous projective (X*ZZZ : Y*ZZ : ZZ*ZZZ); identity -> (0:1:0)

@@ -153,28 +153,52 @@ DEV Fe<1, V> from_v16(v16 a) {
 // ---------------------------------------------------------------------------------------------
 // Montgomery multiplication / squaring (product scanning, one 64-bit accumulator per column).
 // ---------------------------------------------------------------------------------------------
+// One multiply-add of a column sum.  Left to itself the compiler re-associates a column (acc >> 28) + p0 + p1 + ... into a chain of
+// v_mad_u64_u32 that starts from ZERO and joins the shifted carry with a separate 64-bit add (v_lshl_add_u64 x, 0, carry): 26 extra
+// half-rate instructions per product, 5 % of the G1 accumulation loop (profiles/msm_acc_instruction_budget.md).  With SEQ the sum
+// stays in source order, so the carry is the addend of the column's first multiply-add and the join disappears.  What holds the
+// order is ONE empty asm statement (no instruction text) per partial sum: it only READS the sum -- a second use, and the
+// re-association folds single-use sums only -- and passes a token through, the limb mask, which the product's last column then
+// uses so that the statements stay alive.  (The obvious form, the sum itself as the statement's in/out operand, costs more than
+// it saves on gfx950: the hazard recogniser assumes a forwarding hazard for a register an asm statement defines and puts an
+// s_nop in front of the multiply-add that reads it next, a thousand per addition, measured 4 % of the loop.  The token is read
+// next by another asm statement, never by the ALU, but for the one use at the end.)  The price is a serial chain per product: the
+// bucket accumulation, two wavefronts per SIMD, is 4-5 % faster all the same (its isolated launch 3 %); the out-of-line routines of
+// the pairing kernels and the segmented accumulation keep the free order (SEQ = false compiles to what it always did).
+template <bool SEQ>
+DEV void mac(u64& acc, u32& tok, u32 a, u32 b) {
+  acc += (u64)a * b;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (SEQ) asm("" : "+v"(tok) : "v"(acc));
+#endif
+}
+// the limb mask of a product's last column: the token of its mac() chain
+template <bool SEQ> DEV u32 last_mask(u32 tok) { return SEQ ? tok : LMASK; }
+
+template <bool SEQ = false>
 DEV v16 fe_mul_body(v16 a, v16 b) {
   constexpr PLimbs p = P_L;
   u32 m[NL];
   v16 r;
   u64 acc = 0;
+  u32 tok = LMASK;
 #pragma unroll
   for (int k = 0; k < NL; k++) {
 #pragma unroll
-    for (int i = 0; i <= k; i++) acc += (u64)a[i] * b[k - i];
+    for (int i = 0; i <= k; i++) mac<SEQ>(acc, tok, a[i], b[k - i]);
 #pragma unroll
-    for (int i = 0; i < k; i++) acc += (u64)m[i] * p.l[k - i];
+    for (int i = 0; i < k; i++) mac<SEQ>(acc, tok, m[i], p.l[k - i]);
     m[k] = ((u32)acc * BLS_INV28) & LMASK;
-    acc += (u64)m[k] * p.l[0];
+    mac<SEQ>(acc, tok, m[k], p.l[0]);
     acc >>= LW;
   }
 #pragma unroll
   for (int k = NL; k < 2 * NL - 1; k++) {
 #pragma unroll
-    for (int i = k - NL + 1; i < NL; i++) acc += (u64)a[i] * b[k - i];
+    for (int i = k - NL + 1; i < NL; i++) mac<SEQ>(acc, tok, a[i], b[k - i]);
 #pragma unroll
-    for (int i = k - NL + 1; i < NL; i++) acc += (u64)m[i] * p.l[k - i];
-    r[k - NL] = (u32)acc & LMASK;
+    for (int i = k - NL + 1; i < NL; i++) mac<SEQ>(acc, tok, m[i], p.l[k - i]);
+    r[k - NL] = (u32)acc & (k == 2 * NL - 2 ? last_mask<SEQ>(tok) : LMASK);
     acc >>= LW;
   }
   r[NL - 1] = (u32)acc;
@@ -182,6 +206,7 @@ DEV v16 fe_mul_body(v16 a, v16 b) {
   return r;
 }
 
+template <bool SEQ = false>
 DEV v16 fe_sqr_body(v16 a) {
   constexpr PLimbs p = P_L;
   u32 m[NL], a2[NL];
@@ -189,25 +214,26 @@ DEV v16 fe_sqr_body(v16 a) {
 #pragma unroll
   for (int i = 0; i < NL; i++) a2[i] = a[i] << 1;
   u64 acc = 0;
+  u32 tok = LMASK;
 #pragma unroll
   for (int k = 0; k < NL; k++) {
 #pragma unroll
-    for (int i = 0; 2 * i < k; i++) acc += (u64)a[i] * a2[k - i];
-    if ((k & 1) == 0) acc += (u64)a[k / 2] * a[k / 2];
+    for (int i = 0; 2 * i < k; i++) mac<SEQ>(acc, tok, a[i], a2[k - i]);
+    if ((k & 1) == 0) mac<SEQ>(acc, tok, a[k / 2], a[k / 2]);
 #pragma unroll
-    for (int i = 0; i < k; i++) acc += (u64)m[i] * p.l[k - i];
+    for (int i = 0; i < k; i++) mac<SEQ>(acc, tok, m[i], p.l[k - i]);
     m[k] = ((u32)acc * BLS_INV28) & LMASK;
-    acc += (u64)m[k] * p.l[0];
+    mac<SEQ>(acc, tok, m[k], p.l[0]);
     acc >>= LW;
   }
 #pragma unroll
   for (int k = NL; k < 2 * NL - 1; k++) {
 #pragma unroll
-    for (int i = k - NL + 1; 2 * i < k; i++) acc += (u64)a[i] * a2[k - i];
-    if ((k & 1) == 0) acc += (u64)a[k / 2] * a[k / 2];
+    for (int i = k - NL + 1; 2 * i < k; i++) mac<SEQ>(acc, tok, a[i], a2[k - i]);
+    if ((k & 1) == 0) mac<SEQ>(acc, tok, a[k / 2], a[k / 2]);
 #pragma unroll
-    for (int i = k - NL + 1; i < NL; i++) acc += (u64)m[i] * p.l[k - i];
-    r[k - NL] = (u32)acc & LMASK;
+    for (int i = k - NL + 1; i < NL; i++) mac<SEQ>(acc, tok, m[i], p.l[k - i]);
+    r[k - NL] = (u32)acc & (k == 2 * NL - 2 ? last_mask<SEQ>(tok) : LMASK);
     acc >>= LW;
   }
   r[NL - 1] = (u32)acc;
@@ -232,17 +258,17 @@ DEV Fe<1, mul_v(V1, V2)> mul(const Fe<A1, V1>& a, const Fe<A2, V2>& b) {
   static_assert(mul_v(V1, V2) <= MAX_V, "fe mul: value bound too large");
   return from_v16<mul_v(V1, V2)>(fe_mul_raw(to_v16(a), to_v16(b)));
 }
-// force-inlined variants (used by the one kernel whose whole body is a single formula and fits the I-cache)
-template <int A1, int V1, int A2, int V2>
+// force-inlined variants (used by the one kernel whose whole body is a single formula and fits the I-cache); SEQ: see mac()
+template <bool SEQ = false, int A1, int V1, int A2, int V2>
 DEV Fe<1, mul_v(V1, V2)> mul_inl(const Fe<A1, V1>& a, const Fe<A2, V2>& b) {
   static_assert(A1 * A2 <= MAX_A_PROD, "fe mul: limb bound too large, norm() an operand");
   static_assert(mul_v(V1, V2) <= MAX_V, "fe mul: value bound too large");
-  return from_v16<mul_v(V1, V2)>(fe_mul_body(to_v16(a), to_v16(b)));
+  return from_v16<mul_v(V1, V2)>(fe_mul_body<SEQ>(to_v16(a), to_v16(b)));
 }
-template <int A, int V>
+template <bool SEQ = false, int A, int V>
 DEV Fe<1, mul_v(V, V)> sqr_inl(const Fe<A, V>& a) {
   static_assert(A * A <= MAX_A_PROD, "fe sqr: limb bound too large");
-  return from_v16<mul_v(V, V)>(fe_sqr_body(to_v16(a)));
+  return from_v16<mul_v(V, V)>(fe_sqr_body<SEQ>(to_v16(a)));
 }
 
 // mul that renormalises an operand only when the static limb bounds require it
@@ -264,32 +290,34 @@ DEV Fe<1, mul_v(V, V)> sqr(const Fe<A, V>& a) {
 // Sum of two products with ONE Montgomery reduction: (a0*b0 + a1*b1) / R'  (the analogue of the
 // reference's Fp::sum_of_products<2>, fp.rs:430-484).  Column bound: 14*(A00*A01 + A10*A11 + 1) < 256.
 // ---------------------------------------------------------------------------------------------
+template <bool SEQ = false>
 DEV v16 fe_sop2_body(v16 a0, v16 b0, v16 a1, v16 b1) {
   constexpr PLimbs p = P_L;
   u32 m[NL];
   v16 r;
   u64 acc = 0;
+  u32 tok = LMASK;
 #pragma unroll
   for (int k = 0; k < NL; k++) {
 #pragma unroll
-    for (int i = 0; i <= k; i++) acc += (u64)a0[i] * b0[k - i];
+    for (int i = 0; i <= k; i++) mac<SEQ>(acc, tok, a0[i], b0[k - i]);
 #pragma unroll
-    for (int i = 0; i <= k; i++) acc += (u64)a1[i] * b1[k - i];
+    for (int i = 0; i <= k; i++) mac<SEQ>(acc, tok, a1[i], b1[k - i]);
 #pragma unroll
-    for (int i = 0; i < k; i++) acc += (u64)m[i] * p.l[k - i];
+    for (int i = 0; i < k; i++) mac<SEQ>(acc, tok, m[i], p.l[k - i]);
     m[k] = ((u32)acc * BLS_INV28) & LMASK;
-    acc += (u64)m[k] * p.l[0];
+    mac<SEQ>(acc, tok, m[k], p.l[0]);
     acc >>= LW;
   }
 #pragma unroll
   for (int k = NL; k < 2 * NL - 1; k++) {
 #pragma unroll
-    for (int i = k - NL + 1; i < NL; i++) acc += (u64)a0[i] * b0[k - i];
+    for (int i = k - NL + 1; i < NL; i++) mac<SEQ>(acc, tok, a0[i], b0[k - i]);
 #pragma unroll
-    for (int i = k - NL + 1; i < NL; i++) acc += (u64)a1[i] * b1[k - i];
+    for (int i = k - NL + 1; i < NL; i++) mac<SEQ>(acc, tok, a1[i], b1[k - i]);
 #pragma unroll
-    for (int i = k - NL + 1; i < NL; i++) acc += (u64)m[i] * p.l[k - i];
-    r[k - NL] = (u32)acc & LMASK;
+    for (int i = k - NL + 1; i < NL; i++) mac<SEQ>(acc, tok, m[i], p.l[k - i]);
+    r[k - NL] = (u32)acc & (k == 2 * NL - 2 ? last_mask<SEQ>(tok) : LMASK);
     acc >>= LW;
   }
   r[NL - 1] = (u32)acc;
@@ -299,11 +327,11 @@ DEV v16 fe_sop2_body(v16 a0, v16 b0, v16 a1, v16 b1) {
 
 // typed, inlined form: a0*b0 + a1*b1 with one reduction
 constexpr int sop2_v(int v00, int v01, int v10, int v11) { return 1 + (v00 * v01 + v10 * v11 + V_DIV - 1) / V_DIV; }
-template <int A00, int V00, int A01, int V01, int A10, int V10, int A11, int V11>
+template <bool SEQ = false, int A00, int V00, int A01, int V01, int A10, int V10, int A11, int V11>
 DEV Fe<1, sop2_v(V00, V01, V10, V11)> sop2_inl(const Fe<A00, V00>& a0, const Fe<A01, V01>& b0, const Fe<A10, V10>& a1, const Fe<A11, V11>& b1) {
   static_assert(A00 * A01 + A10 * A11 + 1 <= MAX_A_PROD + 1, "fe sop2: limb bound too large, norm() an operand");
   static_assert(sop2_v(V00, V01, V10, V11) <= MAX_V, "fe sop2: value bound too large");
-  return from_v16<sop2_v(V00, V01, V10, V11)>(fe_sop2_body(to_v16(a0), to_v16(b0), to_v16(a1), to_v16(b1)));
+  return from_v16<sop2_v(V00, V01, V10, V11)>(fe_sop2_body<SEQ>(to_v16(a0), to_v16(b0), to_v16(a1), to_v16(b1)));
 }
 
 // Fp2 product core: c0 = a0 b0 - a1 b1, c1 = a0 b1 + a1 b0, two reductions in total.

@@ -806,7 +806,7 @@ __global__ void __launch_bounds__(BLS_ACC_BLOCK) k_msm_accumulate(const u32* __r
         auto qy = cond_neg(q.y, (e >> 31) != 0);
         // G1: the ten field products are inlined (one ~35 KB straight-line body; measured 8% faster than calls even
         // at 2 waves/SIMD).  G2 keeps the out-of-line Fp2 products (its body would not fit the instruction cache).
-        if constexpr (std::is_same<F, FpPolicy>::value) acc = xyzz_add_mixed_inl(acc, acc_inf, q.x, qy);
+        if constexpr (std::is_same<F, FpPolicy>::value) acc = xyzz_add_mixed_inl<true>(acc, acc_inf, q.x, qy);
         else acc = xyzz_add_mixed<F>(acc, acc_inf, q.x, qy);
       }
       q = qn; inf = infn; e = e_next; e_next = e_next2;

@@ -78,7 +78,9 @@ def msm():
     hbm = (2 * fetch_kb + write_kb) * 1024
     n, W = 1 << 20, 16
     alg = W * n * (128 + 4) + (1 << 18) * 176
-    mads = W * n * (7 * 406 + 2 * 315 + 602)
+    # per mixed addition: 6 mul (406) + 2 sqr (315) + 1 two-product sum (602) = 3 668 by formula, 3 542 v_mad_u64_u32 in the ISA: the
+    # compiler turns 126 of the m * p products into shifts and subtractions (profiles/msm_acc_instruction_budget.md)
+    mads = W * n * (6 * 406 + 2 * 315 + 602 - 126)
     j = {"kernel": K, "workload": "2^20-point G1 MSM (GLV: 2^21 terms x 8 windows, c=16)", "launch_avg_ns": dur, "launches": len(d),
          "launch_pipelined_avg_ns": sum(pipe) / max(1, len(pipe)), "launch_isolated_avg_ns": sum(iso) / max(1, len(iso)),
          "FETCH_SIZE_KB_raw": fetch_kb, "WRITE_SIZE_KB": write_kb, "hbm_bytes_per_launch_corrected": hbm,
@@ -99,7 +101,7 @@ Separate rocprofv3 passes (one `--pmc` group each, `--kernel-trace` only; tools/
 * registers / scratch per lane (code-object metadata): {j['vgpr']} VGPR, {j['scratch']} B scratch
 * FETCH_SIZE = {fetch_kb:.0f} KB raw -> x2 (gfx950 half-count of 16-byte-per-lane reads) = {2*fetch_kb*1024/1e9:.2f} GB;  WRITE_SIZE = {write_kb:.0f} KB = {write_kb*1024/1e9:.2f} GB
 * HBM-side traffic per launch = {hbm/1e9:.2f} GB (algorithmic: 8 windows x 2^21 gathers x (128 B record + 4 B index) + 2^18 x 176 B bucket records = {alg/1e9:.2f} GB); at {dur/1e3:.0f} us that is {hbm/dur/1e3:.2f} TB/s = {100*hbm/dur/1e3/8:.0f}% of the 8 TB/s HBM peak: not memory-bound.  With GLV the gathers range over 256 MB (bases + their endomorphism images), the size of the Infinity Cache.
-* SQ_INSTS_VALU = {c.get('SQ_INSTS_VALU',0):.3e} wave-instructions, of which {mads/64:.3e} are the v_mad_u64_u32 of the 7 mul + 2 sqr + one two-product sum per mixed addition ({100*mads/64/max(c.get('SQ_INSTS_VALU',1),1):.0f}%).
+* SQ_INSTS_VALU = {c.get('SQ_INSTS_VALU',0):.3e} wave-instructions, of which {mads/64:.3e} are the v_mad_u64_u32 of the 6 mul + 2 sqr + one two-product sum per mixed addition, 3 542 in the ISA ({100*mads/64/max(c.get('SQ_INSTS_VALU',1),1):.0f}%).
 * wave-cycle split: SQ_ACTIVE_INST_ANY {100*c.get('SQ_ACTIVE_INST_ANY',0)/wc:.0f}%, SQ_WAIT_INST_ANY (issue stalls) {100*c.get('SQ_WAIT_INST_ANY',0)/wc:.0f}%, SQ_WAIT_ANY (s_waitcnt) {100*c.get('SQ_WAIT_ANY',0)/wc:.0f}% of SQ_WAVE_CYCLES = {wc:.3e}
 * instruction cache: {c.get('SQC_ICACHE_MISSES',0):.3e} misses of {c.get('SQC_ICACHE_REQ',0):.3e} requests
 * GRBM_GUI_ACTIVE = {c.get('GRBM_GUI_ACTIVE',0):.3e} (summed over 8 XCDs) -> {ghz:.2f} GHz effective clock under profiling.
