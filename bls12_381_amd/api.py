@@ -369,6 +369,75 @@ class KzgMultiproof:
             pass
 
 
+class KzgCellVerifier:
+    """A verifier of KZG cell proofs resident on the device (`blsgpu_kzg_cell_verifier`), built once by Context.kzg_cell_verifier_create:
+    S[0..l), the `G2Prepared` table {q, -G2} and the powers of w.  .verify decides every batch of (commitment, cell index, cell, proof)
+    tuples by one two-term pairing product (include/bls12_381_hip.h)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    @property
+    def log_n(self):
+        return int(self.ctx.lib.blsgpu_kzg_cell_verifier_log_n(self.handle))
+
+    @property
+    def log_l(self):
+        return int(self.ctx.lib.blsgpu_kzg_cell_verifier_log_l(self.handle))
+
+    @property
+    def cells(self):
+        """2c, the number of cells per polynomial"""
+        return int(self.ctx.lib.blsgpu_kzg_cell_verifier_cells(self.handle))
+
+    def verify(self, commit_xy, commit_inf, row, col, cells, proof_xy, proof_inf, offsets, r, order=FR_ORDER_NATURAL, return_ab=False):
+        """commit_xy (ncommit, 12) u64 affine wire points with their infinity bytes (None: none is the identity); row / col: m u32 each;
+        cells: (m, l, 4) u64 Montgomery limbs or Python ints in [0, r) nested the same way, entries numbered by `order` as kzg_cells
+        writes them; proof_xy (m, 12) with proof_inf; offsets: nseg + 1 u32, batch s owns the cells offsets[s] .. offsets[s + 1]; r: nseg
+        challenges (limbs or ints).  Returns the nseg verdict bytes, and with return_ab the (nseg, 2, 18) projective wire points
+        (A_s, B_s) as well (compare after batch_normalize)."""
+        l = 1 << self.log_l
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        nseg = max(off.shape[0] - 1, 0)
+        m = int(off[-1]) if nseg else 0
+        cxy = _u64(commit_xy, (-1, 12)) if commit_xy is not None else np.zeros((0, 12), dtype=np.uint64)
+        ncommit = cxy.shape[0]
+        cinf = np.zeros(ncommit, dtype=np.uint8) if commit_inf is None else _flags(commit_inf, ncommit)
+        rw = np.ascontiguousarray(row, dtype=np.uint32).reshape(-1)
+        cl = np.ascontiguousarray(col, dtype=np.uint32).reshape(-1)
+        pxy = _u64(proof_xy, (-1, 12)) if m else np.zeros((0, 12), dtype=np.uint64)
+        if rw.shape[0] != m or cl.shape[0] != m or pxy.shape[0] != m:
+            raise ValueError("kzg_cell_verifier.verify: row, col and proof_xy must hold offsets[-1] entries")
+        pinf = np.zeros(m, dtype=np.uint8) if proof_inf is None else _flags(proof_inf, m)
+        v = _fr_limbs(cells, (m, l), "kzg_cell_verifier.verify: cells") if m else np.zeros((0, l, 4), dtype=np.uint64)
+        ch = _fr_limbs(r, (nseg,), "kzg_cell_verifier.verify: r") if nseg else np.zeros((0, 4), dtype=np.uint64)
+        verdict = np.zeros(nseg, dtype=np.uint8)
+        ab = np.zeros((nseg, 2, 18), dtype=np.uint64) if return_ab else None
+        some = lambda a: _ptr(a) if a.size else None
+        check(self.ctx.lib.blsgpu_kzg_verify_cells(self.ctx.h, self.handle, some(cxy), some(cinf), ncommit, some(rw), some(cl), some(v), some(pxy), some(pinf),
+                                                   _ptr(off) if nseg else None, nseg, some(ch), int(order), some(verdict), some(ab) if return_ab else None), "kzg_verify_cells")
+        return (verdict, ab) if return_ab else verdict
+
+    def verify_device(self, d_commit_xy, d_commit_inf, ncommit, d_row, d_col, d_cells, d_proof_xy, d_proof_inf, d_offsets, nseg, m, d_r, d_verdict, d_out_ab=None,
+                      order=FR_ORDER_NATURAL):
+        """the same on arrays in device memory (device pointers as ints; scalars 16-byte aligned, points 8-byte, u32 arrays 4-byte; no
+        overlap of an output with anything); asynchronous on the context's stream.  A bad index or a broken batch gives that batch verdict 0
+        and is reported by the next synchronize."""
+        check(self.ctx.lib.blsgpu_kzg_verify_cells_device(self.ctx.h, self.handle, d_commit_xy, d_commit_inf, int(ncommit), d_row, d_col, d_cells, d_proof_xy, d_proof_inf, d_offsets,
+                                                          int(nseg), int(m), d_r, int(order), d_verdict, d_out_ab), "kzg_verify_cells_device")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_kzg_cell_verifier_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _kzg_polys(polys, n, what):
     """count polynomials of n scalars -> a contiguous (count, n, 4) u64 array of Montgomery limbs ((n, 4) / a flat list of n ints: count = 1)"""
     if isinstance(polys, np.ndarray):
@@ -1592,6 +1661,17 @@ class Context:
         h = ctypes.c_void_p()
         check(self.lib.blsgpu_kzg_multiproof_create(self.h, srs_g1.handle if srs_g1 is not None else None, int(log_n), int(log_l), ctypes.byref(h)), "kzg_multiproof_create")
         return KzgMultiproof(self, h)
+
+    def kzg_cell_verifier_create(self, srs_g1, log_n, log_l, q_xy, q_inf=False):
+        """batched verification of KZG cell proofs (include/bls12_381_hip.h): the handle for cells of 2^log_l points of polynomials of
+        2^log_n coefficients over the first 2^log_l points of the resident G1 bases `srs_g1` and the affine G2 wire point q (24 u64),
+        meant as [tau^l] G2; the caller vouches that q is in the subgroup.  A setup call; the handle keeps no reference to the SRS."""
+        q = _u64(q_xy, (24,)) if q_xy is not None else None
+        qi = np.array([1 if q_inf else 0], dtype=np.uint8)
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_kzg_cell_verifier_create(self.h, srs_g1.handle if srs_g1 is not None else None, int(log_n), int(log_l), _ptr(q), _ptr(qi), ctypes.byref(h)),
+              "kzg_cell_verifier_create")
+        return KzgCellVerifier(self, h)
 
     def kzg_cells(self, polys, log_l, form=KZG_FORM_COEFFS, order=FR_ORDER_NATURAL):
         """the 2c cells of l = 2^log_l evaluations of every polynomial: polys as for KzgMultiproof.proofs (n a power of two); returns a

@@ -8,6 +8,7 @@
 #include "gsum.hip.h"
 #include "lagrange_combine.hip.h"
 #include "kzg.hip.h"
+#include "kzg_verify.hip.h"
 
 // ---------------------------------------------------------------------------------------------------
 // bases
@@ -1263,6 +1264,178 @@ extern "C" int blsgpu_kzg_cells(blsgpu_ctx* c, const uint64_t* polys, int log_n,
   void* o = h.out(c->io_out, cells, (count << (log_n + 1)) * 32);
   if (h.rc) return h.rc;
   return h.finish(kzg_cells_device(c, dp, log_n, log_l, count, form, order, o));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// batched KZG cell-proof verification (kzg_verify.hip.h; kzg_verify_plan.h holds the checks, the maps, the fold's cut and the scratch
+// layout): a random linear combination of all cells of a batch, decided by ONE two-term pairing product.  The chain joins the entry
+// points that exist on the context's stream, as blsgpu_bls_verify_batch does for signatures; it never synchronises.
+// ---------------------------------------------------------------------------------------------------
+static void kzgv_drop(blsgpu_kzg_cell_verifier* h) {
+  if (h->s) bases_drop(h->s);
+  if (h->table) blsgpu_g2_prepared_free(h->table);
+  if (h->roots) hipFree(h->roots);
+  delete h;
+}
+extern "C" int blsgpu_kzg_cell_verifier_create(blsgpu_ctx* c, const blsgpu_bases* srs, int log_n, int log_l, const uint64_t* q_xy, const uint8_t* q_inf,
+                                               blsgpu_kzg_cell_verifier** out) { CTX_CLAIM(c);
+  if (!c) return bad("kzg_cell_verifier_create: ctx is NULL");
+  KzgvCreateArgs a;
+  a.srs_given = srs != nullptr; a.q_given = q_xy != nullptr; a.out_given = out != nullptr; a.log_n = log_n; a.log_l = log_l;
+  if (srs) { a.srs_group = srs->group; a.srs_len = srs->n; a.srs_subgroup = srs->subgroup; }
+  if (const char* why = kzgv_check_create(a)) return bad(why);
+  if (srs->device != c->device) return bad("kzg_cell_verifier_create: the SRS lives on another device than the context");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t l = (size_t)1 << log_l;
+  blsgpu_kzg_cell_verifier* h = new blsgpu_kzg_cell_verifier();
+  h->device = c->device; h->log_n = log_n; h->log_l = log_l;
+  KzgTmp tmp;                                                    // S[0..l) in wire form with its flags; the two G2 points with theirs
+  if (hipMalloc(&tmp.p[0], l * 96) != hipSuccess || hipMalloc(&tmp.p[1], l) != hipSuccess || hipMalloc(&tmp.p[2], 2 * 192) != hipSuccess || hipMalloc(&tmp.p[3], 16) != hipSuccess ||
+      hipMalloc((void**)&h->roots, (size_t)(log_n + 1) * 32) != hipSuccess) {
+    (void)hipGetLastError(); kzgv_drop(h); g_err = "hipMalloc(kzg_cell_verifier_create) failed"; return BLSGPU_ERR_HIP;
+  }
+  auto run = [&]() -> int {
+    if (!srs->ready_seen) {
+      if (hipEventQuery(srs->ev_ready) == hipSuccess) srs->ready_seen = true;
+      else HIPCHK(hipStreamWaitEvent(c->stream, srs->ev_ready, 0));
+    }
+    if (int rc = bases_export<FpPolicy>(c, srs, 0, l, tmp.p[0], tmp.p[1])) return rc;
+    // (a tested or vouched-for SRS needs no second subgroup test; an untested one -- state 3 -- gets the import's own)
+    if (int rc = bases_import<FpPolicy>(c, tmp.p[0], tmp.p[1], l, &h->s, false, srs->subgroup == 1 || srs->subgroup == 2)) return rc;
+    if (h->s->subgroup == 0) return bad("kzg_cell_verifier_create: the SRS holds a point outside the prime-order subgroup");
+    HIPCHK(hipMemcpyAsync(tmp.p[2], q_xy, 192, hipMemcpyHostToDevice, c->stream));
+    KLAUNCH(k_kzgv_table_points, dim3(1), dim3(64), 0, c->stream, (u32*)tmp.p[2], (uint8_t*)tmp.p[3], (q_inf && *q_inf) ? 1 : 0);
+    KLAUNCH(k_kzgv_roots, dim3(1), dim3(64), 0, c->stream, h->roots, log_n);
+    LAUNCHCHK();
+    if (int rc = blsgpu_g2_prepare_device(c, tmp.p[2], tmp.p[3], 2, &h->table)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));                     // a setup call: the temporaries go, and the handle keeps no reference to the SRS
+    return BLSGPU_OK;
+  };
+  if (int rc = run()) {
+    (void)hipStreamSynchronize(c->stream);
+    kzgv_drop(h);
+    return rc;
+  }
+  *out = h;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_kzg_cell_verifier_log_n(const blsgpu_kzg_cell_verifier* h) { return h ? h->log_n : -1; }
+extern "C" int blsgpu_kzg_cell_verifier_log_l(const blsgpu_kzg_cell_verifier* h) { return h ? h->log_l : -1; }
+extern "C" size_t blsgpu_kzg_cell_verifier_cells(const blsgpu_kzg_cell_verifier* h) { return h ? (size_t)2 << (h->log_n - h->log_l) : 0; }
+extern "C" void blsgpu_kzg_cell_verifier_free(blsgpu_kzg_cell_verifier* h) {
+  if (!h) return;
+  handle_quiesce(h->device);                                     // an asynchronous call may still be reading the bases, the table or the roots
+  if (h->s) blsgpu_bases_free(h->s);
+  if (h->table) blsgpu_g2_prepared_free(h->table);
+  if (h->roots) hipFree(h->roots);
+  delete h;
+}
+static KzgvArgs kzgv_args(const blsgpu_kzg_cell_verifier* h, const void* commit_xy, const void* commit_inf, size_t ncommit, const void* row, const void* col, const void* cells,
+                          const void* proof_xy, const void* proof_inf, const void* offsets, size_t nseg, size_t m, const void* r, int order, const void* verdict, const void* out_ab,
+                          bool device) {
+  KzgvArgs a;
+  a.handle_given = h != nullptr;
+  if (h) { a.log_n = h->log_n; a.log_l = h->log_l; }
+  a.commit_xy = commit_xy; a.commit_inf = commit_inf; a.ncommit = ncommit; a.row = row; a.col = col; a.cells = cells; a.proof_xy = proof_xy; a.proof_inf = proof_inf;
+  a.offsets = offsets; a.nseg = nseg; a.m = m; a.r = r; a.order = order; a.verdict = verdict; a.out_ab = out_ab; a.device = device;
+  return a;
+}
+static int kzg_verify_device(blsgpu_ctx* c, const blsgpu_kzg_cell_verifier* h, const void* d_commit_xy, const void* d_commit_inf, size_t ncommit, const void* d_row,
+                             const void* d_col, const void* d_cells, const void* d_proof_xy, const void* d_proof_inf, const void* d_offsets, size_t nseg, size_t m, const void* d_r,
+                             int order, void* d_verdict, void* d_out_ab) {
+  if (!c) return bad("kzg_verify_cells: ctx is NULL");
+  const KzgvArgs a = kzgv_args(h, d_commit_xy, d_commit_inf, ncommit, d_row, d_col, d_cells, d_proof_xy, d_proof_inf, d_offsets, nseg, m, d_r, order, d_verdict, d_out_ab, true);
+  if (const char* why = kzgv_check(a)) return bad(why);
+  if (h->device != c->device) return bad("kzg_verify_cells: the handle lives on another device than the context");
+  if (!nseg) return BLSGPU_OK;
+  const KzgvPlan p = kzgv_plan(h->log_n, h->log_l, m, nseg);
+  if (!p.ok) return bad("kzg_verify_cells: the plan refuses the shape");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->kzgv.reserve(p.bytes)) { g_err = "hipMalloc(kzg_verify_cells scratch) failed"; return BLSGPU_ERR_HIP; }
+  hipStream_t st = c->stream;
+  uint8_t* base = c->kzgv.as<uint8_t>();
+  const int log_n = p.log_n, log_l = p.log_l;
+  u32* eff = (u32*)(base + p.eff);
+  uint8_t *mis = base + p.mis, *badidx = base + p.badidx, *badf = base + p.bad, *isone = base + p.isone;
+  u32 *scal = (u32*)(base + p.scal), *cellc = (u32*)(base + p.cellc), *agg = (u32*)(base + p.agg);
+  // 1. the offsets every stage walks, the weights, the gather
+  HIPCHK(hipMemsetAsync(badidx, 0, nseg, st));
+  KLAUNCH(k_kzgv_offsets, dim3(p.scan_grid), dim3(KZGV_BLOCK), 0, st, (const u32*)d_offsets, (u32)nseg, (u32)m, log_l, eff, mis, (unsigned long long*)(base + p.off64),
+          (u32*)(base + p.msm_off), (u32*)(base + p.base_first), c->status_word);
+  if (m)
+    KLAUNCH(k_kzgv_weights, dim3(p.weights_grid), dim3(KZGV_BLOCK), 0, st, (const u32*)eff, (u32)nseg, (u32)m, (const u32*)d_row, (const u32*)d_col, (u32)ncommit, (const u32*)d_r,
+            (const u32*)h->roots, (const uint2*)d_commit_xy, (const uint8_t*)d_commit_inf, (const uint2*)d_proof_xy, (const uint8_t*)d_proof_inf, log_n, log_l, order, scal,
+            (uint2*)(base + p.pxy), base + p.pinf, badidx, c->status_word);
+  LAUNCHCHK();
+  // 2. the 3 m products in ONE call; 3. their sums per batch and third (the products go through the normalisation the segment sums read)
+  {
+    ScalarFormScope mont(c, SCALAR_MONT);                        // the weights are Montgomery limbs whatever the context's setting
+    if (int rc = mul_batch_device<FpPolicy>(c, base + p.pxy, base + p.pinf, scal, p.products, base + p.prod)) return rc;
+  }
+  if (int rc = batch_normalize_device<FpPolicy>(c, base + p.prod, p.products, base + p.pxy, base + p.pinf)) return rc;
+  if (int rc = sum_segments_device<FpPolicy>(c, base + p.pxy, base + p.pinf, p.products, nullptr, base + p.off64, p.sums, p.products, base + p.sum)) return rc;
+  // 4. the cells in natural coset order, inverse-transformed; 5. the fold
+  if (m) {
+    KLAUNCH(k_kzg_scalar_copy, dim3(p.copy_grid), dim3(KZG_BLOCK), 0, st, (const uint4*)d_cells, (uint4*)cellc, m, log_l, log_l, order == KZGV_ORDER_BITREV ? 1 : 0);
+    LAUNCHCHK();
+    if (int rc = blsgpu_fr_ntt_many_device(c, cellc, log_l, m, 1, nullptr)) return rc;
+    KLAUNCH(k_kzgv_fold_chunks, dim3(p.fold_grid), dim3(KZGV_BLOCK), 0, st, (const u32*)eff, (u32)nseg, (u32)m, (const u32*)d_col, (const u32*)scal, (const u32*)cellc,
+            (const u32*)h->roots, log_n, log_l, order, p.chunk, (u32)p.nchunks, agg, (u32*)(base + p.part));
+  }
+  KLAUNCH(k_kzgv_fold_combine, dim3(p.combine_grid), dim3(KZGV_BLOCK), 0, st, (const u32*)eff, (u32)nseg, log_l, p.chunk, (const u32*)(base + p.part), agg);
+  LAUNCHCHK();
+  // 6. sum_u agg[s][u] S[u]: one segment per batch over the handle's bases
+  {
+    ScalarFormScope mont(c, SCALAR_MONT);
+    if (int rc = msm_segments_device<FpPolicy>(c, h->s, base + p.base_first, base + p.msm_off, agg, nseg, nseg << log_l, base + p.msm)) return rc;
+  }
+  // 7. (A_s, B_s) and the pairing terms; 8.-10. one two-term product per batch against {q, -G2}
+  KLAUNCH(k_kzgv_finish, dim3(p.finish_grid), dim3(KZGV_BLOCK), 0, st, (const u32*)(base + p.sum), (const u32*)(base + p.msm), (const uint8_t*)mis, (const uint8_t*)badidx, (u32)nseg,
+          (u32*)(base + p.ab), (u32*)d_out_ab, (u32*)(base + p.qidx), (unsigned long long*)(base + p.poff), badf);
+  LAUNCHCHK();
+  if (int rc = batch_normalize_device<FpPolicy>(c, base + p.ab, p.terms, base + p.abxy, base + p.abinf)) return rc;
+  if (int rc = blsgpu_multi_miller_loop_prepared_many_device(c, base + p.abxy, base + p.abinf, nullptr, nullptr, base + p.qidx, h->table, base + p.poff, nseg, p.terms, 2, 1, base + p.gt))
+    return rc;
+  if (int rc = blsgpu_gt_is_identity_device(c, base + p.gt, nseg, isone)) return rc;
+  KLAUNCH(k_kzgv_verdict, dim3(p.finish_grid), dim3(KZGV_BLOCK), 0, st, (const uint8_t*)isone, (const uint8_t*)badf, (u32)nseg, (uint8_t*)d_verdict);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_kzg_verify_cells_device(blsgpu_ctx* c, const blsgpu_kzg_cell_verifier* h, const void* commit_xy, const void* commit_inf, size_t ncommit, const void* row,
+                                              const void* col, const void* cells, const void* proof_xy, const void* proof_inf, const void* offsets, size_t nseg, size_t m, const void* r,
+                                              int order, void* verdict, void* out_ab) { CTX_CLAIM(c);
+  return kzg_verify_device(c, h, commit_xy, commit_inf, ncommit, row, col, cells, proof_xy, proof_inf, offsets, nseg, m, r, order, verdict, out_ab); }
+extern "C" int blsgpu_kzg_verify_cells(blsgpu_ctx* c, const blsgpu_kzg_cell_verifier* hd, const uint64_t* commit_xy, const uint8_t* commit_inf, size_t ncommit, const uint32_t* row,
+                                       const uint32_t* col, const uint64_t* cells, const uint64_t* proof_xy, const uint8_t* proof_inf, const uint32_t* offsets, size_t nseg,
+                                       const uint64_t* r, int order, uint8_t* verdict, uint64_t* out_ab) { CTX_CLAIM(c);
+  if (!c) return bad("kzg_verify_cells: ctx is NULL");
+  if (nseg > ((size_t)1 << KZGV_MAX_LOG_SEGS)) return bad("kzg_verify_cells: nseg must not exceed 2^24");
+  if (nseg && !offsets) return bad("kzg_verify_cells: NULL offsets, challenges or verdicts with batches to check");
+  const size_t m = nseg ? offsets[nseg] : 0;
+  const KzgvArgs a = kzgv_args(hd, commit_xy, commit_inf, ncommit, row, col, cells, proof_xy, proof_inf, offsets, nseg, m, r, order, verdict, out_ab, false);
+  if (const char* why = kzgv_check(a)) return bad(why);
+  if (const char* why = kzgv_check_host(offsets, nseg, m, row, col, ncommit, hd->log_n, hd->log_l)) return bad(why);
+  if (!nseg) return BLSGPU_OK;
+  HostCall h(c);
+  h.report_status();
+  // nine inputs through the staging buffers: the u32 arrays share one, the flag arrays another (each piece at a 256-byte boundary)
+  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+  void* dcells = h.in(c->io_a, cells, (m << hd->log_l) * 32);
+  void* dproof = h.in(c->io_b, proof_xy, m * 96);
+  void* dcommit = h.in(c->io_e, commit_xy, ncommit * 96);
+  const size_t o_row = up(nseg * 32), o_col = o_row + up(m * 4), o_off = o_col + up(m * 4), words = o_off + (nseg + 1) * 4;
+  const size_t o_cinf = up(m), flags = o_cinf + ncommit;
+  uint8_t *wf = nullptr, *ff = nullptr;
+  if (h.reserve(c->io_f, words) && h.reserve(c->flags_a, flags)) {
+    wf = c->io_f.as<uint8_t>(); ff = c->flags_a.as<uint8_t>();
+    const struct { void* dst; const void* src; size_t bytes; } piece[6] = {{wf, r, nseg * 32}, {wf + o_row, row, m * 4}, {wf + o_col, col, m * 4}, {wf + o_off, offsets, (nseg + 1) * 4},
+                                                                          {ff, proof_inf, m}, {ff + o_cinf, commit_inf, ncommit}};
+    for (const auto& q : piece) if (!h.rc && q.bytes) h.rc = staged_upload(c, q.dst, q.src, q.bytes);
+  }
+  void* v = h.out(c->flags_b, verdict, nseg);
+  void* ab = out_ab ? h.out(c->io_out, out_ab, nseg * 288) : nullptr;
+  if (h.rc) return h.rc;
+  return h.finish(kzg_verify_device(c, hd, dcommit, ff + o_cinf, ncommit, wf + o_row, wf + o_col, dcells, dproof, ff, wf + o_off, nseg, m, wf, order, v, ab));
 }
 
 // ---------------------------------------------------------------------------------------------------

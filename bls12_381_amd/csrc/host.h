@@ -3,8 +3,9 @@
 //
 //   api_ctx.hip      contexts, streams, status, diagnostics, staged uploads, field / point self-test hooks
 //   api_msm.hip      resident bases, MSM, batched scalar multiplication, sums, batch_normalize,       (msm.hip.h, mulbatch.hip.h,
-//                    group transforms, segmented point sums, Lagrange combines, amortised KZG openings         gntt.hip.h, gsum.hip.h,
-//                                                                                                       lagrange_combine.hip.h, kzg.hip.h)
+//                    group transforms, segmented point sums, Lagrange combines, amortised KZG openings,        gntt.hip.h, gsum.hip.h,
+//                    batched KZG cell-proof verification                                                 lagrange_combine.hip.h, kzg.hip.h,
+//                                                                                                       kzg_verify.hip.h)
 //   api_pairing.hip  pairings, Miller loops, G2Prepared, final exponentiation, Gt, Fp6 / Fp12 hooks   (pairing / quad / prep / wide)
 //   api_aux.hip      hash-to-curve, expanders and hash-to-scalar, point codecs, bulk BLS verification   (h2c / expand_kernels / codec / generators)
 //   api_fr.hip       Fr vectors, transforms, scans, Lagrange, fraction scans, openings, SpMV, Poseidon,  (fr*.hip.h)
@@ -41,6 +42,7 @@
 #include "gsum_plan.h"
 #include "fr_lagrange_plan.h"
 #include "kzg_plan.h"
+#include "kzg_verify_plan.h"
 
 using namespace bls;
 
@@ -249,6 +251,7 @@ struct blsgpu_ctx {
   DevBuf kzg_coeff, kzg_rows, kzg_seg;  // blsgpu_kzg_multiproof_proofs_device / blsgpu_kzg_cells_device: the coefficients of an evaluation-form input, the rows c^_t (cells: the
                                         // zero-extended rows), the segment-order copy (kzg_plan.h)
   DevBuf kzg_pts, kzg_off;              // ... the points between the MSM and the caller's array, the offsets and base_first of the Toeplitz MSM
+  DevBuf kzgv;                          // blsgpu_kzg_verify_cells_device: every intermediate of the chain, laid out by kzg_verify_plan.h
   DevBuf frp_nodes;                     // blsgpu_fr_poseidon_merkle_device with nodes == NULL: the levels below the roots (fr_poseidon_plan.h)
 };
 
@@ -327,6 +330,16 @@ struct blsgpu_fr_lookup {
 struct blsgpu_kzg_multiproof {
   int device = 0; int log_n = 0, log_l = 0;
   blsgpu_bases* xhat = nullptr;
+};
+
+// a verifier of KZG cell proofs (api_msm.hip: blsgpu_kzg_cell_verifier_create; kzg_verify.hip.h): S[0..l) as a resident base set of its
+// own with its endomorphism images, the two-entry `G2Prepared` table {q, -G2}, and the log_n + 1 scalars winv^(2^b) every power of w
+// is made of
+struct blsgpu_kzg_cell_verifier {
+  int device = 0; int log_n = 0, log_l = 0;
+  blsgpu_bases* s = nullptr;
+  blsgpu_g2_prepared* table = nullptr;
+  u32* roots = nullptr;
 };
 
 // a sumcheck in progress (api_fr.hip: blsgpu_fr_sumcheck_begin*; fr_mle.hip.h): its own copy of the tables, which the rounds consume,

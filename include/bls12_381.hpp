@@ -849,6 +849,63 @@ inline std::vector<FrLimbs> kzg_cells(const std::vector<FrLimbs>& polys, int log
   return out;
 }
 
+// Batched verification of KZG cell proofs (include/bls12_381_hip.h: blsgpu_kzg_cell_verifier_*, blsgpu_kzg_verify_cells): every batch of
+// (commitment, cell index, cell, proof) tuples decided by one two-term pairing product.  The constructor uploads the first l = 2^log_l
+// points of `srs`, builds the handle (S[0..l), the `G2Prepared` table {q, -G2}, the powers of w) and lets the upload go; q is meant as
+// [tau^l] G2 and the caller vouches that it is in the subgroup.  verify() takes m cells of l scalars laid end to end, numbered by `order` as
+// kzg_cells writes them, with row[k] / col[k] naming the commitment and the cell number; offsets is the CSR array of the batches and r
+// holds one challenge per batch -- the caller's, unpredictable from the inputs.  Returns the verdict bytes; `out_ab`, if given, receives
+// (A_s, B_s) per batch.
+class KzgCellVerifier {
+ public:
+  KzgCellVerifier(const std::vector<G1Affine>& srs, int log_n, int log_l, const G2Affine& q) {
+    if (log_l < 0 || log_l > 12 || srs.size() < ((size_t)1 << log_l)) throw std::invalid_argument("KzgCellVerifier: the SRS holds fewer than 2^log_l points");
+    const size_t l = (size_t)1 << log_l;
+    std::vector<uint64_t> xy(l * G1Affine::W);
+    std::vector<uint8_t> inf(l);
+    for (size_t i = 0; i < l; i++) { std::memcpy(xy.data() + i * G1Affine::W, srs[i].xy.data(), G1Affine::W * 8); inf[i] = srs[i].infinity ? 1 : 0; }
+    blsgpu_bases* b = nullptr;
+    check(blsgpu_g1_bases_upload(Context::instance().handle(), xy.data(), inf.data(), l, &b), "g1_bases_upload");
+    const uint8_t q_inf = q.infinity ? 1 : 0;
+    const int rc = blsgpu_kzg_cell_verifier_create(Context::instance().handle(), b, log_n, log_l, q.xy.data(), &q_inf, &h_);
+    blsgpu_bases_free(b);
+    check(rc, "kzg_cell_verifier_create");
+  }
+  ~KzgCellVerifier() { blsgpu_kzg_cell_verifier_free(h_); }
+  KzgCellVerifier(const KzgCellVerifier&) = delete;
+  KzgCellVerifier& operator=(const KzgCellVerifier&) = delete;
+  KzgCellVerifier(KzgCellVerifier&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  int log_n() const { return blsgpu_kzg_cell_verifier_log_n(h_); }
+  int log_l() const { return blsgpu_kzg_cell_verifier_log_l(h_); }
+  size_t cells() const { return blsgpu_kzg_cell_verifier_cells(h_); }
+  const blsgpu_kzg_cell_verifier* handle() const { return h_; }
+  std::vector<uint8_t> verify(const std::vector<G1Affine>& commitments, const std::vector<uint32_t>& row, const std::vector<uint32_t>& col, const std::vector<FrLimbs>& cell_values,
+                              const std::vector<G1Affine>& proofs, const std::vector<uint32_t>& offsets, const std::vector<FrLimbs>& r, int order = BLSGPU_FR_ORDER_NATURAL,
+                              std::vector<G1Projective>* out_ab = nullptr) const {
+    const size_t nseg = offsets.empty() ? 0 : offsets.size() - 1, m = nseg ? offsets.back() : 0, l = (size_t)1 << log_l();
+    if (row.size() != m || col.size() != m || proofs.size() != m || cell_values.size() != m * l || r.size() != nseg)
+      throw std::invalid_argument("KzgCellVerifier::verify: row, col, proofs and cells must hold offsets.back() cells, r one challenge per batch");
+    std::vector<uint8_t> verdict(nseg);
+    if (!nseg) return verdict;
+    auto wire = [](const std::vector<G1Affine>& p, std::vector<uint64_t>& xy, std::vector<uint8_t>& inf) {
+      xy.resize(p.size() * G1Affine::W + 1); inf.resize(p.size() + 1);
+      for (size_t i = 0; i < p.size(); i++) { std::memcpy(xy.data() + i * G1Affine::W, p[i].xy.data(), G1Affine::W * 8); inf[i] = p[i].infinity ? 1 : 0; }
+    };
+    std::vector<uint64_t> cxy, pxy, ab(out_ab ? nseg * 2 * G1Projective::W : 0);
+    std::vector<uint8_t> cinf, pinf;
+    wire(commitments, cxy, cinf); wire(proofs, pxy, pinf);
+    check(blsgpu_kzg_verify_cells(Context::instance().handle(), h_, cxy.data(), cinf.data(), commitments.size(), row.data(), col.data(), m ? cell_values[0].data() : nullptr, pxy.data(),
+                                  pinf.data(), offsets.data(), nseg, r[0].data(), order, verdict.data(), out_ab ? ab.data() : nullptr), "kzg_verify_cells");
+    if (out_ab) {
+      out_ab->assign(nseg * 2, G1Projective());
+      for (size_t i = 0; i < out_ab->size(); i++) std::memcpy((*out_ab)[i].xyz.data(), ab.data() + i * G1Projective::W, G1Projective::W * 8);
+    }
+    return verdict;
+  }
+ private:
+  blsgpu_kzg_cell_verifier* h_ = nullptr;
+};
+
 // The same operations sharded over several GPUs of one node from this process (blsgpu_group: one context + one host thread per
 // listed device; partial results folded with `Sum` / `MillerLoopResult + MillerLoopResult`, src/g1.rs:161-171, src/pairings.rs:179-186)
 class Group {

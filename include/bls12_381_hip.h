@@ -979,7 +979,7 @@ int blsgpu_g2_ntt_many_device(blsgpu_ctx* ctx, void* d_xyz, int log_n, size_t k,
  * BLSGPU_ERR_ARG with nothing staged or launched: a NULL pointer with work to do; a G2 or too-short SRS (blsgpu_bases_len < n); an SRS
  * whose subgroup state is 0 (a point outside the subgroup); log_n, log_l, count, form or order out of range, 64-bit overflow of the
  * products included; a misaligned device pointer; an overlap.
- * Not in scope: verification of cells, recovery from half the cells, G2, a Lagrange-form SRS, window-table precomputation for the
+ * Not in scope: verification of cells (a call of its own: blsgpu_kzg_verify_cells below), recovery from half the cells, G2, a Lagrange-form SRS, window-table precomputation for the
  * Toeplitz MSM. */
 typedef struct blsgpu_kzg_multiproof blsgpu_kzg_multiproof;
 #define BLSGPU_KZG_FORM_COEFFS 0   /* n coefficients, X^0 first */
@@ -993,6 +993,68 @@ int blsgpu_kzg_multiproof_proofs(blsgpu_ctx* ctx, const blsgpu_kzg_multiproof* h
 int blsgpu_kzg_multiproof_proofs_device(blsgpu_ctx* ctx, const blsgpu_kzg_multiproof* h, const void* d_polys, size_t count, int form, int order, void* d_out_xyz);
 int blsgpu_kzg_cells(blsgpu_ctx* ctx, const uint64_t* polys, int log_n, int log_l, size_t count, int form, int order, uint64_t* cells);
 int blsgpu_kzg_cells_device(blsgpu_ctx* ctx, const void* d_polys, int log_n, int log_l, size_t count, int form, int order, void* d_cells);
+/* Batched verification of KZG cell proofs: many (commitment, cell index, cell, proof) tuples decided by ONE two-term pairing product per
+ * batch -- the consumer's half of data-availability sampling, blsgpu_kzg_multiproof_proofs / blsgpu_kzg_cells being the producer's.
+ * Notation is that of the comment above: n = 2^log_n, l = 2^log_l, c = n / l, w the root blsgpu_fr_ntt uses for log_n + 1; cell j < 2c is
+ * the coset h_j <w^(2c)>, numbered by `order` (BLSGPU_FR_ORDER_*) exactly as blsgpu_kzg_cells writes it; S[u] are the first l points of a
+ * resident G1 base set, meant as [tau^u] G1.
+ * blsgpu_kzg_cell_verifier_create(ctx, srs_g1, log_n, log_l, q_xy, q_inf, &out): q is ONE affine G2 wire point (24 u64, a HOST pointer;
+ * q_inf NULL or one infinity byte), meant as [tau^l] G2; the caller vouches that it is in the subgroup, as for the key sets of
+ * blsgpu_bls_fast_aggregate_verify_batch.  A setup call that synchronises, like blsgpu_kzg_multiproof_create: the handle keeps no
+ * reference to srs_g1; it holds S[0..l) as a resident base set of its own with its endomorphism images, a two-entry `G2Prepared` table
+ * {q, -G2 generator} and log_n + 1 powers of w.  _log_n / _log_l / _cells (= 2c) and _free follow the rules of the multiproof handle.
+ * Refused (BLSGPU_ERR_ARG): a NULL argument; a G2 SRS or one shorter than l; an SRS with subgroup state 0; another device; log_n outside
+ * [0, 23]; log_l outside [0, min(log_n, 12)].
+ * blsgpu_kzg_verify_cells takes host pointers; blsgpu_kzg_verify_cells_device takes device pointers, is asynchronous on the context's
+ * stream and never synchronises.
+ *   commit_xy, commit_inf, ncommit   decoded affine G1 wire points + infinity bytes, as *_from_bytes_batch_device writes them
+ *   row, col      m u32 each: cell k belongs to commitment row[k] and is cell number col[k] < 2c
+ *   cells         m x l scalars, canonical Montgomery limbs, entry t of cell k as blsgpu_kzg_cells numbers it in `order`
+ *   proof_xy, proof_inf              m decoded affine G1 wire points
+ *   offsets, nseg [, m]              nseg + 1 u32, the CSR array of *_msm_segments: batch s owns the cells offsets[s] .. offsets[s + 1];
+ *                 m = offsets[nseg] is passed by value in the device form
+ *   r             nseg scalars (Montgomery limbs; a DEVICE pointer in the device form): the challenge of batch s
+ *   verdict       nseg bytes;    out_ab   NULL, or nseg x 2 projective G1 wire points (18 u64 each): A_s, B_s
+ * For batch s and its cells k, with rho_k = r_s^(k - offsets[s]) (rho = 1 for the first cell whatever r_s is), a_k = h_col[k]^l and I_k the
+ * polynomial of degree < l that takes the values cells[k][*] on the points of cell col[k], the results are DEFINED by
+ *   A_s = sum_k rho_k proof_k
+ *   B_s = sum_k rho_k commit[row_k] + sum_k rho_k a_k proof_k - sum_{u<l} (sum_k rho_k I_k[u]) S[u]
+ *   verdict[s] = 1 if multi_miller_loop([(A_s, q), (B_s, -G2)]).final_exponentiation() == Gt::identity()  (e(A_s, q) == e(B_s, G2)), else 0
+ * and by nothing else: for honest inputs over a powers-of-tau SRS every batch holds, and the definition is meaningful for ANY points.
+ * An empty batch has verdict 1; identities among commitments and proofs are ordinary terms (a polynomial of degree < l has identity
+ * proofs); a pairing term with an identity on either side is skipped, as the reference's multi_miller_loop skips it; c = 1 is legal.
+ * out_ab makes the call usable inside a larger pairing product; its projective representative is unspecified (compare after
+ * batch_normalize).  (I_k[u] = h^(-u) INTT_l(v)[u], v the cell in natural coset order, INTT_l the inverse blsgpu_fr_ntt of size l.)
+ * THE CHALLENGE IS THE CALLER'S, for example from blsgpu_hash_to_scalar_device over a transcript of the batch: soundness needs r_s to be
+ * unpredictable from the inputs -- with a known r a wrong cell can be offset by another.  Batches of ONE cell give a per-cell verdict
+ * after a failed batch, at the cost of one pairing product per cell.
+ * Limits: m <= 2^24, nseg <= 2^24, m * l <= 2^27, nseg * l <= 2^27 (the total of msm_segments).  Device scalar arrays are 16-byte
+ * aligned, point arrays 8-byte, u32 arrays 4-byte.  BLSGPU_ERR_ARG with nothing staged or launched: a NULL required pointer with work to
+ * do; a range or product overflow, 64-bit wrap included; a bad `order`; a misaligned device pointer; an output that overlaps an input or
+ * the other output; a handle of another device.  The host form also refuses offsets that do not start at 0 or that decrease,
+ * row[k] >= ncommit and col[k] >= 2c.  The device form cannot see offsets or indices: a bad index or a broken batch (an offset that is
+ * not the running maximum of the offsets before it, or beyond m; offsets[0] != 0; offsets[nseg] != m) is never used as an address, its
+ * batch gets verdict 0 and an identity pair in out_ab, the context's sticky flag is set (the next blsgpu_synchronize returns
+ * BLSGPU_ERR_ARG), and every other batch is right.  nseg == 0 is a no-op.  The caller's arrays are never written.  Scalars are read as
+ * Montgomery limbs whatever blsgpu_set_scalar_form says.  The products are exact for every curve point; the endomorphism split of the
+ * 3 m scalar multiplications applies only under blsgpu_set_assume_subgroup, as for the Lagrange combines.  The chain -- weights and
+ * gather, ONE mul_batch, segment sums, inverse fr_ntt_many of the cells, the fold, msm_segments over S[0..l), batch_normalize,
+ * multi_miller_loop_prepared_many with final exponentiation, gt_is_identity -- runs on the context's stream with scratch of its own (about
+ * 820 + 32 l bytes per cell), not shared with pipelined *_msm_device calls in flight.
+ * Not in scope: byte-level inputs, big-endian scalars, Fiat-Shamir derivation of r, recovery from half the cells, a Pippenger MSM over
+ * the fresh proofs (it would need *_bases_from_device and its synchronisation), multi-GPU. */
+typedef struct blsgpu_kzg_cell_verifier blsgpu_kzg_cell_verifier;
+int blsgpu_kzg_cell_verifier_create(blsgpu_ctx* ctx, const blsgpu_bases* srs_g1, int log_n, int log_l, const uint64_t* q_xy, const uint8_t* q_inf, blsgpu_kzg_cell_verifier** out);
+int blsgpu_kzg_cell_verifier_log_n(const blsgpu_kzg_cell_verifier* h);
+int blsgpu_kzg_cell_verifier_log_l(const blsgpu_kzg_cell_verifier* h);
+size_t blsgpu_kzg_cell_verifier_cells(const blsgpu_kzg_cell_verifier* h);
+void blsgpu_kzg_cell_verifier_free(blsgpu_kzg_cell_verifier* h);
+int blsgpu_kzg_verify_cells(blsgpu_ctx* ctx, const blsgpu_kzg_cell_verifier* h, const uint64_t* commit_xy, const uint8_t* commit_inf, size_t ncommit, const uint32_t* row,
+                            const uint32_t* col, const uint64_t* cells, const uint64_t* proof_xy, const uint8_t* proof_inf, const uint32_t* offsets, size_t nseg, const uint64_t* r,
+                            int order, uint8_t* verdict, uint64_t* out_ab);
+int blsgpu_kzg_verify_cells_device(blsgpu_ctx* ctx, const blsgpu_kzg_cell_verifier* h, const void* d_commit_xy, const void* d_commit_inf, size_t ncommit, const void* d_row,
+                                   const void* d_col, const void* d_cells, const void* d_proof_xy, const void* d_proof_inf, const void* d_offsets, size_t nseg, size_t m,
+                                   const void* d_r, int order, void* d_verdict, void* d_out_ab);
 
 /* ---- hash-to-curve (the step in front of multi_miller_loop in bulk signature checks) ---- */
 /* `<G as HashToCurve<ExpandMsgXmd<Sha256>>>::hash_to_curve(msg, dst)` / `encode_to_curve` (encode_only != 0) for n
