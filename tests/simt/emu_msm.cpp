@@ -1,8 +1,9 @@
 // tests/simt/emu_msm.cpp -- the MSM kernels of bls12_381_amd/csrc compiled for the HOST (test infrastructure only): the segmented MSM
-// (msm_seg.hip.h), the scalar decompositions, the endomorphism images, the subgroup check and the G1 bucket accumulation of msm.hip.h.
+// (msm_seg.hip.h), the scalar decompositions, the endomorphism images, the subgroup check, the bucket accumulations of msm.hip.h and the
+// point kernels behind them (cut-bucket fold, level forms, tree sums, shift-add, window combine), one stage per entry point.
 // The entry points launch the __global__ functions themselves with the grid and block shapes of api_msm.hip (restated below, each with
 // the lines it restates), every lane a host thread where lanes cooperate (tests/simt/hip/hip_runtime.h), so that the CPU suite can
-// compare the very code the GPU runs with the oracle (tests/test_simt_msm.py).
+// compare the very code the GPU runs with the oracle (tests/test_simt_msm.py, tests/test_simt_msm_points.py).
 //
 // The lane pool, the launchers, the trapping checks and emu_guarded() are those of tests/simt/emu_harness.h; the tests call this
 // library from a child process (tests/simt_msm_child.py).
@@ -78,5 +79,68 @@ void emu_msm_accumulate_g1(const u32* bases, const u32* bases2, u32 nsplit, cons
 void emu_proj_export(int group, const u32* rec, u32* xyz, size_t n) {
   if (group == 1) launch_loop(nblk(n, 256), 256, [=] { k_proj_export<FpPolicy>(rec, xyz, n); });
   else launch_loop(nblk(n, 256), 256, [=] { k_proj_export<Fp2Policy>(rec, xyz, n); });
+}
+
+// ---- the point kernels behind the sort of the large MSM, one stage per entry point (tests/test_simt_msm_points.py) ----------------
+// records are PROJ records (Store<F>::PROJ_WORDS words each) in buffers of exactly the size the test states; group 1 = G1, 2 = G2
+void emu_proj_import(int group, const u32* xyz, u32* rec, size_t n) {
+  if (group == 1) launch_loop(nblk(n, 256), 256, [=] { k_proj_import<FpPolicy>(xyz, rec, n); });
+  else launch_loop(nblk(n, 256), 256, [=] { k_proj_import<Fp2Policy>(xyz, rec, n); });
+}
+// api_msm.hip :428 (G2): one lane pair per item, the grid covers 2 * max_items lanes
+void emu_msm_accumulate_g2(const u32* bases, const u32* sorted, const u32* items, const u32* ctrl, u32* records, u32 max_items) {
+  launch_threads(nblk(2 * (size_t)max_items, BLS_G2ACC_BLOCK), BLS_G2ACC_BLOCK,
+                 [=] { k_msm_accumulate_g2pair(bases, sorted, reinterpret_cast<const ItemDesc*>(items), ctrl, records); });
+}
+// api_msm.hip :437-438: one lane per bucket of the call, then HEAVY_BIG_BLOCKS blocks for the block-folded buckets
+void emu_msm_heavy(int group, const u32* heavy, const u32* ctrl, u32* records, u32 gnb) {
+  const u32 small_blocks = nblk(gnb, 256);
+  const uint4* h = reinterpret_cast<const uint4*>(heavy);
+  if (group == 1) launch_threads(small_blocks + HEAVY_BIG_BLOCKS, 256, [=] { k_msm_heavy<FpPolicy>(h, ctrl, records, gnb, small_blocks); });
+  else launch_threads(small_blocks + HEAVY_BIG_BLOCKS, 256, [=] { k_msm_heavy<Fp2Policy>(h, ctrl, records, gnb, small_blocks); });
+}
+// api_msm.hip :486-494, one reduction level in the form asked for: 0 = team2 (:487), 1 = team (:490), 2 = the pair form of the group
+// (:492 g2pair, :494 pair).  The product picks the form by the lane count; here every form runs on the same inputs.
+void emu_wsum_level(int group, int form, const u32* E, u32* Rout, u32* Tout, int nseg, int n, int M, int off) {
+  const size_t chains = (size_t)nseg * (n / M);
+  if (form == 0) {
+    if (group == 1) launch_threads(nblk(chains * 2 * TEAM, 256), 256, [=] { k_wsum_level_team2<FpPolicy>(E, Rout, Tout, nseg, n, M, off); });
+    else launch_threads(nblk(chains * 2 * TEAM, 256), 256, [=] { k_wsum_level_team2<Fp2Policy>(E, Rout, Tout, nseg, n, M, off); });
+  } else if (form == 1) {
+    if (group == 1) launch_threads(nblk(chains * TEAM, 256), 256, [=] { k_wsum_level_team<FpPolicy>(E, Rout, Tout, nseg, n, M, off); });
+    else launch_threads(nblk(chains * TEAM, 256), 256, [=] { k_wsum_level_team<Fp2Policy>(E, Rout, Tout, nseg, n, M, off); });
+  } else {
+    if (group == 1) launch_threads(nblk(chains * 2, BLS_WSUM_BLOCK), BLS_WSUM_BLOCK, [=] { k_wsum_level_pair(E, Rout, Tout, nseg, n, M, off); });
+    else launch_threads(nblk(chains * 2, 256), 256, [=] { k_wsum_level_g2pair(E, Rout, Tout, nseg, n, M, off); });
+  }
+}
+// api_msm.hip :469 / :509: the one-lane tree pass
+void emu_tree_sum(int group, const u32* E, u32* out, int nseg, int n, int M) {
+  const int TG = (n + M - 1) / M;
+  if (group == 1) launch_loop(nblk((size_t)nseg * TG, 256), 256, [=] { k_tree_sum<FpPolicy>(E, out, nseg, n, M); });
+  else launch_loop(nblk((size_t)nseg * TG, 256), 256, [=] { k_tree_sum<Fp2Policy>(E, out, nseg, n, M); });
+}
+// api_msm.hip tree_step (:459-473): one pass of njobs trees in one launch; job j sums n[j] records per window in groups of M[j].
+// tree_step itself always takes M = min(8, n); the kernel's contract is wider (any M <= maxM), and the tests use both.
+void emu_tree_sum_multi(int group, int njobs, const u32* const* in, u32* const* out, const int* n, const int* M, int nseg) {
+  TreeJobs J; J.njobs = 0; J.nseg = nseg; J.first_team[0] = 0; J.maxM = 0;
+  for (int t = 0; t < njobs; t++) {
+    int TM = M[t], TG = (n[t] + TM - 1) / TM;
+    int j = J.njobs++;
+    J.in[j] = in[t]; J.out[j] = out[t]; J.n[j] = n[t]; J.M[j] = TM; J.G[j] = TG; J.first_team[j + 1] = J.first_team[j] + nseg * TG;
+    if (TM > J.maxM) J.maxM = TM;
+  }
+  if (group == 1) launch_threads(nblk((size_t)J.first_team[J.njobs] * TEAM, 256), 256, [=] { k_tree_sum_team_multi<FpPolicy>(J); });
+  else launch_threads(nblk((size_t)J.first_team[J.njobs] * TEAM, 256), 256, [=] { k_tree_sum_team_multi<Fp2Policy>(J); });
+}
+// api_msm.hip :536
+void emu_shift_add(int group, const u32* x, const u32* y, u32* out, int nseg, int k) {
+  if (group == 1) launch_threads(nblk((size_t)nseg * TEAM, 256), 256, [=] { k_shift_add_team<FpPolicy>(x, y, out, nseg, k); });
+  else launch_threads(nblk((size_t)nseg * TEAM, 256), 256, [=] { k_shift_add_team<Fp2Policy>(x, y, out, nseg, k); });
+}
+// api_msm.hip :544
+void emu_msm_combine(int group, const u32* wsums, u32* out, int nwin, int c) {
+  if (group == 1) launch_threads(1, TEAM, [=] { k_msm_combine_team<FpPolicy>(wsums, out, nwin, c); });
+  else launch_threads(1, TEAM, [=] { k_msm_combine_team<Fp2Policy>(wsums, out, nwin, c); });
 }
 }

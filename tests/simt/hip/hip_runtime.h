@@ -122,7 +122,14 @@ struct uint2 { unsigned x, y; };
 static inline uint4 make_uint4(unsigned x, unsigned y, unsigned z, unsigned w) { return uint4{x, y, z, w}; }
 static inline uint2 make_uint2(unsigned x, unsigned y) { return uint2{x, y}; }
 #define __builtin_amdgcn_update_dpp emu_update_dpp
+// EMU_SYNCTHREADS_HOOK: a library whose kernels meet ONLY at the workgroup barrier may run the lanes of a workgroup as fibers of one
+// thread and supplies the barrier itself (tests/simt/emu_msm_front.cpp)
+#ifdef EMU_SYNCTHREADS_HOOK
+void emu_syncthreads();
+static inline void __syncthreads() { emu_syncthreads(); }
+#else
 static inline void __syncthreads() { g_emu.wg.barrier(blockDim.x); }
+#endif
 #define __builtin_amdgcn_s_setprio(x) ((void)0)
 #define __builtin_amdgcn_s_getreg(x) 0u
 #define __builtin_amdgcn_readfirstlane(x) (x)

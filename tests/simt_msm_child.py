@@ -11,6 +11,15 @@ A job is a dict with "op" and "label"; the result list has one dict per job:
               [nbases]                                                            -> out (k, 18|36 u64), status, wsums (wire, last batch)
   decompose   group, scalars (n, 8 u32), form                                     -> out (u32 words), status
   accumulate  bases, nsplit, sorted, items (m, 3 u32), ctrl (4 u32), max_items, ndest, [bases2_endo]    -> records (ndest, 18 u64 wire)
+The point kernels of the large MSM, one stage per job (tests/test_simt_msm_points.py); points travel as projective wire limbs
+((n, 18|36) u64) and live in PROJ-record buffers of exactly the stated number of records, each against a guard page:
+  accumulate_g2  bases, sorted, items, ctrl, max_items, ndest                       -> records
+  heavy       group, records, heavy (m, 4 u32), big (indices into heavy), ctrl, nb  -> records (in place)
+  level       group, form (0 team2, 1 team, 2 pair), E (nseg * n), nseg, n, M, off  -> R, T (nseg * n / M each)
+  tree        group, E, nseg, n, M                                                  -> out (nseg * ceil(n / M))
+  tree_multi  group, nseg, trees [(E, n, M)]                                        -> outs
+  shift_add   group, x, y (nseg each), k                                            -> out
+  combine     group, wsums (nwin), c                                                -> out (1)
 Test infrastructure only: the product never imports this file."""
 import ctypes
 
@@ -125,6 +134,96 @@ class _Child(simt_harness.Child):
         wire, pwire = self.out(ndest * 36)
         self.lib.emu_proj_export(1, self.guarded(rec), pwire, ctypes.c_size_t(ndest))
         return {"records": wire.copy().view(np.uint64).reshape(ndest, 18)}
+
+    # ---- the point kernels of the large MSM ---------------------------------------------------------------------------------------
+    def recs(self, group, wire):
+        """projective wire limbs -> a guarded buffer of exactly that many PROJ records (k_proj_import); (view, address, n)"""
+        wire = np.ascontiguousarray(wire, dtype=np.uint64).reshape(-1, 3 * WIRE[group])
+        n = wire.shape[0]
+        rec, prec = self.buf(n * PROJ_WORDS[group])
+        self.lib.emu_proj_import(group, self.guarded(wire), prec, ctypes.c_size_t(n))
+        return rec, prec, n
+
+    def empty(self, group, n):
+        return self.buf(n * PROJ_WORDS[group])
+
+    def wire(self, group, rec, n):
+        out, pout = self.out(n * 6 * WIRE[group])
+        self.lib.emu_proj_export(group, self.guarded(rec), pout, ctypes.c_size_t(n))
+        return out.copy().view(np.uint64).reshape(n, 3 * WIRE[group])
+
+    def accumulate_g2(self, j):
+        b = self.results[j["bases"]]
+        assert b["group"] == 2
+        items = np.ascontiguousarray(j["items"], dtype=np.uint32).reshape(-1, 3)
+        ndest = int(j["ndest"])
+        rec, prec = self.empty(2, ndest)
+        _, pbases = self.buf(len(b["rec"]), b["rec"])
+        _, psorted = self.buf(len(j["sorted"]), j["sorted"])
+        _, pitems = self.buf(items.size, items)
+        _, pctrl = self.buf(4, j["ctrl"])
+        self.lib.emu_msm_accumulate_g2(pbases, psorted, pitems, pctrl, prec, ctypes.c_uint32(int(j["max_items"])))
+        return {"records": self.wire(2, rec, ndest)}
+
+    def heavy(self, j):
+        g, nb = int(j["group"]), int(j["nb"])
+        rec, prec, n = self.recs(g, j["records"])
+        heavy, pheavy = self.buf(2 * nb * 4, fill=0xffffffff)
+        h = heavy.reshape(2 * nb, 4)
+        for i, e in enumerate(j["heavy"]):
+            h[i] = e
+        for i, e in enumerate(j["big"]):
+            h[nb + i, 0] = e
+        _, pctrl = self.buf(4, j["ctrl"])
+        self.lib.emu_msm_heavy(g, pheavy, pctrl, prec, ctypes.c_uint32(nb))
+        return {"records": self.wire(g, rec, n)}
+
+    def level(self, j):
+        g, nseg, n, M = int(j["group"]), int(j["nseg"]), int(j["n"]), int(j["M"])
+        _, pe, ne = self.recs(g, j["E"])
+        assert ne == nseg * n and n % M == 0
+        chains = nseg * (n // M)
+        r, pr = self.empty(g, chains)
+        t, pt = self.empty(g, chains)
+        self.lib.emu_wsum_level(g, int(j["form"]), pe, pr, pt, nseg, n, M, int(j["off"]))
+        return {"R": self.wire(g, r, chains), "T": self.wire(g, t, chains)}
+
+    def tree(self, j):
+        g, nseg, n, M = int(j["group"]), int(j["nseg"]), int(j["n"]), int(j["M"])
+        _, pe, ne = self.recs(g, j["E"])
+        assert ne == nseg * n
+        m = nseg * ((n + M - 1) // M)
+        o, po = self.empty(g, m)
+        self.lib.emu_tree_sum(g, pe, po, nseg, n, M)
+        return {"out": self.wire(g, o, m)}
+
+    def tree_multi(self, j):
+        g, nseg = int(j["group"]), int(j["nseg"])
+        k = len(j["trees"])
+        ins, outs, views, ns, ms = (ctypes.c_void_p * k)(), (ctypes.c_void_p * k)(), [], (ctypes.c_int * k)(), (ctypes.c_int * k)()
+        for i, (E, n, M) in enumerate(j["trees"]):
+            _, pe, ne = self.recs(g, E)
+            assert ne == nseg * n
+            m = nseg * ((n + M - 1) // M)
+            o, po = self.empty(g, m)
+            ins[i], outs[i], ns[i], ms[i] = pe.value, po.value, n, M
+            views.append((o, m))
+        self.lib.emu_tree_sum_multi(g, k, ins, outs, ns, ms, nseg)
+        return {"outs": [self.wire(g, o, m) for o, m in views]}
+
+    def shift_add(self, j):
+        g = int(j["group"])
+        rx, px, n = self.recs(g, j["x"])
+        _, py, _ = self.recs(g, j["y"])
+        self.lib.emu_shift_add(g, px, py, px, n, int(j["k"]))       # in place, as api_msm.hip :536 runs it (accbuf is x and out)
+        return {"out": self.wire(g, rx, n)}
+
+    def combine(self, j):
+        g = int(j["group"])
+        _, pw, n = self.recs(g, j["wsums"])
+        o, po = self.empty(g, 1)
+        self.lib.emu_msm_combine(g, pw, po, n, int(j["c"]))
+        return {"out": self.wire(g, o, 1)}
 
 
 if __name__ == "__main__":

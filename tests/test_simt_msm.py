@@ -10,8 +10,12 @@ The library is built with trapping bounds / shift checks and reads every input f
 and it runs in a child process under a time limit (tests/simt_msm_child.py): an LDS index out of range, a read past a buffer or a
 lane that waits for a partner for ever fails the test that caused it.
 
-NOT covered yet (the next step): the sort / item-list / tail kernels of the large MSM -- `k_sort_*`, `k_item_*`, `k_wsum_*`,
-`k_tree_sum*`, `k_msm_heavy` -- and `k_msm_accumulate_g2pair`; they are checked on the GPU only (tests/test_gpu_parity.py).
+The rest of the large MSM runs on the host stage by stage, each stage on inputs of its own and against the models of
+tests/msm_pipe_model.py: the integer front end -- `k_sort_*`, the fallback sort (`k_msm_digits`, `k_scan_*`, `k_msm_scatter`) and
+`k_item_*` -- in tests/test_simt_msm_front.py (tests/simt/emu_msm_front.cpp); the point kernels behind it -- `k_msm_accumulate_g2pair`,
+`k_msm_heavy`, the four `k_wsum_level_*` forms, `k_tree_sum*`, `k_shift_add_team`, `k_msm_combine_team` -- in
+tests/test_simt_msm_points.py (this library).  NOT covered on the host: the driver logic of api_msm.hip (`run_group`) and the DPP
+modifiers the emulation ignores; tests/test_msm_pipeline_gpu.py covers both on the GPU with every bucket of every window filled.
 
 That the tests bite was checked by seeding faults into the device headers one at a time: no carry in DigitIter::next
 (test_signed_recoding_carries, test_window_sums), sub2 flipped in glv_split / a sign flipped in gls_split
