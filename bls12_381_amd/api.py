@@ -1696,6 +1696,35 @@ class Context:
         asynchronous on the context's stream"""
         check(self.lib.blsgpu_kzg_cells_device(self.h, d_polys, int(log_n), int(log_l), int(count), int(form), int(order), d_cells), "kzg_cells_device")
 
+    def kzg_recover(self, col, offsets, cells, log_n, log_l, order=FR_ORDER_NATURAL, want_polys=True, want_cells=False):
+        """polynomials rebuilt from c or more of their 2c cells (include/bls12_381_hip.h): offsets: count + 1 u32, polynomial v owns the
+        received cells offsets[v] .. offsets[v + 1]; col: m u32 cell numbers in `order`; cells: (m, l, 4) u64 Montgomery limbs or Python
+        ints in [0, r) nested the same way, entries numbered as kzg_cells writes them.  Returns (polys, out_cells, ok): the (count, n, 4)
+        coefficients (None without want_polys), the (count, 2c, l, 4) cells of the recovered polynomials (None without want_cells) and
+        the count ok bytes; a polynomial with ok = 0 (inconsistent cells) has zero rows."""
+        n, l = 1 << log_n, 1 << log_l
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        count = max(off.shape[0] - 1, 0)
+        m = int(off[-1]) if count else 0
+        cl = np.ascontiguousarray(col, dtype=np.uint32).reshape(-1)
+        if cl.shape[0] != m:
+            raise ValueError("kzg_recover: col must hold offsets[-1] entries")
+        v = _fr_limbs(cells, (m, l), "kzg_recover: cells") if m else np.zeros((0, l, 4), dtype=np.uint64)
+        polys = np.zeros((count, n, 4), dtype=np.uint64) if want_polys else None
+        out = np.zeros((count, 2 * (n >> log_l), l, 4), dtype=np.uint64) if want_cells else None
+        ok = np.zeros(count, dtype=np.uint8)
+        some = lambda a: _ptr(a) if a is not None and a.size else None
+        check(self.lib.blsgpu_kzg_recover(self.h, some(cl), _ptr(off) if count else None, count, some(v), int(log_n), int(log_l), int(order), some(polys), some(out), some(ok)),
+              "kzg_recover")
+        return polys, out, ok
+
+    def kzg_recover_device(self, d_col, d_offsets, count, m, d_cells, log_n, log_l, d_polys, d_out_cells, d_ok, order=FR_ORDER_NATURAL):
+        """the same on arrays in device memory (device pointers as ints; scalars 16-byte aligned, u32 arrays 4-byte; no overlap of an output
+        with anything; d_polys or d_out_cells may be None); asynchronous on the context's stream.  A malformed polynomial (a bad or
+        duplicate cell number, fewer than c cells, broken offsets) gets ok = 0 and is reported by the next synchronize."""
+        check(self.lib.blsgpu_kzg_recover_device(self.h, d_col, d_offsets, int(count), int(m), d_cells, int(log_n), int(log_l), int(order), d_polys, d_out_cells, d_ok),
+              "kzg_recover_device")
+
     def fr_to_bytes(self, limbs, return_flags=False):
         """`Scalar::to_bytes` (scalar.rs:284-296) over (n, 4) u64 Montgomery limbs -> (n, 32) uint8; flags: limbs below r"""
         a = _u64(limbs, (-1, 4))

@@ -151,6 +151,7 @@ static int ctx_init(blsgpu_ctx* c) {
   for (auto& e : c->ev) HIPCHK(hipEventCreate(&e));
   for (auto& e : c->ev_fr) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (auto& e : c->ev_fr_cs) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&c->ev_kzgr_roots, hipEventDisableTiming));
   for (auto& e : c->ev_fb) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&c->ev_gt_one, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&c->ev_ver, hipEventDisableTiming));
@@ -215,6 +216,7 @@ extern "C" void blsgpu_destroy(blsgpu_ctx* c) {
   for (auto& e : c->ev) if (e) hipEventDestroy(e);
   for (auto& e : c->ev_fr) if (e) hipEventDestroy(e);
   for (auto& e : c->ev_fr_cs) if (e) hipEventDestroy(e);
+  if (c->ev_kzgr_roots) hipEventDestroy(c->ev_kzgr_roots);
   for (auto& e : c->ev_fb) if (e) hipEventDestroy(e);
   if (c->ev_gt_one) hipEventDestroy(c->ev_gt_one);
   if (c->fold_stream) hipStreamDestroy(c->fold_stream);
@@ -247,6 +249,7 @@ static int take_status(blsgpu_ctx* c) {
     if (st & GSUM_STATUS_BAD) return bad("sum_segments_device: an index lies outside the point set (the term was skipped, that segment's value is unspecified)");
     if (st & FLG_STATUS_BAD) return bad("fr_lagrange_segments_device / lagrange_combine_device: a segment has decreasing offsets, more than BLSGPU_FR_LAGRANGE_LEN_MAX nodes or ends beyond total (nothing of it was written)");
     if (st & KZGV_STATUS_BAD) return bad("kzg_verify_cells_device: a row or cell number is out of range, or a batch's offsets are broken (that batch has verdict 0 and an identity pair)");
+    if (st & KZGR_STATUS_BAD) return bad("kzg_recover_device: a polynomial has a bad or duplicate cell number, fewer than c cells or broken offsets (its ok byte is 0 and its rows are zero)");
     if (st & 8u) return bad("msm_segments_device: a segment has decreasing offsets, more than SEG_LEN_MAX points or bases outside the resident set (its value is unspecified)");
     return bad("msm: a scalar is not canonical (>= r); Scalar::to_bytes never produces such bytes (scalar.rs:284-296)");
   }

@@ -1,5 +1,5 @@
 // api_fr.hip -- the scalar field Fr: element-wise vector operations, the transforms, scans and batch inversion, Lagrange coefficients, fraction
-// scans, evaluation-form openings, sparse products, Poseidon, expression programs, lookup tables, multilinear folds and sumcheck.
+// scans, evaluation-form openings, sparse products, Poseidon, expression programs, lookup tables, multilinear folds and sumcheck, KZG cell recovery.
 #define BLS_TU_NAME "api_fr.hip"
 #include "host.h"
 #include "fr.hip.h"
@@ -13,6 +13,7 @@
 #include "fr_expr.hip.h"
 #include "fr_lookup.hip.h"
 #include "fr_lagrange.hip.h"
+#include "kzg_recover.hip.h"
 
 using namespace bls;
 
@@ -1418,4 +1419,88 @@ extern "C" void blsgpu_fr_sumcheck_free(blsgpu_fr_sumcheck* s) {
   if (!s) return;
   handle_quiesce(s->device);               // work queued on a stream may still use the tables
   frsc_drop(s);
+}
+
+// ---- KZG cell recovery (kzg_recover.hip.h; kzg_recover_plan.h holds the mathematics, the checks, the maps, the scratch layout and the launch shapes) ------
+static KzgrArgs kzgr_args(const void* col, const void* offsets, size_t count, size_t m, const void* cells, int log_n, int log_l, int order, const void* polys, const void* out_cells,
+                          const void* ok, bool device) {
+  KzgrArgs a;
+  a.col = col; a.offsets = offsets; a.count = count; a.m = m; a.cells = cells; a.log_n = log_n; a.log_l = log_l; a.order = order;
+  a.polys = polys; a.out_cells = out_cells; a.ok = ok; a.device = device;
+  return a;
+}
+static int kzg_recover_device(blsgpu_ctx* c, const void* d_col, const void* d_offsets, size_t count, size_t m, const void* d_cells, int log_n, int log_l, int order, void* d_polys,
+                              void* d_out_cells, void* d_ok) {
+  if (!c) return bad("kzg_recover: ctx is NULL");
+  if (const char* why = kzgr_check(kzgr_args(d_col, d_offsets, count, m, d_cells, log_n, log_l, order, d_polys, d_out_cells, d_ok, true))) return bad(why);
+  if (!count) return BLSGPU_OK;
+  const KzgrPlan p = kzgr_plan(log_n, log_l, count, m, d_polys == nullptr);
+  if (!p.ok) return bad("kzg_recover: the plan refuses the shape");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->kzgr.reserve(p.bytes) || c->kzgr_roots.reserve(p.roots_bytes)) { g_err = "hipMalloc(kzg_recover scratch) failed"; return BLSGPU_ERR_HIP; }
+  hipStream_t st = c->stream;
+  uint8_t* base = c->kzgr.as<uint8_t>();
+  u32* eff = (u32*)(base + p.eff); uint8_t* mis = base + p.mis;
+  int* slot = (int*)(base + p.slot);
+  u32 *status = (u32*)(base + p.status), *upper = (u32*)(base + p.upper);
+  u32 *zd = (u32*)(base + p.zd), *zc = (u32*)(base + p.zc), *work = (u32*)(base + p.work);
+  u32 *rootd = (u32*)(c->kzgr_roots.as<uint8_t>() + p.rootd), *rootc = (u32*)(c->kzgr_roots.as<uint8_t>() + p.rootc);
+  uint4* coef = d_polys ? (uint4*)d_polys : (uint4*)(base + p.coef);
+  KLAUNCH(k_kzg_rec_offsets, dim3(p.offsets_grid), dim3(KZGR_BLOCK), 0, st, (const u32*)d_offsets, (u32)count, (u32)m, eff, mis);
+  KLAUNCH(k_kzg_rec_slots, dim3(p.slots_grid), dim3(KZGR_BLOCK), 0, st, (const u32*)eff, (const uint8_t*)mis, (const u32*)d_col, p.log_c, slot, status, upper, c->status_word);
+  if (c->kzgr_roots_log_c != p.log_c || c->kzgr_roots_log_l != log_l) {      // the tables of another shape (cached as the transform caches its coset tables)
+    FrArg g;
+    for (int i = 0; i < 8; i++) g.w[i] = (u32)(KZGR_GEN_MONT[i >> 1] >> (32 * (i & 1)));
+    KLAUNCH(k_kzg_rec_roots, dim3(p.roots_grid), dim3(KZGR_BLOCK), 0, st, rootd, rootc, g, p.log_c, log_l);
+    LAUNCHCHK();
+    c->kzgr_roots_log_c = p.log_c; c->kzgr_roots_log_l = log_l;
+    HIPCHK(hipEventRecord(c->ev_kzgr_roots, st));
+  }
+  HIPCHK(hipStreamWaitEvent(st, c->ev_kzgr_roots, 0));
+  KLAUNCH(k_kzg_rec_vanish, dim3(p.vanish_grid), dim3(KZGR_BLOCK), 0, st, (const int*)slot, (const u32*)status, (const u32*)rootd, (const u32*)rootc, p.log_c, order, p.vanish_per_poly,
+          KZGR_ROOT_TILE, zd, zc);
+  LAUNCHCHK();
+  if (int rc = blsgpu_fr_batch_invert_device(c, zc, p.tables, zc, nullptr)) return rc;
+  KLAUNCH(k_kzg_rec_scatter<KZGR_TILE>, dim3(p.scatter_grid), dim3(p.scatter_block), 0, st, (const int*)slot, (const uint4*)d_cells, (const u32*)zd, count, p.log_c, log_l, order,
+          (uint4*)work);
+  LAUNCHCHK();
+  if (int rc = blsgpu_fr_ntt_many_device(c, work, log_n + 1, count, 1, nullptr)) return rc;
+  if (int rc = blsgpu_fr_ntt_many_device(c, work, log_n + 1, count, 0, KZGR_GEN_MONT)) return rc;
+  KLAUNCH(k_kzg_rec_scale, dim3(p.scale_grid), dim3(KZGR_BLOCK), 0, st, work, (const u32*)zc, (size_t)p.scalars, log_n, p.log_c);
+  LAUNCHCHK();
+  if (int rc = blsgpu_fr_ntt_many_device(c, work, log_n + 1, count, 1, KZGR_GEN_MONT)) return rc;
+  KLAUNCH(k_kzg_rec_check, dim3(p.finish_grid), dim3(KZGR_BLOCK), 0, st, (const u32*)work, log_n, p.finish_per_poly, upper);
+  KLAUNCH(k_kzg_rec_finish, dim3(p.finish_grid), dim3(KZGR_BLOCK), 0, st, (const uint4*)work, (const u32*)status, (const u32*)upper, log_n, p.finish_per_poly, coef, (uint8_t*)d_ok);
+  LAUNCHCHK();
+  // the coefficients of a failed polynomial are zero by now, so its cells are too
+  if (d_out_cells) return blsgpu_kzg_cells_device(c, coef, log_n, log_l, count, KZG_FORM_COEFFS, order, d_out_cells);
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_kzg_recover_device(blsgpu_ctx* c, const void* col, const void* offsets, size_t count, size_t m, const void* cells, int log_n, int log_l, int order, void* polys,
+                                         void* out_cells, void* ok) { CTX_CLAIM(c);
+  return kzg_recover_device(c, col, offsets, count, m, cells, log_n, log_l, order, polys, out_cells, ok); }
+extern "C" int blsgpu_kzg_recover(blsgpu_ctx* c, const uint32_t* col, const uint32_t* offsets, size_t count, const uint64_t* cells, int log_n, int log_l, int order, uint64_t* polys,
+                                  uint64_t* out_cells, uint8_t* ok) { CTX_CLAIM(c);
+  if (!c) return bad("kzg_recover: ctx is NULL");
+  if (count > ((size_t)1 << KZGR_MAX_LOG_TOTAL)) return bad("kzg_recover: count * 2n must not exceed 2^28");
+  if (count && !offsets) return bad("kzg_recover: NULL offsets or ok with polynomials to recover");
+  const size_t m = count ? offsets[count] : 0;
+  if (const char* why = kzgr_check(kzgr_args(col, offsets, count, m, cells, log_n, log_l, order, polys, out_cells, ok, false))) return bad(why);
+  if (const char* why = kzgr_check_host(offsets, count, col, log_n, log_l)) return bad(why);
+  if (!count) return BLSGPU_OK;
+  HostCall h(c);
+  // the two u32 arrays share one staging buffer (each piece at a 256-byte boundary)
+  const size_t o_off = (m * 4 + 255) / 256 * 256, words = o_off + (count + 1) * 4;
+  void* dcells = h.in(c->io_a, cells, (m << log_l) * 32);
+  uint8_t* wf = nullptr;
+  if (h.reserve(c->io_f, words)) {
+    wf = c->io_f.as<uint8_t>();
+    if (!h.rc && m) h.rc = staged_upload(c, wf, col, m * 4);
+    if (!h.rc) h.rc = staged_upload(c, wf + o_off, offsets, (count + 1) * 4);
+  }
+  void* dp = polys ? h.out(c->io_out, polys, (count << log_n) * 32) : nullptr;
+  void* dc = out_cells ? h.out(c->io_b, out_cells, (count << log_n) * 64) : nullptr;
+  void* dk = h.out(c->flags_b, ok, count);
+  if (h.rc) return h.rc;
+  return h.finish(kzg_recover_device(c, wf, wf + o_off, count, m, dcells, log_n, log_l, order, dp, dc, dk));
 }

@@ -9,7 +9,7 @@
 //   api_pairing.hip  pairings, Miller loops, G2Prepared, final exponentiation, Gt, Fp6 / Fp12 hooks   (pairing / quad / prep / wide)
 //   api_aux.hip      hash-to-curve, expanders and hash-to-scalar, point codecs, bulk BLS verification   (h2c / expand_kernels / codec / generators)
 //   api_fr.hip       Fr vectors, transforms, scans, Lagrange, fraction scans, openings, SpMV, Poseidon,  (fr*.hip.h)
-//                    expression programs, lookup tables, multilinear folds and sumcheck
+//                    expression programs, lookup tables, multilinear folds and sumcheck, KZG cell recovery       (kzg_recover.hip.h)
 //   api_group.hip    device groups: one process driving several GPUs (host code only)
 //
 // Every kernel header is compiled into exactly ONE of them (a non-template __global__ function has one host-side stub per library).
@@ -43,6 +43,7 @@
 #include "fr_lagrange_plan.h"
 #include "kzg_plan.h"
 #include "kzg_verify_plan.h"
+#include "kzg_recover_plan.h"
 
 using namespace bls;
 
@@ -252,6 +253,9 @@ struct blsgpu_ctx {
                                         // zero-extended rows), the segment-order copy (kzg_plan.h)
   DevBuf kzg_pts, kzg_off;              // ... the points between the MSM and the caller's array, the offsets and base_first of the Toeplitz MSM
   DevBuf kzgv;                          // blsgpu_kzg_verify_cells_device: every intermediate of the chain, laid out by kzg_verify_plan.h
+  DevBuf kzgr;                          // blsgpu_kzg_recover_device: every intermediate of the chain, laid out by kzg_recover_plan.h
+  DevBuf kzgr_roots; int kzgr_roots_log_c = -1, kzgr_roots_log_l = -1;      // ... and its root tables (w^l)^rho, g^l (w^l)^rho of the last (log_c, log_l) used
+  hipEvent_t ev_kzgr_roots = nullptr;   // as ev_fr_cs: recorded where the tables were built, awaited by every user
   DevBuf frp_nodes;                     // blsgpu_fr_poseidon_merkle_device with nodes == NULL: the levels below the roots (fr_poseidon_plan.h)
 };
 

@@ -979,8 +979,8 @@ int blsgpu_g2_ntt_many_device(blsgpu_ctx* ctx, void* d_xyz, int log_n, size_t k,
  * BLSGPU_ERR_ARG with nothing staged or launched: a NULL pointer with work to do; a G2 or too-short SRS (blsgpu_bases_len < n); an SRS
  * whose subgroup state is 0 (a point outside the subgroup); log_n, log_l, count, form or order out of range, 64-bit overflow of the
  * products included; a misaligned device pointer; an overlap.
- * Not in scope: verification of cells (a call of its own: blsgpu_kzg_verify_cells below), recovery from half the cells, G2, a Lagrange-form SRS, window-table precomputation for the
- * Toeplitz MSM. */
+ * Calls of their own: verification of cells (blsgpu_kzg_verify_cells below) and recovery from half the cells (blsgpu_kzg_recover below).
+ * Not in scope: G2, a Lagrange-form SRS, window-table precomputation for the Toeplitz MSM. */
 typedef struct blsgpu_kzg_multiproof blsgpu_kzg_multiproof;
 #define BLSGPU_KZG_FORM_COEFFS 0   /* n coefficients, X^0 first */
 #define BLSGPU_KZG_FORM_EVALS  1   /* n values on <w^2> in `order` (BLSGPU_FR_ORDER_*), as fr_bary_* reads them */
@@ -1041,8 +1041,8 @@ int blsgpu_kzg_cells_device(blsgpu_ctx* ctx, const void* d_polys, int log_n, int
  * gather, ONE mul_batch, segment sums, inverse fr_ntt_many of the cells, the fold, msm_segments over S[0..l), batch_normalize,
  * multi_miller_loop_prepared_many with final exponentiation, gt_is_identity -- runs on the context's stream with scratch of its own (about
  * 820 + 32 l bytes per cell), not shared with pipelined *_msm_device calls in flight.
- * Not in scope: byte-level inputs, big-endian scalars, Fiat-Shamir derivation of r, recovery from half the cells, a Pippenger MSM over
- * the fresh proofs (it would need *_bases_from_device and its synchronisation), multi-GPU. */
+ * Not in scope: byte-level inputs, big-endian scalars, Fiat-Shamir derivation of r, a Pippenger MSM over the fresh proofs (it would need
+ * *_bases_from_device and its synchronisation), multi-GPU.  A call of its own: recovery from half the cells (blsgpu_kzg_recover below). */
 typedef struct blsgpu_kzg_cell_verifier blsgpu_kzg_cell_verifier;
 int blsgpu_kzg_cell_verifier_create(blsgpu_ctx* ctx, const blsgpu_bases* srs_g1, int log_n, int log_l, const uint64_t* q_xy, const uint8_t* q_inf, blsgpu_kzg_cell_verifier** out);
 int blsgpu_kzg_cell_verifier_log_n(const blsgpu_kzg_cell_verifier* h);
@@ -1055,6 +1055,50 @@ int blsgpu_kzg_verify_cells(blsgpu_ctx* ctx, const blsgpu_kzg_cell_verifier* h, 
 int blsgpu_kzg_verify_cells_device(blsgpu_ctx* ctx, const blsgpu_kzg_cell_verifier* h, const void* d_commit_xy, const void* d_commit_inf, size_t ncommit, const void* d_row,
                                    const void* d_col, const void* d_cells, const void* d_proof_xy, const void* d_proof_inf, const void* d_offsets, size_t nseg, size_t m,
                                    const void* d_r, int order, void* d_verdict, void* d_out_ab);
+/* KZG cell recovery: a polynomial rebuilt from ANY c of its 2c cells, and from it all 2c cells again -- the third operation of
+ * data-availability sampling: blsgpu_kzg_verify_cells on what was received -> blsgpu_kzg_recover -> blsgpu_kzg_multiproof_proofs on the
+ * recovered coefficients -> serve the full set, all on the device.  Notation is that of the two comments above: n = 2^log_n, l = 2^log_l,
+ * c = n / l, w the root blsgpu_fr_ntt uses for log_n + 1; cell i < 2c is the coset h_i <w^(2c)>, numbered by `order` (BLSGPU_FR_ORDER_*)
+ * exactly as blsgpu_kzg_cells writes it; g = 7, the reference's GENERATOR.
+ *   offsets, count [, m]   count + 1 u32, the CSR array of *_msm_segments: polynomial v owns the received cells offsets[v] .. offsets[v + 1],
+ *                 in any order; m = offsets[count] is passed by value in the device form
+ *   col           m u32: received cell k is cell number col[k] < 2c in `order`
+ *   cells         m x l scalars, canonical Montgomery limbs, entry t of cell k as blsgpu_kzg_cells numbers it in `order`
+ *   polys         NULL, or count x n coefficients, X^0 first: BLSGPU_KZG_FORM_COEFFS, ready for blsgpu_kzg_multiproof_proofs_device
+ *   out_cells     NULL, or count x 2c x l scalars: ALL cells in `order`, exactly what blsgpu_kzg_cells writes for the recovered polynomial;
+ *                 the received cells come back limb-identical when ok[v] = 1.  With ORDER_BITREV the first c cells are the n values of
+ *                 the polynomial on <w^2> in bit-reversed order: the blob in evaluation form.  One of polys / out_cells must be given.
+ *   ok            count bytes, required.  ok[v] = 1: recovered, and every received cell lies on the polynomial written.  ok[v] = 0: the
+ *                 cells are inconsistent (no polynomial of degree < n takes them all), or the polynomial's input is malformed (below);
+ *                 its rows of polys / out_cells are then all zero.  Inconsistent data is an ordinary outcome and does NOT set the
+ *                 context's sticky flag.  With exactly c cells any values are consistent.
+ * For polynomial v with M its missing cells (|M| <= c) and a_i = h_i^l the result is DEFINED by
+ *   Z(X) = prod_{i in M} (X^l - a_i);   EZ[j] = the received value at w^j times Z(w^j), 0 at the points of missing cells   (j < 2n)
+ *   Q = the 2n coefficients of (P Z) / Z, P Z interpolated from EZ on <w> and divided by Z pointwise on the coset g <w>
+ *   ok[v] = Q[n .. 2n) is all zero;   polys[v] = Q[0 .. n)
+ * Z(w^j) and Z(g w^j) depend on j mod 2c alone: two tables of 2c scalars per polynomial, built by direct products (O(c^2) per polynomial),
+ * the second inverted by ONE batch inversion (it has no zero: g^(2n) != 1).  The chain -- effective offsets, slot table, roots, tables,
+ * blsgpu_fr_batch_invert_device, the tiled scatter, inverse blsgpu_fr_ntt_many_device, the forward and the inverse one on the coset g with
+ * the scaling between them, the check of the upper half, and blsgpu_kzg_cells_device when out_cells is given -- runs on the context's
+ * stream; the device form is asynchronous and never synchronises; its launches depend on (log_n, log_l, count, m) alone (and on whether the root tables of (log_n, log_l) are the ones the context holds); its scratch
+ * (about 64 n + 136 c bytes per polynomial, 32 n more without polys, next to that of the calls it chains) is the context's own and is not
+ * shared with pipelined *_msm_device calls in flight.  Scalars are Montgomery limbs whatever blsgpu_set_scalar_form says.  The
+ * caller's arrays are never written.
+ * Limits: log_n in [0, 27], log_l in [0, min(log_n, 12)], log_n - log_l + 1 <= 12 (2c <= 4096), count * 2n <= 2^28, m <= 2^24,
+ * m * l <= 2^28.  Scalar arrays are 16-byte aligned, u32 arrays 4-byte.  count == 0 is a no-op.
+ * BLSGPU_ERR_ARG with nothing staged or launched: a NULL required pointer; both outputs NULL; a range or product overflow, 64-bit wrap
+ * included; a bad `order`; a misaligned device pointer; any overlap of an output with an input or with another output.  The host form
+ * also refuses offsets that do not start at 0 or that decrease, col[k] >= 2c, a cell listed twice for one polynomial and fewer than c
+ * cells for a polynomial.  The device form cannot see any of that: a polynomial with a bad or duplicate cell number, with fewer than c
+ * cells, or with a broken offset (one that is not the running maximum of the offsets before it, or beyond m; offsets[0] != 0;
+ * offsets[count] != m -- the rule of blsgpu_kzg_verify_cells_device) gets ok[v] = 0 and zero rows, the context's sticky flag is set (the
+ * next blsgpu_synchronize returns BLSGPU_ERR_ARG), every other polynomial is right, and no bad value is ever used as an address.
+ * Not in scope: recomputing the proofs inside the call (chain blsgpu_kzg_multiproof_proofs_device on polys), byte-level cells, sharing the
+ * tables between polynomials with equal patterns, 2c > 4096. */
+int blsgpu_kzg_recover(blsgpu_ctx* ctx, const uint32_t* col, const uint32_t* offsets, size_t count, const uint64_t* cells, int log_n, int log_l, int order, uint64_t* polys,
+                       uint64_t* out_cells, uint8_t* ok);
+int blsgpu_kzg_recover_device(blsgpu_ctx* ctx, const void* d_col, const void* d_offsets, size_t count, size_t m, const void* d_cells, int log_n, int log_l, int order, void* d_polys,
+                              void* d_out_cells, void* d_ok);
 
 /* ---- hash-to-curve (the step in front of multi_miller_loop in bulk signature checks) ---- */
 /* `<G as HashToCurve<ExpandMsgXmd<Sha256>>>::hash_to_curve(msg, dst)` / `encode_to_curve` (encode_only != 0) for n
