@@ -4,6 +4,7 @@
 #include "abi_kernels.hip.h"
 #include "mulbatch.hip.h"
 #include "msm_seg.hip.h"
+#include "msm_plan.h"
 #include "gntt.hip.h"
 #include "gsum.hip.h"
 #include "lagrange_combine.hip.h"
@@ -207,19 +208,11 @@ extern "C" int blsgpu_bases_download(blsgpu_ctx* c, const blsgpu_bases* b, size_
 // ---------------------------------------------------------------------------------------------------
 // MSM
 // ---------------------------------------------------------------------------------------------------
-static int pick_window(size_t n, int bits) {
-  // minimise  n*W (mixed adds) + 2*W*2^(c-1)*1.2 (bucket reduction), W = ceil(bits/c); n = scalars of `bits` bits
-  int best = 8; double bc = 1e300;
-  for (int c = 6; c <= 16; c++) {
-    int W = (bits + c - 1) / c;
-    double cost = (double)n * W + 2.4 * W * (double)(1u << (c - 1));
-    if (cost < bc) { bc = cost; best = c; }
-  }
-  return best;
-}
-
-// a reduction level runs one chain per TEAM of lanes when that still fits comfortably on the chip
-constexpr size_t TEAM_LANES_MAX = 131072;
+// The shape of a call, the sizes of its scratch and the schedule of its bucket reduction are plain host code (msm_plan.h); what the
+// plan restates from the device headers is held to them here.
+static_assert(MSMP_TEAM == TEAM && MSMP_SORT_MAX_COUNTERS == SORT_MAX_COUNTERS && MSMP_TREE_JOBS_MAX == TREE_JOBS_MAX, "msm_plan.h restates team.hip.h / msm.hip.h");
+static_assert(MSMP_CTRL_WORDS == 4 + 2 * ITEM_BINS && MSMP_ITEM_BYTES == sizeof(ItemDesc) && MSMP_HEAVY_BYTES == sizeof(uint4), "msm_plan.h restates msm.hip.h");
+static_assert(MSMP_MAX_LEVELS == sizeof(blsgpu_ctx::Slot::ev_lvl) / sizeof(hipEvent_t), "one event per reduction level");
 #define TEAM_LDS(threads) ((size_t)team_lds_words<F>(threads) * 4)
 
 template <class F>
@@ -231,14 +224,226 @@ static int msm_check(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, con
   if (n > ((size_t)1 << 27)) return bad("msm: n too large for one call (shard the input)");
   return BLSGPU_OK;
 }
+// the slot's buffers at the sizes of the plan, in a fixed order.  ft: the stream the sort runs on (a fresh counter buffer is cleared
+// there); st: the caller's stream
+static int msm_reserve(blsgpu_ctx::Slot& sl, const MsmSizes& z, hipStream_t ft, hipStream_t st) {
+  int bad_alloc = 0;
+  bad_alloc |= sl.ent.reserve(z.ent);
+  bad_alloc |= sl.sorted.reserve(z.sorted);
+  const bool fresh = sl.hist.cap < z.hist;
+  bad_alloc |= sl.hist.reserve(z.hist);
+  if (fresh && !bad_alloc) HIPCHK(hipMemsetAsync(sl.hist.p, 0, sl.hist.cap, ft));      // the sort keeps its counters zeroed between calls
+  bad_alloc |= sl.cursor.reserve(z.cursor);
+  bad_alloc |= sl.glv.reserve(z.glv);
+  bad_alloc |= sl.offs.reserve(z.offs);
+  bad_alloc |= sl.bsum.reserve(z.bsum);
+  bad_alloc |= sl.items.reserve(z.items);
+  bad_alloc |= sl.heavy.reserve(z.heavy);
+  bad_alloc |= sl.ctrl.reserve(z.ctrl);
+  // (re)allocation frees memory: make sure nothing of this slot is in flight
+  const bool grow = sl.buckets.cap < z.buckets || sl.lvlR[0].cap < z.lvlR || sl.lvlT.cap < z.lvlT || sl.wacc[0].cap < z.wacc || sl.wsums.cap < z.wsums;
+  if (grow) { HIPCHK(hipStreamSynchronize(sl.tail)); HIPCHK(hipStreamSynchronize(sl.tail2)); HIPCHK(hipStreamSynchronize(st)); }
+  bad_alloc |= sl.buckets.reserve(z.buckets);
+  bad_alloc |= sl.lvlR[0].reserve(z.lvlR); bad_alloc |= sl.lvlR[1].reserve(z.lvlR); bad_alloc |= sl.lvlT.reserve(z.lvlT);
+  bad_alloc |= sl.tsum[0].reserve(z.tsum); bad_alloc |= sl.tsum[1].reserve(z.tsum);
+  bad_alloc |= sl.wacc[0].reserve(z.wacc); bad_alloc |= sl.wacc[1].reserve(z.wacc);
+  bad_alloc |= sl.wsums.reserve(z.wsums);
+  bad_alloc |= sl.result.reserve(z.result);
+  if (bad_alloc) { g_err = "hipMalloc(msm scratch) failed"; return BLSGPU_ERR_HIP; }
+  return BLSGPU_OK;
+}
+
+// phase marks of blsgpu_set_profiling
+static inline void msm_mark(blsgpu_ctx* c, int i, hipStream_t stream) { if (c->profiling) hipEventRecord(c->ev[i], stream); }
+
+// 1'-3'. the two-level counting sort (LDS atomics; see msm.hip.h) on ft, behind the decomposition of the scalars where the call has one.
+// stride: the resident bases' count (the index of a table entry is window * stride + i)
+static int msm_sort_fast(blsgpu_ctx* c, blsgpu_ctx::Slot& sl, const MsmShape& s, const void* d_scalars, u32 stride, hipStream_t ft) {
+  // fixed layout: [MAX] counts (kept zero between calls) | [MAX+1] bases | [MAX] cursors
+  u32* ghist = sl.hist.as<u32>();
+  u32* gbase = ghist + SORT_MAX_COUNTERS;
+  u32* gcur = gbase + SORT_MAX_COUNTERS + 1;
+  if (sl.hist_dirty) { HIPCHK(hipMemsetAsync(ghist, 0, (size_t)SORT_MAX_COUNTERS * 4, ft)); sl.hist_dirty = false; }
+  const unsigned tiles = nblk(s.ns, SORT_TILE);
+  const int n = (int)s.n, ns = (int)s.ns, nc = s.nc, sform = c->scalar_form;
+  const u32* sort_in = (const u32*)d_scalars;
+  if (s.glv) {
+    KLAUNCH(k_glv_decompose, dim3(nblk(s.n, 256)), dim3(256), 0, ft, (const u32*)d_scalars, sl.glv.as<u32>(), n, c->status_word, sform);
+    sort_in = sl.glv.as<u32>();
+    KLAUNCH(k_sort_hist<4>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 4, ft, sort_in, ghist, ns, s.cw, s.nwin, s.fine_bits, s.ncoarse, 0, c->status_word);
+  } else if (s.gls) {
+    KLAUNCH(k_gls_decompose, dim3(nblk(s.n, 256)), dim3(256), 0, ft, (const u32*)d_scalars, sl.glv.as<u32>(), n, c->status_word, sform);
+    sort_in = sl.glv.as<u32>();
+    KLAUNCH(k_sort_hist<2>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 4, ft, sort_in, ghist, ns, s.cw, s.nwin, s.fine_bits, s.ncoarse, 0, c->status_word);
+  } else {
+    KLAUNCH(k_sort_hist<8>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 4, ft, sort_in, ghist, ns, s.cw, s.nwin, s.fine_bits, s.ncoarse, s.merged ? 1 : 0, c->status_word);
+  }
+  LAUNCHCHK();
+  msm_mark(c, 1, ft);
+  KLAUNCH(k_sort_scan, dim3(1), dim3(1024), 0, ft, ghist, gbase, gcur, nc, sl.ctrl.as<u32>(), 4 + 2 * ITEM_BINS);
+  LAUNCHCHK();
+  msm_mark(c, 2, ft);
+  if (s.glv)
+    KLAUNCH(k_sort_scatter<4>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 8, ft, sort_in, gbase, gcur, sl.ent.as<u32>(), ns, s.cw, s.nwin, s.fine_bits, s.ncoarse, 0, (u32)0);
+  else if (s.gls)
+    KLAUNCH(k_sort_scatter<2>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 8, ft, sort_in, gbase, gcur, sl.ent.as<u32>(), ns, s.cw, s.nwin, s.fine_bits, s.ncoarse, 0, (u32)0);
+  else
+    KLAUNCH(k_sort_scatter<8>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 8, ft, sort_in, gbase, gcur, sl.ent.as<u32>(), ns, s.cw, s.nwin,
+                       s.fine_bits, s.ncoarse, s.merged ? 1 : 0, stride);
+  KLAUNCH(k_sort_fine, dim3(nc), dim3(256), 0, ft, sl.ent.as<u32>(), gbase, sl.sorted.as<u32>(), sl.offs.as<u32>(), s.fine_bits, nc);
+  LAUNCHCHK();
+  msm_mark(c, 3, ft);
+  return BLSGPU_OK;
+}
+// 1.-3. the fallback beyond the counting sort's reach (more than 2^24 sort scalars; BLSGPU_FORCE_SLOW_SORT): global atomics, on ft
+static int msm_sort_fallback(blsgpu_ctx* c, blsgpu_ctx::Slot& sl, const MsmShape& s, const void* d_scalars, hipStream_t ft) {
+  const int n = (int)s.n, nb = (int)s.nb;
+  // 1. digits + histogram
+  sl.hist_dirty = true;
+  HIPCHK(hipMemsetAsync(sl.hist.p, 0, s.nb * 4, ft));
+  HIPCHK(hipMemsetAsync(sl.ctrl.p, 0, (4 + 2 * ITEM_BINS) * 4, ft));
+  KLAUNCH(k_msm_digits, dim3(nblk(s.n, 256)), dim3(256), 0, ft, (const u32*)d_scalars, sl.ent.as<u32>(), sl.cursor.as<u32>(), sl.hist.as<u32>(), n, s.cw, s.nwin, c->status_word);
+  LAUNCHCHK();
+  msm_mark(c, 1, ft);
+  // 2. scan
+  const unsigned sb = nblk(s.nb, 1024);
+  KLAUNCH(k_scan_block_sums, dim3(sb), dim3(256), 0, ft, sl.hist.as<u32>(), sl.bsum.as<u32>(), nb);
+  KLAUNCH(k_scan_top, dim3(1), dim3(1024), 0, ft, sl.bsum.as<u32>(), (int)sb);
+  KLAUNCH(k_scan_apply, dim3(sb), dim3(256), 0, ft, sl.hist.as<u32>(), sl.bsum.as<u32>(), sl.offs.as<u32>(), nb);
+  LAUNCHCHK();
+  msm_mark(c, 2, ft);
+  // 3. scatter
+  KLAUNCH(k_msm_scatter, dim3(nblk(s.total, 256)), dim3(256), 0, ft, sl.ent.as<u32>(), sl.cursor.as<u32>(), sl.offs.as<u32>(), sl.sorted.as<u32>(), n, s.total);
+  LAUNCHCHK();
+  msm_mark(c, 3, ft);
+  return BLSGPU_OK;
+}
+
+
+// 4.-5. work items on ft, then the bucket accumulation and the fold of cut buckets on as: records [0, nb) of sl.buckets end as the bucket sums
+template <class F>
+static int msm_accumulate(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, blsgpu_ctx::Slot& sl, const MsmShape& s, hipStream_t ft, hipStream_t as) {
+  const int nb = (int)s.nb;
+  u32* ctrl = sl.ctrl.as<u32>();
+  u32* bins = ctrl + 4;
+  u32* bcur = ctrl + 4 + ITEM_BINS;
+  // 4. work items
+  KLAUNCH(k_item_count, dim3(nblk(s.nb, ITEM_BLOCK_BUCKETS)), dim3(256), 0, ft, sl.offs.as<u32>(), bins, ctrl, nb, s.cap);
+  KLAUNCH(k_item_scan, dim3(1), dim3(256), 0, ft, bins, ctrl, s.cap);
+  KLAUNCH(k_item_fill, dim3(nblk(s.nb, ITEM_BLOCK_BUCKETS)), dim3(256), 0, ft, sl.offs.as<u32>(), bins, bcur, ctrl, sl.items.as<ItemDesc>(),
+                     sl.heavy.as<uint4>(), nb, s.cap);
+  LAUNCHCHK();
+  msm_mark(c, 4, ft);
+  if (as != ft) { HIPCHK(hipEventRecord(sl.ev_front, ft)); HIPCHK(hipStreamWaitEvent(as, sl.ev_front, 0)); }
+  // the records (and images) may have been written on another stream than this call's (blsgpu_set_stream after the upload)
+  if (!bases->ready_seen) {
+    if (hipEventQuery(bases->ev_ready) == hipSuccess) bases->ready_seen = true;
+    else HIPCHK(hipStreamWaitEvent(as, bases->ev_ready, 0));
+  }
+  // 5. accumulate (grid covers the worst-case item count; surplus lanes exit on ctrl[2])
+  // timing events are not free in a pipelined run (two records cost ~0.05-0.1 ms of queue time per MSM): sample every N-th launch
+  const bool time_this = c->acc_timing && (c->acc_tick++ % (unsigned)c->acc_timing) == 0;
+  if (time_this) { acc_harvest(c, false); if (sl.k_pending) { hipEventSynchronize(sl.ev_k1); acc_harvest(c, false); } hipEventRecord(sl.ev_k0, as); }
+  u32* records = sl.buckets.as<u32>();
+  const u32* base_rec = (s.merged ? bases->table : bases->rec) + first * Store<F>::AFF_WORDS;
+  if constexpr (GroupTag<F>::id == 2)
+    KLAUNCH(k_msm_accumulate_g2pair, dim3(nblk(2 * s.max_items, BLS_G2ACC_BLOCK)), dim3(BLS_G2ACC_BLOCK), 0, as, s.gls ? bases->endo + 4 * first * Store<F>::AFF_WORDS : base_rec,
+                       sl.sorted.as<u32>(), sl.items.as<ItemDesc>(), ctrl, records);
+  else
+    KLAUNCH(k_msm_accumulate<F>, dim3(nblk(s.max_items, BLS_ACC_BLOCK)), dim3(BLS_ACC_BLOCK), 0, as, base_rec, s.glv ? bases->endo + first * Store<F>::AFF_WORDS : (const u32*)nullptr,
+                       s.glv ? (u32)s.n : 0xffffffffu, sl.sorted.as<u32>(), sl.items.as<ItemDesc>(), ctrl, records);
+  if (time_this) { hipEventRecord(sl.ev_k1, as); sl.k_pending = true; }
+  // the fold of cut buckets (almost always a no-op) stays on the accumulation stream: as the first kernel of the tail it made
+  // the next accumulation start ~90 us earlier, inside the previous call's bottom reduction level, and the pipelined rate FELL
+  // by 2.6 % (A/B on one box, twice: 3.57 vs 3.66*10^8 scalar-muls/s)
+  const u32 heavy_small_blocks = (u32)nblk(s.nb, 256);
+  KLAUNCH(k_msm_heavy<F>, dim3(heavy_small_blocks + HEAVY_BIG_BLOCKS), dim3(256), 0, as, sl.heavy.as<uint4>(), ctrl, records, (u32)s.nb, heavy_small_blocks);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+
+// the rows of the Horner table: the T sum of level l for every bucket set, in wacc[0]
+template <class F> static u32* msm_horner_row(blsgpu_ctx::Slot& sl, int nseg, int level) { return sl.wacc[0].as<u32>() + (size_t)level * nseg * Store<F>::PROJ_WORDS; }
+// one pass of every unfinished T tree, on t2: a single multi-job launch when all of them fit the team form
+template <class F>
+static int msm_tree_step(blsgpu_ctx::Slot& sl, int nseg, const MsmTreeStep& step, hipStream_t t2) {
+  constexpr int PW = Store<F>::PROJ_WORDS;
+  auto in = [&](const MsmTreePass& p) -> const u32* { return (p.src < 0 ? sl.lvlT.as<u32>() : sl.tsum[p.src].as<u32>()) + p.off * PW; };
+  auto out = [&](const MsmTreePass& p) -> u32* { return p.to_horner ? msm_horner_row<F>(sl, nseg, p.level) : sl.tsum[p.pp].as<u32>() + p.off * PW; };
+  for (int i = 0; i < step.npass; i++) {
+    const MsmTreePass& p = step.pass[i];
+    if (!p.multi) KLAUNCH(k_tree_sum<F>, dim3(nblk((size_t)nseg * p.TG, 256)), dim3(256), 0, t2, in(p), out(p), nseg, p.n, p.TM);
+  }
+  TreeJobs J;
+  msm_tree_jobs(J, nseg, step, in, out);
+  if (J.njobs) KLAUNCH(k_tree_sum_team_multi<F>, dim3(step.multi_grid), dim3(MSMP_BLOCK), TEAM_LDS(256), t2, J);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+// 6. per-window weighted sums  wsum = sum_b (b + 1) * bucket_b  by the schedule of msm_plan.h: the levels on tt, the T trees on t2;
+// sl.wsums ends as one record per bucket set
+template <class F>
+static int msm_reduce(blsgpu_ctx::Slot& sl, const MsmReduction& red, hipStream_t tt, hipStream_t t2) {
+  constexpr int PW = Store<F>::PROJ_WORDS;
+  const int nseg = red.nseg;
+  const u32* records = sl.buckets.as<u32>();
+  const u32* E = records;
+  for (int l = 0; l < red.levels; l++) {
+    const MsmLevel& L = red.level[l];
+    u32* Rout = sl.lvlR[l & 1].as<u32>();
+    u32* Tout = L.to_horner ? msm_horner_row<F>(sl, nseg, l) : sl.lvlT.as<u32>() + L.toff * PW;
+    // team2: the two running sums of a chain (R and T) advance on two teams / two lanes, T one step behind R: M + 1 dependent
+    // additions per level instead of 2 M
+    if (L.form == MSM_FORM_TEAM2)
+      KLAUNCH(k_wsum_level_team2<F>, dim3(L.grid), dim3(MSMP_BLOCK),
+                         TEAM_LDS(256) + (size_t)(256 / TEAM / 2) * 3 * TeamTraits<F>::WORDS * 4, tt, E, Rout, Tout, nseg, L.n, L.M, L.off);
+    else if (L.form == MSM_FORM_TEAM)
+      KLAUNCH(k_wsum_level_team<F>, dim3(L.grid), dim3(MSMP_BLOCK), TEAM_LDS(256), tt, E, Rout, Tout, nseg, L.n, L.M, L.off);
+    else if constexpr (GroupTag<F>::id == 2)
+      KLAUNCH(k_wsum_level_g2pair, dim3(L.grid), dim3(MSMP_BLOCK), 0, tt, E, Rout, Tout, nseg, L.n, L.M, L.off);
+    else
+      KLAUNCH(k_wsum_level_pair, dim3(nblk(L.lanes, BLS_WSUM_BLOCK)), dim3(BLS_WSUM_BLOCK), 0, tt, E, Rout, Tout, nseg, L.n, L.M, L.off);
+    LAUNCHCHK();
+    // sum the G T-records of each window down to one -- on the second tail stream: the next level needs only Rout.  Level l
+    // needs log8(G_l) passes; after every level ONE launch carries the next pass of every tree that still has one (the T
+    // trees of different levels are independent), so the trees finish while the R chain is still running.
+    if (L.G > 1 && t2 != tt) { HIPCHK(hipEventRecord(sl.ev_lvl[l], tt)); HIPCHK(hipStreamWaitEvent(t2, sl.ev_lvl[l], 0)); }
+    if (int rc = msm_tree_step<F>(sl, nseg, red.step[l], t2)) return rc;
+    E = Rout;
+  }
+  for (int t = red.levels; t < red.nsteps; t++)              // passes that are left when the last level has run
+    if (int rc = msm_tree_step<F>(sl, nseg, red.step[t], t2)) return rc;
+  if (t2 != tt) { HIPCHK(hipEventRecord(sl.ev_tree, t2)); HIPCHK(hipStreamWaitEvent(tt, sl.ev_tree, 0)); }
+  if (red.levels == 0) {
+    // a single bucket per window (c = 1): the bucket itself is the window sum
+    HIPCHK(hipMemcpyAsync(sl.wsums.p, records, (size_t)nseg * PW * 4, hipMemcpyDeviceToDevice, tt));
+    return BLSGPU_OK;
+  }
+  // Horner over the levels: acc_L = T_L ; acc_l = T_l + M_l * acc_{l+1}
+  u32* accbuf = sl.wacc[1].as<u32>();
+  HIPCHK(hipMemcpyAsync(accbuf, msm_horner_row<F>(sl, nseg, red.levels - 1), (size_t)nseg * PW * 4, hipMemcpyDeviceToDevice, tt));
+  for (int l = red.levels - 2; l >= 0; l--) {
+    KLAUNCH(k_shift_add_team<F>, dim3(nblk((size_t)nseg * TEAM, 256)), dim3(256), TEAM_LDS(256), tt, accbuf, msm_horner_row<F>(sl, nseg, l), accbuf, nseg, red.level[l].shift);
+    LAUNCHCHK();
+  }
+  HIPCHK(hipMemcpyAsync(sl.wsums.p, accbuf, (size_t)nseg * PW * 4, hipMemcpyDeviceToDevice, tt));
+  return BLSGPU_OK;
+}
+// 7. combine the window sums and export the result, on tt
+template <class F>
+static int msm_combine(blsgpu_ctx::Slot& sl, const MsmShape& s, void* d_out_wire, hipStream_t tt) {
+  KLAUNCH(k_msm_combine_team<F>, dim3(1), dim3(TEAM), TEAM_LDS(TEAM), tt, sl.wsums.as<u32>(), sl.result.as<u32>(), s.nseg, s.cw);
+  LAUNCHCHK();
+  KLAUNCH(k_proj_export<F>, dim3(1), dim3(256), 0, tt, sl.result.as<u32>(), (u32*)d_out_wire, (size_t)1);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+
+
 template <class F>
 static int msm_device(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, const void* d_scalars, size_t n, void* d_out_wire) {
   if (int rc = msm_check<F>(c, bases, first, d_scalars, n, d_out_wire)) return rc;
   HIPCHK(hipSetDevice(c->device));
-  // Calls beyond the sort's index width with the endomorphism split (G1: 2 n > 2^24, G2: 4 n > 2^24) run on plain windows.
-  // Cutting them into passes that each keep the split was measured (round 3, 2^24 G1 points on one MI355X: two GLV passes
-  // 52.6 ms against 45.9 ms for one plain pass): the split halves the WINDOWS, not the bucket additions, and at this size
-  // the additions are everything -- two tails and gathers over twice the memory only add to them.
   hipStream_t st = c->stream;
   constexpr int PW = Store<F>::PROJ_WORDS;
   if (c->result.reserve(PW * 4)) { g_err = "hipMalloc failed"; return BLSGPU_ERR_HIP; }
@@ -250,318 +455,48 @@ static int msm_device(blsgpu_ctx* c, const blsgpu_bases* bases, size_t first, co
     LAUNCHCHK();
     return BLSGPU_OK;
   }
-  // resident window-shifted tables (blsgpu_bases_precompute): all windows share one bucket set
-  const bool merged = bases->table != nullptr;
-  // GLV (G1): 2n points (the bases and their images under the endomorphism) with balanced 127-bit scalars -> half the windows
-  const bool glv = GroupTag<F>::id == 1 && !merged && bases->endo && !c->no_glv && !c->force_slow_sort && 2 * n <= ((size_t)1 << 24);
-  // four-dimensional decomposition (G2): 4n points (every base with its images under psi, psi^2, psi^3) with 63-bit scalars -> a quarter of the windows
-  const bool gls = GroupTag<F>::id == 2 && !merged && bases->endo && !c->no_glv && !c->force_slow_sort && 4 * n <= ((size_t)1 << 24);
-  const size_t ns = glv ? 2 * n : gls ? 4 * n : n;      // scalars the sort sees
-  const int sbits = glv ? 128 : gls ? 64 : 256;         // ... and their width (incl. the spare bit of the signed recoding)
-  const int cw = merged ? bases->table_c : (c->msm_c ? c->msm_c : pick_window(ns, sbits));
-  const int nwin = (sbits + cw - 1) / cw;               // digit windows per scalar
-  const int nseg = merged ? 1 : nwin;                   // independent bucket sets
-  const u32 nbw = 1u << (cw - 1);
-  const size_t nb = (size_t)nseg * nbw;
-  const size_t total = (size_t)nwin * ns;
-  if (total > 0xfffffff0ull) return bad("msm: n * windows exceeds 2^32 entries");
   // the whole configuration is validated BEFORE a slot is taken or anything is enqueued
-  const bool fast_sort = merged || ((ns <= ((size_t)1 << 24)) && cw <= 16 && cw >= 2 && !c->force_slow_sort);
-  const int key_bits = cw - 1;
-  const int coarse_bits = merged ? (key_bits > 7 ? key_bits - 7 : 0) : (key_bits < 8 ? key_bits : 8);
-  const int fine_bits = key_bits - coarse_bits;           // <= 7
-  const int ncoarse = 1 << coarse_bits;
-  const int nc = nseg * ncoarse;
-  if (fast_sort && nc > SORT_MAX_COUNTERS) return bad("msm: window configuration exceeds the sort's counter table");
-  if (!fast_sort && nblk(nb, 1024) > 4096) return bad("msm: too many buckets for the fallback sort (use a window <= 16)");
-  int bad_alloc = 0;
+  const MsmShape s = msm_shape(GroupTag<F>::id, n, bases->table ? bases->table_c : 0, bases->endo != nullptr, c->no_glv, c->force_slow_sort, c->msm_c, c->item_cap);
+  if (s.refusal) return bad(s.refusal);
+  const MsmReduction red = msm_reduction(s.nseg, s.nbw);
+  if (red.refusal) return bad(red.refusal);
+  const MsmSizes z = msm_sizes(s, PW, c->scalar_form == SCALAR_MONT);
   blsgpu_ctx::Slot& sl = c->slot[c->next_slot];
   c->next_slot = (c->next_slot + 1) % NSLOT;
   // One call at a time (no pipelining): front, accumulation and tail run on the caller's stream -- every cross-stream
   // dependency costs a barrier packet and 20-90 us of idle time between the phases (kernel trace of a single call), and there is
-  // nothing to overlap with.  Only the T tree sums keep their side stream.  Pipelined calls use the slot's own streams.
+  // nothing to overlap with.  Only the T tree sums keep their side stream.  Pipelined calls use the slot's own streams, and
+  // accumulate on the library's own: front(i+1) must not queue behind accumulate(i).
   const bool single = !c->pipelining;
-  hipStream_t ft = single ? st : sl.front, tt = single ? st : sl.tail;
+  const hipStream_t ft = single ? st : sl.front, as = single ? st : c->acc_stream, tt = single ? st : sl.tail, t2 = sl.tail2;
   // every buffer of this slot may still be in use by the call that used it last (NSLOT calls ago)
   if (sl.tail_pending) { HIPCHK(hipStreamWaitEvent(ft, sl.ev_tail, 0)); HIPCHK(hipStreamWaitEvent(st, sl.ev_tail, 0)); }
-  bad_alloc |= sl.ent.reserve(total * 4);
-  bad_alloc |= sl.sorted.reserve(total * 4);
-  {
-    size_t hb = (nb > 3 * (size_t)SORT_MAX_COUNTERS + 4 ? nb : 3 * (size_t)SORT_MAX_COUNTERS + 4) * 4;
-    bool fresh = sl.hist.cap < hb;
-    bad_alloc |= sl.hist.reserve(hb);
-    if (fresh && !bad_alloc) HIPCHK(hipMemsetAsync(sl.hist.p, 0, sl.hist.cap, ft));      // the sort keeps its counters zeroed between calls
-  }
-  if (!fast_sort) bad_alloc |= sl.cursor.reserve(total * 4);      // per-entry rank inside its bucket (fallback sort only)
-  const int sform = c->scalar_form;
-  const bool plain_mont = sform == SCALAR_MONT && !glv && !gls;      // no decomposition kernel touches the scalars: reduce them first
-  if (glv) bad_alloc |= sl.glv.reserve(ns * 16);
-  if (gls) bad_alloc |= sl.glv.reserve(ns * 8);
-  if (plain_mont) bad_alloc |= sl.glv.reserve(n * 32);
-  bad_alloc |= sl.offs.reserve((nb + 1) * 4);
-  bad_alloc |= sl.bsum.reserve(4096 * 4);
-  // item cap: ~4x the mean bucket load, so that with uniform scalars (almost) no bucket is cut
-  u32 cap = 128;
-  while (cap < ITEM_CAP_MAX && (size_t)cap * nbw < 4 * ns) cap *= 2;
-  if (c->item_cap) cap = c->item_cap;
-  const size_t max_items = total / cap + nb + 1;                // every bucket has >= 1 item
-  const size_t max_records = nb + max_items;                    // bucket sums + partial sums of heavy buckets
-  {
-    blsgpu_ctx::Slot* g = &sl;
-    bad_alloc |= g->items.reserve(max_items * sizeof(ItemDesc));
-    bad_alloc |= g->heavy.reserve(2 * nb * sizeof(uint4));            // the heavy list, then the indices of its block-folded entries
-    bad_alloc |= g->ctrl.reserve((4 + 2 * ITEM_BINS) * 4);
-    // (re)allocation frees memory: make sure nothing of this slot is in flight
-    size_t lvl = (nb / 2 + 1) * PW * 4;
-    bool grow = g->buckets.cap < max_records * PW * 4 || g->lvlR[0].cap < lvl || g->lvlT.cap < 2 * lvl || g->wacc[0].cap < (size_t)nwin * 32 * PW * 4 || g->wsums.cap < (size_t)nwin * PW * 4;
-    if (grow) { HIPCHK(hipStreamSynchronize(g->tail)); HIPCHK(hipStreamSynchronize(g->tail2)); HIPCHK(hipStreamSynchronize(st)); }
-    bad_alloc |= g->buckets.reserve(max_records * PW * 4);
-    bad_alloc |= g->lvlR[0].reserve(lvl); bad_alloc |= g->lvlR[1].reserve(lvl); bad_alloc |= g->lvlT.reserve(2 * lvl);     // every level's T records side by side
-    bad_alloc |= g->tsum[0].reserve(lvl); bad_alloc |= g->tsum[1].reserve(lvl);
-    bad_alloc |= g->wacc[0].reserve((size_t)nwin * 32 * PW * 4); bad_alloc |= g->wacc[1].reserve((size_t)nwin * 32 * PW * 4);
-    bad_alloc |= g->wsums.reserve((size_t)nwin * PW * 4);
-    bad_alloc |= g->result.reserve(PW * 4);
-  }
-  if (bad_alloc) { g_err = "hipMalloc(msm scratch) failed"; return BLSGPU_ERR_HIP; }
-  const bool prof = c->profiling;
-  auto mark = [&](int i) { if (prof) hipEventRecord(c->ev[i], ft); };
+  if (int rc = msm_reserve(sl, z, ft, st)) return rc;
   // the front stream starts after whatever produced the scalars on the caller's stream
   if (ft != st) { HIPCHK(hipEventRecord(sl.ev_in, st)); HIPCHK(hipStreamWaitEvent(ft, sl.ev_in, 0)); }
 
-  mark(0);
-  if (plain_mont) {
+  // ---- front: the sorted entry list and the bucket offsets ----------------------------------------------------------------------------
+  msm_mark(c, 0, ft);
+  if (c->scalar_form == SCALAR_MONT && !s.glv && !s.gls) {       // no decomposition kernel touches the scalars: reduce them first
     KLAUNCH(k_scalars_from_mont, dim3(nblk(n, 256)), dim3(256), 0, ft, (const u32*)d_scalars, sl.glv.as<u32>(), (int)n, c->status_word);
     LAUNCHCHK();
     d_scalars = sl.glv.p;
   }
-  if (fast_sort) {
-    // 1'-3'. two-level counting sort (LDS atomics; see msm.hip.h)
-    // fixed layout: [MAX] counts (kept zero between calls) | [MAX+1] bases | [MAX] cursors
-    u32* ghist = sl.hist.as<u32>();
-    u32* gbase = ghist + SORT_MAX_COUNTERS;
-    u32* gcur = gbase + SORT_MAX_COUNTERS + 1;
-    if (sl.hist_dirty) { HIPCHK(hipMemsetAsync(ghist, 0, (size_t)SORT_MAX_COUNTERS * 4, ft)); sl.hist_dirty = false; }
-    const unsigned tiles = nblk(ns, SORT_TILE);
-    const u32* sort_in = (const u32*)d_scalars;
-    if (glv) {
-      KLAUNCH(k_glv_decompose, dim3(nblk(n, 256)), dim3(256), 0, ft, (const u32*)d_scalars, sl.glv.as<u32>(), (int)n, c->status_word, sform);
-      sort_in = sl.glv.as<u32>();
-      KLAUNCH(k_sort_hist<4>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 4, ft, sort_in, ghist, (int)ns, cw, nwin, fine_bits, ncoarse, 0, c->status_word);
-    } else if (gls) {
-      KLAUNCH(k_gls_decompose, dim3(nblk(n, 256)), dim3(256), 0, ft, (const u32*)d_scalars, sl.glv.as<u32>(), (int)n, c->status_word, sform);
-      sort_in = sl.glv.as<u32>();
-      KLAUNCH(k_sort_hist<2>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 4, ft, sort_in, ghist, (int)ns, cw, nwin, fine_bits, ncoarse, 0, c->status_word);
-    } else {
-      KLAUNCH(k_sort_hist<8>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 4, ft, sort_in, ghist, (int)ns, cw, nwin, fine_bits, ncoarse, merged ? 1 : 0, c->status_word);
-    }
-    LAUNCHCHK();
-    mark(1);
-    KLAUNCH(k_sort_scan, dim3(1), dim3(1024), 0, ft, ghist, gbase, gcur, nc, sl.ctrl.as<u32>(), 4 + 2 * ITEM_BINS);
-    LAUNCHCHK();
-    mark(2);
-    if (glv)
-      KLAUNCH(k_sort_scatter<4>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 8, ft, sort_in, gbase, gcur, sl.ent.as<u32>(), (int)ns, cw, nwin, fine_bits, ncoarse, 0, (u32)0);
-    else if (gls)
-      KLAUNCH(k_sort_scatter<2>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 8, ft, sort_in, gbase, gcur, sl.ent.as<u32>(), (int)ns, cw, nwin, fine_bits, ncoarse, 0, (u32)0);
-    else
-      KLAUNCH(k_sort_scatter<8>, dim3(tiles), dim3(SORT_THREADS), (size_t)nc * 8, ft, sort_in, gbase, gcur, sl.ent.as<u32>(), (int)ns, cw, nwin,
-                         fine_bits, ncoarse, merged ? 1 : 0, (u32)bases->n);
-    KLAUNCH(k_sort_fine, dim3(nc), dim3(256), 0, ft, sl.ent.as<u32>(), gbase, sl.sorted.as<u32>(), sl.offs.as<u32>(), fine_bits, nc);
-    LAUNCHCHK();
-    mark(3);
-  } else {
-    // 1. digits + histogram
-    sl.hist_dirty = true;
-    HIPCHK(hipMemsetAsync(sl.hist.p, 0, nb * 4, ft));
-    HIPCHK(hipMemsetAsync(sl.ctrl.p, 0, (4 + 2 * ITEM_BINS) * 4, ft));
-    KLAUNCH(k_msm_digits, dim3(nblk(n, 256)), dim3(256), 0, ft, (const u32*)d_scalars, sl.ent.as<u32>(), sl.cursor.as<u32>(), sl.hist.as<u32>(), (int)n, cw, nwin, c->status_word);
-    LAUNCHCHK();
-    mark(1);
-    // 2. scan
-    unsigned sb = nblk(nb, 1024);
-    KLAUNCH(k_scan_block_sums, dim3(sb), dim3(256), 0, ft, sl.hist.as<u32>(), sl.bsum.as<u32>(), (int)nb);
-    KLAUNCH(k_scan_top, dim3(1), dim3(1024), 0, ft, sl.bsum.as<u32>(), (int)sb);
-    KLAUNCH(k_scan_apply, dim3(sb), dim3(256), 0, ft, sl.hist.as<u32>(), sl.bsum.as<u32>(), sl.offs.as<u32>(), (int)nb);
-    LAUNCHCHK();
-    mark(2);
-    // 3. scatter
-    KLAUNCH(k_msm_scatter, dim3(nblk(total, 256)), dim3(256), 0, ft, sl.ent.as<u32>(), sl.cursor.as<u32>(), sl.offs.as<u32>(), sl.sorted.as<u32>(),
-                       (int)n, total);
-    LAUNCHCHK();
-    mark(3);
-  }
-  // 4.-7. for the windows [g0, g0 + ng) (the whole call: cutting a single call into a high and a low window group whose tails overlap
-  // was measured in round 4 and is slower, tools/experiments/msm_window_groups.patch): work items, accumulation, bucket reduction,
-  // window combine.  gs = the slot whose buffers, side streams and events are used; gft / gas / gtt / gt2 = front, accumulation, tail
-  // and tree streams
-  auto run_group = [&](blsgpu_ctx::Slot& gs, int g0, int ng, hipStream_t gft, hipStream_t gas, hipStream_t gtt, hipStream_t gt2, bool last) -> int {
-  const size_t gnb = (size_t)ng * nbw;
-  // entries in THIS group's bucket sets / cap + one item per bucket: with resident tables (merged) the single bucket set holds the
-  // entries of ALL nwin windows (the accumulation kernels run one lane per item without a grid stride, so the grid must cover them)
-  const size_t gmax_items = (size_t)(merged ? nwin : ng) * ns / cap + gnb + 1;
-  const u32* goffs = sl.offs.as<u32>() + (size_t)g0 * nbw;
-  // 4. work items
-  u32* ctrl = gs.ctrl.as<u32>();
-  u32* bins = ctrl + 4;
-  u32* bcur = ctrl + 4 + ITEM_BINS;
-  {
-    KLAUNCH(k_item_count, dim3(nblk(gnb, ITEM_BLOCK_BUCKETS)), dim3(256), 0, gft, goffs, bins, ctrl, (int)gnb, cap);
-    KLAUNCH(k_item_scan, dim3(1), dim3(256), 0, gft, bins, ctrl, cap);
-    KLAUNCH(k_item_fill, dim3(nblk(gnb, ITEM_BLOCK_BUCKETS)), dim3(256), 0, gft, goffs, bins, bcur, ctrl, gs.items.as<ItemDesc>(),
-                       gs.heavy.as<uint4>(), (int)gnb, cap);
-    LAUNCHCHK();
-    if (last) mark(4);
-    if (gas != gft) { HIPCHK(hipEventRecord(gs.ev_front, gft)); HIPCHK(hipStreamWaitEvent(gas, gs.ev_front, 0)); }
-  }
-  // the records (and images) may have been written on another stream than this call's (blsgpu_set_stream after the upload)
-  if (!bases->ready_seen) {
-    if (hipEventQuery(bases->ev_ready) == hipSuccess) bases->ready_seen = true;
-    else HIPCHK(hipStreamWaitEvent(gas, bases->ev_ready, 0));
-  }
-  // 5. accumulate (grid covers the worst-case item count; surplus lanes exit on ctrl[2])
-  // timing events are not free in a pipelined run (two records cost ~0.05-0.1 ms of queue time per MSM): sample every N-th launch
-  const bool time_this = c->acc_timing && (c->acc_tick++ % (unsigned)c->acc_timing) == 0;
-  if (time_this) { acc_harvest(c, false); if (gs.k_pending) { hipEventSynchronize(gs.ev_k1); acc_harvest(c, false); } hipEventRecord(gs.ev_k0, gas); }
-  u32* records = gs.buckets.as<u32>();
-  const u32* base_rec = (merged ? bases->table : bases->rec) + first * Store<F>::AFF_WORDS;
-  if constexpr (GroupTag<F>::id == 2)
-    KLAUNCH(k_msm_accumulate_g2pair, dim3(nblk(2 * gmax_items, BLS_G2ACC_BLOCK)), dim3(BLS_G2ACC_BLOCK), 0, gas, gls ? bases->endo + 4 * first * Store<F>::AFF_WORDS : base_rec,
-                       sl.sorted.as<u32>(), gs.items.as<ItemDesc>(), ctrl, records);
-  else
-    KLAUNCH(k_msm_accumulate<F>, dim3(nblk(gmax_items, BLS_ACC_BLOCK)), dim3(BLS_ACC_BLOCK), 0, gas, base_rec, glv ? bases->endo + first * Store<F>::AFF_WORDS : (const u32*)nullptr,
-                       glv ? (u32)n : 0xffffffffu, sl.sorted.as<u32>(), gs.items.as<ItemDesc>(), ctrl, records);
-  if (time_this) { hipEventRecord(gs.ev_k1, gas); gs.k_pending = true; }
-  // the fold of cut buckets (almost always a no-op) stays on the accumulation stream: as the first kernel of the tail it made
-  // the next accumulation start ~90 us earlier, inside the previous call's bottom reduction level, and the pipelined rate FELL
-  // by 2.6 % (A/B on one box, twice: 3.57 vs 3.66*10^8 scalar-muls/s)
-  const u32 heavy_small_blocks = (u32)nblk(gnb, 256);
-  KLAUNCH(k_msm_heavy<F>, dim3(heavy_small_blocks + HEAVY_BIG_BLOCKS), dim3(256), 0, gas, gs.heavy.as<uint4>(), ctrl, records, (u32)gnb, heavy_small_blocks);
-  LAUNCHCHK();
-  if (prof) hipEventRecord(c->ev[5], gas);
-  // ---- tail ------------------------------------------------------------------------------------------------------
-  if (gtt != gas) { HIPCHK(hipEventRecord(gs.ev_acc, gas)); HIPCHK(hipStreamWaitEvent(gtt, gs.ev_acc, 0)); }
-  // 6. per-window weighted sums:  wsum = sum_g T_g + M * wsum0(R)
-  {
-    const int nseg = ng;                                // (shadows the call's window count: everything below is per group)
-    hipStream_t tt = gtt;
-    blsgpu_ctx::Slot& sl = gs;
-    std::vector<int> Ms;
-    const u32* E = records;
-    int nn = (int)nbw, off = 1, cur = 0, level = 0;
-    // level T sums are stored consecutively in wacc[0]: level l at offset l * nseg
-    u32* tstore = sl.wacc[0].template as<u32>();
-    hipStream_t t2 = gt2;
-    size_t toff = 0;                                    // offset (records) of this level's T block inside lvlT
-    struct Tree { const u32* in; int n, pp, level; size_t off; };
-    std::vector<Tree> trees;                            // T trees with passes left
-    // one pass of every unfinished tree: a single multi-job launch when all of them fit the team form
-    auto tree_step = [&]() -> int {
-      TreeJobs J; J.njobs = 0; J.nseg = nseg; J.first_team[0] = 0; J.maxM = 0;
-      for (auto& tr : trees) {
-        if (tr.n <= 1) continue;
-        int TM = tr.n >= 8 ? 8 : tr.n, TG = (tr.n + TM - 1) / TM;
-        u32* o = TG == 1 ? tstore + (size_t)tr.level * nseg * PW : sl.tsum[tr.pp].template as<u32>() + tr.off * PW;   // the last pass lands in the Horner table
-        if ((size_t)nseg * TG * TEAM <= TEAM_LANES_MAX && J.njobs < TREE_JOBS_MAX) {
-          int j = J.njobs++;
-          J.in[j] = tr.in; J.out[j] = o; J.n[j] = tr.n; J.M[j] = TM; J.G[j] = TG; J.first_team[j + 1] = J.first_team[j] + nseg * TG;
-          if (TM > J.maxM) J.maxM = TM;
-        } else {
-          KLAUNCH(k_tree_sum<F>, dim3(nblk((size_t)nseg * TG, 256)), dim3(256), 0, t2, tr.in, o, nseg, tr.n, TM);
-        }
-        tr.in = o; tr.n = TG; tr.pp ^= 1;
-      }
-      if (J.njobs) KLAUNCH(k_tree_sum_team_multi<F>, dim3(nblk((size_t)J.first_team[J.njobs] * TEAM, 256)), dim3(256), TEAM_LDS(256), t2, J);
-      LAUNCHCHK();
-      return BLSGPU_OK;
-    };
-    while (nn > 1) {
-      int M = nn >= 8 ? 8 : nn;
-      int G = nn / M;
-      u32* Rout = sl.lvlR[cur].template as<u32>();
-      u32* Tout = sl.lvlT.template as<u32>() + toff * PW;
-      // a level with a single group writes its T straight into the Horner table
-      if (G == 1) Tout = tstore + (size_t)level * nseg * PW;
-      // the two running sums of a chain (R and T) advance on two teams / two lanes, T one step behind R: M + 1 dependent
-      // additions per level instead of 2 M
-      if ((size_t)nseg * G * 2 * TEAM <= TEAM_LANES_MAX)
-        KLAUNCH(k_wsum_level_team2<F>, dim3(nblk((size_t)nseg * G * 2 * TEAM, 256)), dim3(256),
-                           TEAM_LDS(256) + (size_t)(256 / TEAM / 2) * 3 * TeamTraits<F>::WORDS * 4, tt, E, Rout, Tout, nseg, nn, M, off);
-      else if ((size_t)nseg * G * TEAM <= TEAM_LANES_MAX)
-        KLAUNCH(k_wsum_level_team<F>, dim3(nblk((size_t)nseg * G * TEAM, 256)), dim3(256), TEAM_LDS(256), tt, E, Rout, Tout, nseg, nn, M, off);
-      else if constexpr (GroupTag<F>::id == 2)
-        KLAUNCH(k_wsum_level_g2pair, dim3(nblk((size_t)nseg * G * 2, 256)), dim3(256), 0, tt, E, Rout, Tout, nseg, nn, M, off);
-      else
-        KLAUNCH(k_wsum_level_pair, dim3(nblk((size_t)nseg * G * 2, BLS_WSUM_BLOCK)), dim3(BLS_WSUM_BLOCK), 0, tt, E, Rout, Tout, nseg, nn, M, off);
-      LAUNCHCHK();
-      // sum the G T-records of each window down to one -- on the second tail stream: the next level needs only Rout.  Level l
-      // needs log8(G_l) passes; after every level ONE launch carries the next pass of every tree that still has one (the T
-      // trees of different levels are independent), so the trees finish while the R chain is still running.
-      if (G > 1) {
-        if (level < 8) {
-          if (t2 != tt) { HIPCHK(hipEventRecord(sl.ev_lvl[level], tt)); HIPCHK(hipStreamWaitEvent(t2, sl.ev_lvl[level], 0)); }
-          trees.push_back({Tout, G, 0, level, toff});
-        } else {
-          // (never reached with windows <= 16 bits: more than eight levels)  plain sequential tree on the tail stream
-          const u32* Tin = Tout; int tn = G, tc = 0;
-          while (tn > 1) {
-            int TM = tn >= 8 ? 8 : tn; int TG = (tn + TM - 1) / TM;
-            u32* o = TG == 1 ? tstore + (size_t)level * nseg * PW : sl.tsum[tc].template as<u32>() + toff * PW;
-            KLAUNCH(k_tree_sum<F>, dim3(nblk((size_t)nseg * TG, 256)), dim3(256), 0, tt, Tin, o, nseg, tn, TM);
-            LAUNCHCHK();
-            Tin = o; tn = TG; tc ^= 1;
-          }
-        }
-      }
-      tree_step();
-      toff += (size_t)nseg * G;
-      Ms.push_back(M);
-      E = Rout; nn = G; off = 0; cur ^= 1; level++;
-      if (level >= 31) return bad("msm: reduction depth");
-    }
-    for (bool more = true; more;) {                    // passes that are left when the last level has run
-      more = false;
-      for (auto& tr : trees) more |= tr.n > 1;
-      if (more) tree_step();
-    }
-    if (t2 != tt) { HIPCHK(hipEventRecord(sl.ev_tree, t2)); HIPCHK(hipStreamWaitEvent(tt, sl.ev_tree, 0)); }
-    if (level == 0) {
-      // a single bucket per window (c = 1): the bucket itself is the window sum
-      HIPCHK(hipMemcpyAsync(sl.wsums.p, records, (size_t)nseg * PW * 4, hipMemcpyDeviceToDevice, tt));
-    } else {
-      // Horner over the levels: acc_L = T_L ; acc_l = T_l + M_l * acc_{l+1}
-      u32* accbuf = sl.wacc[1].template as<u32>();
-      HIPCHK(hipMemcpyAsync(accbuf, tstore + (size_t)(level - 1) * nseg * PW, (size_t)nseg * PW * 4, hipMemcpyDeviceToDevice, tt));
-      for (int l = level - 2; l >= 0; l--) {
-        int k = 0; while ((1 << k) < Ms[l]) k++;
-        KLAUNCH(k_shift_add_team<F>, dim3(nblk((size_t)nseg * TEAM, 256)), dim3(256), TEAM_LDS(256), tt, accbuf, tstore + (size_t)l * nseg * PW, accbuf, nseg, k);
-        LAUNCHCHK();
-      }
-      HIPCHK(hipMemcpyAsync(sl.wsums.p, accbuf, (size_t)nseg * PW * 4, hipMemcpyDeviceToDevice, tt));
-    }
-  }
-  if (prof) hipEventRecord(c->ev[6], gtt);
-  // 7. combine windows
-  KLAUNCH(k_msm_combine_team<F>, dim3(1), dim3(TEAM), TEAM_LDS(TEAM), gtt, gs.wsums.as<u32>(), gs.result.as<u32>(), ng, cw);
-  LAUNCHCHK();
-  if (last) {
-    KLAUNCH(k_proj_export<F>, dim3(1), dim3(256), 0, gtt, gs.result.as<u32>(), (u32*)d_out_wire, (size_t)1);
-    LAUNCHCHK();
-  }
-  if (prof) hipEventRecord(c->ev[7], gtt);
-  HIPCHK(hipEventRecord(gs.ev_tail, gtt));
-  gs.tail_pending = true;
-  gs.seq = c->msm_calls + 1;
-  return BLSGPU_OK;
-  };
-  // pipelined calls accumulate on the library's own stream: front(i+1) must not queue behind accumulate(i)
-  hipStream_t as = c->pipelining ? c->acc_stream : st;
-  {
-    int rc = run_group(sl, 0, nseg, ft, as, tt, sl.tail2, true);
-    if (rc) return rc;
-  }
-  ++c->msm_calls;
-  if (!c->pipelining && tt != st) HIPCHK(hipStreamWaitEvent(st, sl.ev_tail, 0));    // in-order semantics on the caller's stream
-  if (prof) {
+  if (int rc = s.fast_sort ? msm_sort_fast(c, sl, s, d_scalars, (u32)bases->n, ft) : msm_sort_fallback(c, sl, s, d_scalars, ft)) return rc;
+  // ---- accumulate, reduce, combine: all windows of the call at once (cutting a single call into a high and a low window group whose
+  // tails overlap was measured in round 4 and is slower, tools/experiments/msm_window_groups.patch) -------------------------------------
+  if (int rc = msm_accumulate<F>(c, bases, first, sl, s, ft, as)) return rc;
+  msm_mark(c, 5, as);
+  if (tt != as) { HIPCHK(hipEventRecord(sl.ev_acc, as)); HIPCHK(hipStreamWaitEvent(tt, sl.ev_acc, 0)); }
+  if (int rc = msm_reduce<F>(sl, red, tt, t2)) return rc;
+  msm_mark(c, 6, tt);
+  if (int rc = msm_combine<F>(sl, s, d_out_wire, tt)) return rc;
+  msm_mark(c, 7, tt);
+  // ---- bookkeeping ---------------------------------------------------------------------------------------------------------------------
+  HIPCHK(hipEventRecord(sl.ev_tail, tt));
+  sl.tail_pending = true;
+  sl.seq = ++c->msm_calls;
+  if (c->profiling) {
     HIPCHK(hipStreamSynchronize(tt));
     HIPCHK(hipStreamSynchronize(st));
     for (int i = 0; i < 7; i++) hipEventElapsedTime(&c->phase_ms[i], c->ev[i], c->ev[i + 1]);

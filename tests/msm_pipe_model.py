@@ -13,7 +13,7 @@ HEAVY_SMALL = 16                 # msm.hip.h
 HEAVY_BIG_BLOCKS = 512           # msm.hip.h
 WINDOW_RANGE = (4, 16)           # api_ctx.hip blsgpu_set_msm_window
 TABLE_WINDOW_RANGE = (9, 21)     # api_msm.hip blsgpu_bases_precompute
-SBITS = {8: 256, 4: 128, 2: 64}  # api_msm.hip msm_device: the width the windows cover, by words per sort scalar
+SBITS = {8: 256, 4: 128, 2: 64}  # msm_plan.h msm_shape: the width the windows cover, by words per sort scalar
 
 
 def recode(v, c, nwin, words=8):
@@ -66,7 +66,7 @@ def offsets(buckets):
 
 
 def sort_split(c, nwin, merged=False):
-    """api_msm.hip msm_device: (fine_bits, ncoarse, nc) -- the key (window, |digit| - 1) is cut into a coarse part that counts in
+    """msm_plan.h msm_sort_split: (fine_bits, ncoarse, nc) -- the key (window, |digit| - 1) is cut into a coarse part that counts in
     LDS (nc = bucket sets * ncoarse counters) and a fine part of at most 7 bits"""
     key_bits = c - 1
     coarse_bits = (key_bits - 7 if key_bits > 7 else 0) if merged else min(key_bits, 8)
@@ -101,7 +101,7 @@ def item_partition(offs, cap):
 
 
 def item_cap(ns, c, forced=0):
-    """api_msm.hip msm_device: ~4x the mean bucket load, a power of two in [128, ITEM_CAP_MAX]"""
+    """msm_plan.h msm_shape: ~4x the mean bucket load, a power of two in [128, ITEM_CAP_MAX]"""
     if forced:
         return forced
     cap = 128
@@ -136,6 +136,112 @@ def window_sum(E):
         acc = T + M * acc
     # Horner: acc_l = T_l + M_l * acc_{l+1}, the top level's M multiplies nothing
     return want, (acc if ts else E[0])
+
+
+# ---- the launch plan (csrc/msm_plan.h), restated from its description; tests/test_msm_plan.py compares the two ---------------------
+TEAM = 8                         # team.hip.h
+TEAM_LANES_MAX = 131072          # msm_plan.h
+TREE_JOBS_MAX = 8                # msm.hip.h
+REDUCTION_BLOCK = 256            # threads per block of the level, tree and shift-add launches
+
+
+def pick_window(n, bits):
+    """msm_plan.h msm_pick_window: the c in 6..16 (the smallest on a tie) that minimises n W + 2.4 W 2^(c-1), W = ceil(bits / c) -- in
+    integers, five times the cost"""
+    return min(range(6, 17), key=lambda c: (-(-bits // c) * (5 * n + 12 * (1 << (c - 1))), c))
+
+
+def reduction_schedule(nseg, nbw):
+    """msm_plan.h msm_reduction: the reduction of nseg windows of nbw bucket records each.
+    levels: per level n, M = min(8, n), G = n / M, off (1 at the bottom, 0 above), form, grid, toff (records of T before this level)
+    and horner (G == 1: T is the level's Horner row).  steps: after every level one pass of every unfinished T tree (a level with
+    G > 1 starts one), then passes until none is left: per step (jobs of the multi launch, its grid, passes); a pass is (level, n, TM,
+    TG, src, pp, horner, multi, off) with src -1 = the level's T block, else the ping-pong buffer it reads.  horner: the shifts
+    log2(M_l) for l = levels - 2 .. 0."""
+    levels, steps, trees = [], [], []
+
+    def step():
+        passes, jobs, teams = [], 0, 0
+        for tr in trees:
+            if tr["n"] <= 1:
+                continue
+            tm = min(8, tr["n"])
+            tg = -(-tr["n"] // tm)
+            multi = nseg * tg * TEAM <= TEAM_LANES_MAX and jobs < TREE_JOBS_MAX
+            if multi:
+                jobs += 1
+                teams += nseg * tg
+            passes.append((tr["level"], tr["n"], tm, tg, tr["src"], tr["pp"], tg == 1, multi, tr["off"]))
+            tr["src"], tr["n"], tr["pp"] = tr["pp"], tg, tr["pp"] ^ 1
+        steps.append((jobs, -(-teams * TEAM // REDUCTION_BLOCK), passes))
+        return bool(passes)
+
+    n, off, toff = nbw, 1, 0
+    while n > 1:
+        m = min(8, n)
+        g = n // m
+        if nseg * g * 2 * TEAM <= TEAM_LANES_MAX:
+            form, lanes = 0, nseg * g * 2 * TEAM
+        elif nseg * g * TEAM <= TEAM_LANES_MAX:
+            form, lanes = 1, nseg * g * TEAM
+        else:
+            form, lanes = 2, nseg * g * 2
+        levels.append({"n": n, "M": m, "G": g, "off": off, "form": form, "grid": -(-lanes // REDUCTION_BLOCK), "toff": toff, "horner": g == 1})
+        if g > 1:
+            trees.append({"level": len(levels) - 1, "n": g, "src": -1, "pp": 0, "off": toff})
+        step()
+        toff += nseg * g
+        n, off = g, 0
+    while step():
+        pass
+    steps.pop()                                                     # the step that found nothing to do
+    return {"levels": levels, "steps": steps, "horner": [lv["M"].bit_length() - 1 for lv in reversed(levels[:-1])]}
+
+
+def schedule_text(nseg, nbw):
+    """the schedule in the text form of tests/cpp/msm_plan_main.cpp"""
+    s = reduction_schedule(nseg, nbw)
+    out = "sched nseg=%d nbw=%d levels=%d nsteps=%d :" % (nseg, nbw, len(s["levels"]), len(s["steps"]))
+    for lv in s["levels"]:
+        out += " L%d,%d,%d,%d,%d,%d,%d,%d" % (lv["n"], lv["M"], lv["G"], lv["off"], lv["form"], lv["grid"], lv["toff"], lv["horner"])
+    out += " :"
+    for jobs, grid, passes in s["steps"]:
+        out += " S%d,%d" % (jobs, grid) + "".join("/%d,%d,%d,%d,%d,%d,%d,%d,%d" % p for p in passes)
+    return out + " : H" + "".join(" %d" % k for k in s["horner"])
+
+
+def launch_counts(group, words, c, merged=False, fast_sort=True, mont=False):
+    """kernel name -> launches of ONE msm call, as kernel_timing_report() names them: group 1 / 2, words per sort scalar (8 plain, 4
+    GLV halves, 2 psi digits), window c; mont: Montgomery scalars without a decomposition kernel in front"""
+    nwin = nwin_of(c, words)
+    s = reduction_schedule(1 if merged else nwin, 1 << (c - 1))
+    k = {}
+
+    def add(name, count=1):
+        if count:
+            k[name] = k.get(name, 0) + count
+    if words == 8 and mont:
+        add("k_scalars_from_mont")
+    if words != 8:
+        add("k_glv_decompose" if words == 4 else "k_gls_decompose")
+    if fast_sort:
+        for name in ("k_sort_hist<%d>" % words, "k_sort_scan", "k_sort_scatter<%d>" % words, "k_sort_fine"):
+            add(name)
+    else:
+        for name in ("k_msm_digits", "k_scan_block_sums", "k_scan_top", "k_scan_apply", "k_msm_scatter"):
+            add(name)
+    for name in ("k_item_count", "k_item_scan", "k_item_fill", "k_msm_accumulate<F>" if group == 1 else "k_msm_accumulate_g2pair", "k_msm_heavy<F>"):
+        add(name)
+    pair = "k_wsum_level_pair" if group == 1 else "k_wsum_level_g2pair"
+    for lv in s["levels"]:
+        add(("k_wsum_level_team2<F>", "k_wsum_level_team<F>", pair)[lv["form"]])
+    for jobs, _, passes in s["steps"]:
+        add("k_tree_sum_team_multi<F>", 1 if jobs else 0)
+        add("k_tree_sum<F>", sum(1 for p in passes if not p[7]))
+    add("k_shift_add_team<F>", len(s["horner"]))
+    add("k_msm_combine_team<F>")
+    add("k_proj_export<F>")
+    return k
 
 
 # ---- scalars with prescribed digits (tests/test_msm_pipeline_gpu.py) -----------------------------------------------------------

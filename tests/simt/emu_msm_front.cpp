@@ -1,7 +1,8 @@
 // tests/simt/emu_msm_front.cpp -- the integer front end of the large MSM (bls12_381_amd/csrc/msm.hip.h) compiled for the HOST (test
 // infrastructure only): the two-level counting sort, the fallback sort and the work-item kernels.  The entry points launch the
-// __global__ functions themselves with the grid, block and dynamic-LDS shapes of api_msm.hip msm_device (restated below, each with the
-// lines it restates), one stage per entry point: the tests hand every stage inputs of their own (tests/test_simt_msm_front.py).
+// __global__ functions themselves with the grid, block and dynamic-LDS shapes of api_msm.hip (msm_sort_fast, msm_sort_fallback,
+// msm_accumulate; the key split is the one of csrc/msm_plan.h), one stage per entry point: the tests hand every stage inputs of their
+// own (tests/test_simt_msm_front.py).
 //
 // A library of its own because k_sort_scan and k_scan_top run 1024 lanes and k_sort_fine runs up to 8192 workgroups.  With the lane
 // pool of emu_harness.h (one host thread per lane) that was measured at 28 s for ONE sort with 7424 counters: every workgroup wakes
@@ -11,7 +12,7 @@
 // EMU_SYNCTHREADS_HOOK).  The interleaving is one of those the GPU may produce; LDS and global atomics keep their meaning.  Its limit:
 // between two barriers lane l always runs before lane l + 1, so a MISSING barrier whose producer is the lower lane is not seen.  The
 // trapping checks, launch_loop and emu_guarded() are those of tests/simt/emu_harness.h; the tests call this library from a child
-// process (tests/simt_msm_front_child.py), which places every buffer, at exactly the size api_msm.hip computes for it, flush
+// process (tests/simt_msm_front_child.py), which places every buffer, at exactly the size msm_plan.h msm_sizes gives for it, flush
 // against an inaccessible page.
 //
 // Not checked here: the dynamic LDS of the emulation is one fixed array (EMU_DYN_LDS_WORDS = 16384 words, the 2 * SORT_MAX_COUNTERS
@@ -34,6 +35,7 @@ asm(".text\n.hidden emu_switch\n.globl emu_switch\n.type emu_switch,@function\ne
     ".size emu_switch, .-emu_switch\n");
 
 #include "msm.hip.h"
+#include "msm_plan.h"
 
 using namespace bls;
 
@@ -88,16 +90,11 @@ template <class Fn> void launch_fibers(unsigned grid, unsigned block, Fn fn) {
   g_in_fibers = false;
 }
 
-// api_msm.hip msm_device (:270-274): the split of the (window, |digit| - 1) key
-struct Split { int fine_bits, ncoarse, nc; };
-Split split_of(int cw, int nwin, int merged) {
-  const int key_bits = cw - 1;
-  const int coarse_bits = merged ? (key_bits > 7 ? key_bits - 7 : 0) : (key_bits < 8 ? key_bits : 8);
-  const int nseg = merged ? 1 : nwin;
-  return {key_bits - coarse_bits, 1 << coarse_bits, nseg * (1 << coarse_bits)};
-}
+// msm_plan.h: the split of the (bucket set, |digit| - 1) key, as msm_shape takes it
+typedef MsmSortSplit Split;
+Split split_of(int cw, int nwin, int merged) { return msm_sort_split(cw, merged ? 1 : nwin, merged != 0); }
 
-// api_msm.hip :349-355, :363-368: the hist and scatter launches by words per sort scalar
+// api_msm.hip msm_sort_fast: the hist and scatter launches by words per sort scalar
 template <int WORDS>
 void hist(const u32* in, u32* ghist, int ns, int cw, int nwin, const Split& s, int merged, u32* status) {
   launch_fibers(nblk(ns, SORT_TILE), SORT_THREADS, [=] { k_sort_hist<WORDS>(in, ghist, ns, cw, nwin, s.fine_bits, s.ncoarse, merged, status); });
@@ -122,15 +119,15 @@ int emu_front_constants(int which) {
   const int v[] = {SORT_TILE, SORT_THREADS, SORT_MAX_COUNTERS, ITEM_CAP_MAX, ITEM_BINS, ITEM_BLOCK_BUCKETS, HEAVY_SMALL, HEAVY_BIG_BLOCKS, (int)sizeof(ItemDesc), (int)sizeof(uint4)};
   return v[which];
 }
-// the counters the sort needs, or -1 where api_msm.hip :275 refuses the configuration
+// the counters the sort needs, or -1 where msm_plan.h msm_shape refuses the configuration (the counter table)
 int emu_sort_counters(int cw, int nwin, int merged) {
   const int nc = split_of(cw, nwin, merged).nc;
   return nc > SORT_MAX_COUNTERS ? -1 : nc;
 }
 
-// api_msm.hip :340-369, the two-level counting sort.  hist: the slot's counter buffer of 3 * SORT_MAX_COUNTERS + 4 words in the fixed
-// layout [MAX] counts | [MAX + 1] bases | [MAX] cursors (:290, :340-342), counts zero on entry as the product keeps them;
-// words: 8 (plain, merged allowed), 4 (GLV halves), 2 (psi digits); stride: bases->n with resident tables, else 0 (:363-368)
+// api_msm.hip msm_sort_fast, the two-level counting sort.  hist: the slot's counter buffer of 3 * SORT_MAX_COUNTERS + 4 words in the fixed
+// layout [MAX] counts | [MAX + 1] bases | [MAX] cursors (msm_sizes hist), counts zero on entry as the product keeps them;
+// words: 8 (plain, merged allowed), 4 (GLV halves), 2 (psi digits); stride: bases->n with resident tables, else 0
 void emu_sort_fast(int words, const u32* in, int ns, int cw, int nwin, int merged, u32 stride, u32* hist_buf, u32* ctrl, u32* ent, u32* sorted, u32* offs, u32* status) {
   const Split s = split_of(cw, nwin, merged);
   u32* ghist = hist_buf;
@@ -139,17 +136,15 @@ void emu_sort_fast(int words, const u32* in, int ns, int cw, int nwin, int merge
   if (words == 4) hist<4>(in, ghist, ns, cw, nwin, s, 0, status);
   else if (words == 2) hist<2>(in, ghist, ns, cw, nwin, s, 0, status);
   else hist<8>(in, ghist, ns, cw, nwin, s, merged ? 1 : 0, status);
-  // :359
   launch_fibers(1, 1024, [=] { k_sort_scan(ghist, gbase, gcur, s.nc, ctrl, 4 + 2 * ITEM_BINS); });
   if (words == 4) scatter<4>(in, gbase, gcur, ent, ns, cw, nwin, s, 0, 0);
   else if (words == 2) scatter<2>(in, gbase, gcur, ent, ns, cw, nwin, s, 0, 0);
   else scatter<8>(in, gbase, gcur, ent, ns, cw, nwin, s, merged ? 1 : 0, stride);
-  // :369
   launch_fibers(s.nc, 256, [=] { k_sort_fine(ent, gbase, sorted, offs, s.fine_bits, s.nc); });
 }
 
-// api_msm.hip :373-391, the fallback sort over n 256-bit scalars.  hist: nb words, zero on entry (:375; the product's buffer is larger,
-// but only these are cleared), bsum: 4096 words (:302), ent / rank / sorted: total = nwin * n words each
+// api_msm.hip msm_sort_fallback, the fallback sort over n 256-bit scalars.  hist: nb words, zero on entry (the product's buffer is
+// larger, but only these are cleared), bsum: 4096 words (msm_sizes bsum), ent / rank / sorted: total = nwin * n words each
 void emu_sort_fallback(const u32* in, int n, int cw, int nwin, u32* hist_buf, u32* bsum, u32* ent, u32* rank, u32* offs, u32* sorted, u32* status) {
   const size_t nb = (size_t)nwin << (cw - 1), total = (size_t)nwin * n;
   launch_loop(nblk(n, 256), 256, [=] { k_msm_digits(in, ent, rank, hist_buf, n, cw, nwin, status); });
@@ -160,7 +155,8 @@ void emu_sort_fallback(const u32* in, int n, int cw, int nwin, u32* hist_buf, u3
   launch_loop(nblk(total, 256), 256, [=] { k_msm_scatter(ent, rank, offs, sorted, n, total); });
 }
 
-// api_msm.hip :404-411, the work items of gnb buckets.  ctrl: 4 + 2 * ITEM_BINS words, zero on entry (k_sort_scan / :376 clear them)
+// api_msm.hip msm_accumulate, the work items of gnb buckets.  ctrl: 4 + 2 * ITEM_BINS words, zero on entry (k_sort_scan / the fallback
+// sort's memset clear them)
 void emu_items(const u32* offs, int gnb, u32 cap, u32* ctrl, u32* items, u32* heavy) {
   u32* bins = ctrl + 4;
   u32* bcur = ctrl + 4 + ITEM_BINS;

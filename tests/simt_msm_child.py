@@ -20,6 +20,8 @@ The point kernels of the large MSM, one stage per job (tests/test_simt_msm_point
   tree_multi  group, nseg, trees [(E, n, M)]                                        -> outs
   shift_add   group, x, y (nseg each), k                                            -> out
   combine     group, wsums (nwin), c                                                -> out (1)
+  reduce      group, records (nseg * nbw), nseg, nbw, [fault]                       -> wsums (nseg), levels: the whole reduction by the
+              schedule of csrc/msm_plan.h, in buffers of the sizes of msm_sizes
 Test infrastructure only: the product never imports this file."""
 import ctypes
 
@@ -215,7 +217,7 @@ class _Child(simt_harness.Child):
         g = int(j["group"])
         rx, px, n = self.recs(g, j["x"])
         _, py, _ = self.recs(g, j["y"])
-        self.lib.emu_shift_add(g, px, py, px, n, int(j["k"]))       # in place, as api_msm.hip :536 runs it (accbuf is x and out)
+        self.lib.emu_shift_add(g, px, py, px, n, int(j["k"]))       # in place, as api_msm.hip msm_reduce runs it (accbuf is x and out)
         return {"out": self.wire(g, rx, n)}
 
     def combine(self, j):
@@ -224,6 +226,19 @@ class _Child(simt_harness.Child):
         o, po = self.empty(g, 1)
         self.lib.emu_msm_combine(g, pw, po, n, int(j["c"]))
         return {"out": self.wire(g, o, 1)}
+
+    def reduce(self, j):
+        g, nseg, nbw = int(j["group"]), int(j["nseg"]), int(j["nbw"])
+        _, prec, n = self.recs(g, j["records"])
+        assert n == nseg * nbw
+        words = (ctypes.c_size_t * 5)()
+        self.lib.emu_msm_reduce_words(g, nseg, ctypes.c_uint32(nbw), words)
+        pair = lambda w: (ctypes.c_void_p * 2)(self.buf(w, fill=0xffffffff)[1].value, self.buf(w, fill=0xffffffff)[1].value)
+        lvlR, (_, plvlT), tsum, wacc = pair(words[0]), self.buf(words[1], fill=0xffffffff), pair(words[2]), pair(words[3])
+        assert words[4] == nseg * PROJ_WORDS[g]
+        ws, pws = self.empty(g, nseg)
+        levels = self.lib.emu_msm_reduce(g, prec, nseg, ctypes.c_uint32(nbw), lvlR, plvlT, tsum, wacc, pws, int(j.get("fault", 0)))
+        return {"wsums": self.wire(g, ws, nseg), "levels": int(levels)}
 
 
 if __name__ == "__main__":

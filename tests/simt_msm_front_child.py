@@ -2,15 +2,15 @@
 (tests/test_simt_msm_front.py), over tests/simt_harness.py: trapping bounds / shift checks, every buffer flush against an
 inaccessible page, a crash or a time-out becomes a pytest failure that names the job.
 
-Every buffer a kernel reads or writes has exactly the size api_msm.hip msm_device computes for it -- none of the `bytes / 8 + 256` slack
-of DevBuf::reserve (host.h), in which an entry written a little past the end changes nothing on the GPU:
-  ent / sorted / rank   total * 4 bytes, total = nwin * ns                                                      (:287-288, :295)
-  hist                  (3 * SORT_MAX_COUNTERS + 4) * 4 for the fast sort; nb * 4 for the fallback (what :375 clears)   (:290)
-  offs                  (nb + 1) * 4                                                                            (:301)
-  bsum                  4096 * 4                                                                                (:302)
-  items                 max_items * sizeof(ItemDesc), max_items = total / cap + nb + 1                          (:307, :311)
-  heavy                 2 * nb * sizeof(uint4)                                                                  (:312)
-  ctrl                  (4 + 2 * ITEM_BINS) * 4                                                                 (:313)
+Every buffer a kernel reads or writes has exactly the size csrc/msm_plan.h msm_sizes gives for it (the field in brackets) -- none of the
+`bytes / 8 + 256` slack of DevBuf::reserve (host.h), in which an entry written a little past the end changes nothing on the GPU:
+  ent / sorted / rank   total * 4 bytes, total = nwin * ns                                              (ent, sorted, cursor)
+  hist                  (3 * SORT_MAX_COUNTERS + 4) * 4 for the fast sort; nb * 4 for the fallback (what msm_sort_fallback clears)   (hist)
+  offs                  (nb + 1) * 4                                                                    (offs)
+  bsum                  4096 * 4                                                                        (bsum)
+  items                 max_items * sizeof(ItemDesc), max_items = total / cap + nb + 1                  (MsmShape max_items; items)
+  heavy                 2 * nb * sizeof(uint4)                                                          (heavy)
+  ctrl                  (4 + 2 * ITEM_BINS) * 4                                                         (ctrl)
 
 A job is a dict with "op" and "label":
   state     (none)                                                  -> fresh sort state for the jobs after it (hist zeroed once, as at allocation)

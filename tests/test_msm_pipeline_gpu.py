@@ -304,3 +304,45 @@ def test_dense_uniform_pipelined_across_window_changes(env, group):
                 assert _got(ctx, group, out) == _want(group, _dot(env.ks[group], s)), c
     finally:
         ctx.set_msm_window(0)
+
+
+# ---- launch plan ---------------------------------------------------------------------------------------------------------------
+# (label, group, context, n, forced window, table window, words per sort scalar)
+PLAN_SHAPES = [("g1 default", 1, "default", 256, 0, 0, 4), ("g2 default", 2, "default", 64, 0, 0, 2), ("g1 window 16", 1, "default", 4096, 16, 0, 4),
+               ("g1 tables 9", 1, "default", 256, 0, 9, 8), ("g1 plain", 1, "plain", 256, 0, 0, 8)]
+
+
+def plan_shape_launches(label):
+    """what tests/msm_pipe_model.py predicts for one call of a PLAN_SHAPES case: kernel name -> launches"""
+    _, group, _, n, window, table, words = next(s for s in PLAN_SHAPES if s[0] == label)
+    c = table or window or mm.pick_window(n * (8 // words), mm.SBITS[words])
+    return mm.launch_counts(group, words, c, merged=bool(table))
+
+
+@gpu
+def test_launches_follow_the_plan(env):
+    """one call per shape with kernel timing on: the result against the oracle, and the launches of kernel_timing_report() against the
+    counts the model derives from the plan (csrc/msm_plan.h through tests/msm_pipe_model.py launch_counts): the sort kernels of the
+    path taken, three item kernels, one accumulation, one fold, the level launches by form, one multi-job tree launch per step that
+    has a pass, the shift-adds, one combine and one export.  `g1 window 16` has five levels, four of them with a tree."""
+    assert [lv["G"] > 1 for lv in mm.reduction_schedule(8, 1 << 15)["levels"]] == [True] * 4 + [False]
+    for label, group, ctx_name, n, window, table, _ in PLAN_SHAPES:
+        ctx = env.ctx[ctx_name]
+        ks = env.ks[group][:n]
+        ss = [int(x) for x in _uniform(group, 9)[0][:n]]
+        bases = ctx.bases_from_scalars(group, ks)
+        try:
+            if table:
+                bases.precompute(table)
+            ctx.set_msm_window(window)
+            ctx.synchronize()
+            ctx.kernel_timing(True)
+            ctx.kernel_timing_report()
+            out = ctx.msm(bases, _bytes(ss))
+            report = ctx.kernel_timing_report()
+        finally:
+            ctx.kernel_timing(False)
+            ctx.set_msm_window(0)
+            bases.free()
+        assert _got(ctx, group, out) == _want(group, _dot(ks, ss)), label
+        assert {k: v["launches"] for k, v in report.items()} == plan_shape_launches(label), label

@@ -14,8 +14,10 @@ The rest of the large MSM runs on the host stage by stage, each stage on inputs 
 tests/msm_pipe_model.py: the integer front end -- `k_sort_*`, the fallback sort (`k_msm_digits`, `k_scan_*`, `k_msm_scatter`) and
 `k_item_*` -- in tests/test_simt_msm_front.py (tests/simt/emu_msm_front.cpp); the point kernels behind it -- `k_msm_accumulate_g2pair`,
 `k_msm_heavy`, the four `k_wsum_level_*` forms, `k_tree_sum*`, `k_shift_add_team`, `k_msm_combine_team` -- in
-tests/test_simt_msm_points.py (this library).  NOT covered on the host: the driver logic of api_msm.hip (`run_group`) and the DPP
-modifiers the emulation ignores; tests/test_msm_pipeline_gpu.py covers both on the GPU with every bucket of every window filled.
+tests/test_simt_msm_points.py (this library), which also walks the whole bucket reduction by the schedule of csrc/msm_plan.h as
+api_msm.hip `msm_reduce` does.  The launch decisions of `msm_device` are plain host code (csrc/msm_plan.h, tests/test_msm_plan.py).
+NOT covered on the host: the streams, events and slot hand-over of `msm_device` and the DPP modifiers the emulation ignores;
+tests/test_msm_pipeline_gpu.py covers both on the GPU with every bucket of every window filled.
 
 That the tests bite was checked by seeding faults into the device headers one at a time: no carry in DigitIter::next
 (test_signed_recoding_carries, test_window_sums), sub2 flipped in glv_split / a sign flipped in gls_split

@@ -52,7 +52,7 @@ def test_model_restates_the_product_constants():
 
 
 def test_no_accepted_window_exceeds_the_counter_table():
-    """api_msm.hip :275 refuses nc > SORT_MAX_COUNTERS, but no window blsgpu_set_msm_window (4..16) or blsgpu_bases_precompute
+    """msm_plan.h msm_shape refuses nc > SORT_MAX_COUNTERS, but no window blsgpu_set_msm_window (4..16) or blsgpu_bases_precompute
     (9..21) accepts gets there: the largest unmerged table is 29 x 256 = 7424 counters (plain scalars, c = 9), the largest merged one
     8192 (c = 21).  A later change of the window limits trips this."""
     t = mm.counter_tables()

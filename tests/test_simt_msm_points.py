@@ -1,7 +1,8 @@
 """The point kernels behind the sort of the large MSM -- `k_msm_accumulate_g2pair`, `k_msm_heavy<F>`, the level forms
 `k_wsum_level_team2` / `_team` / `_pair` / `_g2pair`, `k_tree_sum<F>`, `k_tree_sum_team_multi<F>`, `k_shift_add_team<F>` and
 `k_msm_combine_team<F>` -- compiled for the HOST (tests/simt/emu_msm.cpp) and run ONE STAGE AT A TIME on hand-built records, with the
-grid, block and LDS shapes of api_msm.hip.  Every record is [e] G for a known exponent e, so every expectation is the oracle's
+grid and block shapes of api_msm.hip, and the whole bucket reduction by the schedule of csrc/msm_plan.h (`test_whole_reduction`: the
+driver logic of api_msm.hip msm_reduce -- levels, tree steps, Horner -- on the host).  Every record is [e] G for a known exponent e, so every expectation is the oracle's
 [f(e ...)] G by exponent arithmetic (`_gen_multiples`, the C oracle's double-and-add) with the level sums of tests/msm_pipe_model.py;
 results are compared as affine points.  Every record buffer holds exactly the records the stage may touch and ends against an
 inaccessible page: a read or write past the last record, which DevBuf's slack swallows on the GPU, ends the child process.
@@ -18,6 +19,8 @@ Seeded faults (msm.hip.h on a scratch copy, one at a time) and the test that fai
                                                  records).  Under tree_step's own rule M = min(8, n) a job with M < maxM has n = M, so
                                                  `i < n` implies `k < M` and the fault cannot show: the first version of the test, which
                                                  restated that rule only, let it pass.
+  `off = 0` at the bottom level of the schedule  test_whole_reduction (seeded through the entry point's `fault` argument: every window
+                                                 sum misses sum_b e_b)
 
 Cost: about 25 s (one run on one machine, the library already built) where tests/test_simt_msm.py takes 170 s.
 """
@@ -171,12 +174,13 @@ def test_tree_sums(group):
     """`k_tree_sum_team_multi` with 1, 3 and 8 trees per launch, fan-ins that differ inside a launch (maxM = 8 next to M = 1, 2, 3), n no
     multiple of M (n = 9, M = 8), nseg 1..3; `k_tree_sum` on the same trees.
 
-    Reachability of the one-lane `k_tree_sum`, by reading api_msm.hip tree_step (:464): a tree joins the multi-job launch when
+    Reachability of the one-lane `k_tree_sum`, by reading msm_plan.h msm_reduction (MsmTreePass::multi): a tree joins the multi-job launch when
     nseg * TG * TEAM <= TEAM_LANES_MAX and fewer than TREE_JOBS_MAX trees are in it.  TG <= 2^(c-1) / 64 (the first pass of the bottom
     level's T records) and nseg <= ceil(256 / c), so nseg * TG * 8 <= 16 * 512 * 8 = 65536 at c = 16 unmerged and 1 * 16384 * 8 = 131072
     at c = 21 merged: never above the limit.  A level adds a tree only while G > 1, which takes levels 0 .. 5 at most (2^20 buckets,
-    fan 8), so there are never 8 trees, and `level < 8` always holds.  Both `k_tree_sum` launches (:469, :509) are therefore
-    unreachable with the windows the product accepts; the kernel is kept and tested here."""
+    fan 8), so there are never 8 trees.  The `k_tree_sum` launch of api_msm.hip msm_tree_step is therefore unreachable with the windows
+    the product accepts (tests/cpp/msm_plan_main.cpp holds the schedule of every accepted shape to that); the kernel is kept and tested
+    here."""
     # (n, M) per tree and nseg per launch; M = min(8, n) is tree_step's rule, the (9, 3) and (10, 2) trees use the kernel's wider contract
     sets = {1: (2, [(9, 8)]), 3: (1, [(9, 8), (2, 2), (64, 8)]), 8: (3, [(8, 8), (3, 3), (9, 8), (2, 2), (16, 8), (1, 1), (9, 3), (17, 8)])}
     if group == 2:
@@ -218,3 +222,31 @@ def test_shift_add_and_combine(group):
         wants.append([sum(e << (c * i) for i, e in enumerate(w))])
     for j, res, w in zip(jobs, child.run(jobs), wants):
         assert _affine(group, res["out"]) == _want(group, w), j["label"]
+
+
+# ---- A9 --------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nbw", [1 << 3, 1 << 7, 1 << 10])
+@pytest.mark.parametrize("group", GROUPS)
+def test_whole_reduction(group, nbw):
+    """the driver logic of api_msm.hip msm_reduce on the host: the schedule of msm_plan.h walked over records [e_b] G of nseg = 2 windows
+    -- every level in the form the plan picks, the tree passes of every step, the Horner shifts -- gives [sum_b (b + 1) e_b] G per
+    window.  nbw = 2^3: one level, no tree; 2^7: three levels, the bottom one with a tree; 2^10: four levels, trees of two passes.
+    Once more with the seeded fault (the bottom level runs with off = 0): the result must differ."""
+    nseg = 2
+    r = o.SplitMix64(0xA9 + nbw + group)
+    exps = [r.next() % 1000 + 1 for _ in range(nseg * nbw)]
+    for i in range(0, nseg * nbw, 7):
+        exps[i] = 0                                                  # empty buckets
+    want = [sum((b + 1) * e for b, e in enumerate(exps[s * nbw:(s + 1) * nbw])) for s in range(nseg)]
+    for s in range(nseg):
+        assert mm.window_sum(exps[s * nbw:(s + 1) * nbw]) == (want[s], want[s])
+    rec = _proj(group, exps)
+    jobs = [{"op": "reduce", "label": "nbw=%d" % nbw, "group": group, "records": rec, "nseg": nseg, "nbw": nbw}]
+    if nbw == 1 << 7:
+        jobs.append({"op": "reduce", "label": "nbw=%d, off = 0 at the bottom level" % nbw, "group": group, "records": rec, "nseg": nseg, "nbw": nbw, "fault": 1})
+    res = child.run(jobs)
+    assert res[0]["levels"] == len(mm.reduction_schedule(nseg, nbw)["levels"]) == {8: 1, 128: 3, 1024: 4}[nbw]
+    assert _affine(group, res[0]["wsums"]) == _want(group, want)
+    if len(jobs) > 1:
+        assert _affine(group, res[1]["wsums"]) != _want(group, want), "the seeded fault was not caught"
+        assert _affine(group, res[1]["wsums"]) == _want(group, [w - sum(exps[s * nbw:(s + 1) * nbw]) for s, w in enumerate(want)])
