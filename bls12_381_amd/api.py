@@ -637,6 +637,138 @@ class FrPoseidon:
             pass
 
 
+class FrEdwards:
+    """A twisted Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 over Fr (`blsgpu_fr_edwards`; Jubjub and Bandersnatch are such curves).  The
+    constants are the CALLER's: the library ships no parameter set.  Affine points are (n, 2, 4) u64 arrays of Montgomery limbs (or n
+    pairs of Python ints in [0, r)), results (n, 3, 4) arrays (X : Y : Z) whose representative is unspecified: compare after
+    normalize.  Scalars are plain 256-bit integers (Python ints or (n, 32) little-endian bytes), NOT Fr elements; `bits` in [1, 256]
+    says how many low bits are read.  On a curve that is not `complete` every input point must have odd order."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    @property
+    def complete(self):
+        """True exactly when a is a square and d is not: the addition law then has no exceptional case at all"""
+        return bool(self.ctx.lib.blsgpu_fr_edwards_complete(self.handle)) if self.handle else False
+
+    @staticmethod
+    def points(xy, what="fr_edwards"):
+        return _fr_limbs(xy, (-1, 2), what)
+
+    @staticmethod
+    def scalars(values, what="fr_edwards"):
+        """Python ints in [0, 2^256) or an array of 32 little-endian bytes each -> (n, 32) u8"""
+        if isinstance(values, np.ndarray):
+            return np.ascontiguousarray(values, dtype=np.uint8).reshape(-1, 32)
+        vals = [int(v) for v in values]
+        if any(v < 0 or v >> 256 for v in vals):
+            raise ValueError("%s: a scalar must be in [0, 2^256)" % what)
+        return np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+
+    def check(self, xy):
+        """ok[i] = 1 iff point i satisfies the curve equation (limbs >= r never do)"""
+        v = self.points(xy, "fr_edwards.check")
+        ok = np.zeros(v.shape[0], dtype=np.uint8)
+        check(self.ctx.lib.blsgpu_fr_edwards_check(self.ctx.h, self.handle, _ptr(v), v.shape[0], _ptr(ok)), "fr_edwards_check")
+        return ok
+
+    def normalize(self, xyz):
+        """(n, 3, 4) projective points -> ((n, 2, 4) affine points, ok): (0, 1) and ok = 0 where Z = 0"""
+        v = _u64(xyz, (-1, 3, 4)).copy()
+        xy = np.zeros((v.shape[0], 2, 4), dtype=np.uint64)
+        ok = np.zeros(v.shape[0], dtype=np.uint8)
+        check(self.ctx.lib.blsgpu_fr_edwards_normalize(self.ctx.h, self.handle, _ptr(v), v.shape[0], _ptr(xy), _ptr(ok)), "fr_edwards_normalize")
+        return xy, ok
+
+    def mul_batch(self, xy, scalars, bits=256):
+        """out[i] = scalars[i] * P_i for n independent pairs -> (n, 3, 4); the work depends on `bits` alone"""
+        v = self.points(xy, "fr_edwards.mul_batch")
+        k = self.scalars(scalars, "fr_edwards.mul_batch")
+        if k.shape[0] != v.shape[0]:
+            raise ValueError("fr_edwards.mul_batch: one scalar per point")
+        out = np.zeros((v.shape[0], 3, 4), dtype=np.uint64)
+        check(self.ctx.lib.blsgpu_fr_edwards_mul_batch(self.ctx.h, self.handle, _ptr(v), _ptr(k), int(bits), v.shape[0], _ptr(out)), "fr_edwards_mul_batch")
+        return out
+
+    def bases(self, xy, bits, window):
+        """a fixed-base table for the n bases xy: scalars of `bits` bits, signed windows of `window` in [2, 8] bits -> FrEdwardsBases"""
+        v = self.points(xy, "fr_edwards.bases")
+        h = ctypes.c_void_p()
+        check(self.ctx.lib.blsgpu_fr_edwards_bases_create(self.ctx.h, self.handle, _ptr(v), v.shape[0], int(bits), int(window), ctypes.byref(h)), "fr_edwards_bases_create")
+        return FrEdwardsBases(self.ctx, h, int(bits), int(window))
+
+    def bases_from_device(self, d_xy, n, bits, window):
+        """the same from n affine points in device memory (16-byte aligned); the table is the handle's own memory"""
+        h = ctypes.c_void_p()
+        check(self.ctx.lib.blsgpu_fr_edwards_bases_from_device(self.ctx.h, self.handle, d_xy, int(n), int(bits), int(window), ctypes.byref(h)), "fr_edwards_bases_from_device")
+        return FrEdwardsBases(self.ctx, h, int(bits), int(window))
+
+    def check_device(self, d_xy, n, d_ok):
+        check(self.ctx.lib.blsgpu_fr_edwards_check_device(self.ctx.h, self.handle, d_xy, int(n), d_ok), "fr_edwards_check_device")
+
+    def normalize_device(self, d_xyz, n, d_xy, d_ok=None):
+        check(self.ctx.lib.blsgpu_fr_edwards_normalize_device(self.ctx.h, self.handle, d_xyz, int(n), d_xy, d_ok), "fr_edwards_normalize_device")
+
+    def mul_batch_device(self, d_xy, d_scalars, bits, n, d_out_xyz):
+        """asynchronous on the context's stream; a scalar above `bits` is reported by the next Context.synchronize"""
+        check(self.ctx.lib.blsgpu_fr_edwards_mul_batch_device(self.ctx.h, self.handle, d_xy, d_scalars, int(bits), int(n), d_out_xyz), "fr_edwards_mul_batch_device")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_fr_edwards_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FrEdwardsBases:
+    """A fixed-base table on a twisted Edwards curve over Fr (`blsgpu_fr_edwards_bases`): for every base and every signed window the
+    2^(window-1) multiples, resident on the device.  msm_segments runs many independent fixed-base MSMs of any length in one call."""
+
+    def __init__(self, ctx, handle, bits, window):
+        self.ctx, self.handle, self.bits, self.window = ctx, handle, bits, window
+
+    def __len__(self):
+        return int(self.ctx.lib.blsgpu_fr_edwards_bases_len(self.handle)) if self.handle else 0
+
+    def msm_segments(self, offsets, scalars, base_first=None):
+        """out[j] = sum_i scalars[offsets[j] + i] * B[base_first[j] + i] (base_first=None: offsets[j]) -> (k, 3, 4); the contract of
+        Context.msm_segments with segments of any length"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError("fr_edwards.msm_segments: offsets holds k + 1 values")
+        k = off.shape[0] - 1
+        bf = None if base_first is None else np.ascontiguousarray(base_first, dtype=np.uint32).reshape(-1)
+        if bf is not None and bf.shape[0] != k:
+            raise ValueError("fr_edwards.msm_segments: base_first holds k values")
+        sc = FrEdwards.scalars(scalars, "fr_edwards.msm_segments")
+        if k and sc.shape[0] != int(off[k]):
+            raise ValueError("fr_edwards.msm_segments: offsets[k] scalars expected")
+        out = np.zeros((k, 3, 4), dtype=np.uint64)
+        check(self.ctx.lib.blsgpu_fr_edwards_msm_segments(self.ctx.h, self.handle, _ptr(bf), _ptr(off), _ptr(sc) if sc.shape[0] else None, k, _ptr(out)), "fr_edwards_msm_segments")
+        return out
+
+    def msm_segments_device(self, d_offsets, d_scalars, k, total, d_out_xyz, d_base_first=None):
+        """asynchronous on the context's stream; a broken segment or a scalar above `bits` is reported by the next Context.synchronize"""
+        check(self.ctx.lib.blsgpu_fr_edwards_msm_segments_device(self.ctx.h, self.handle, d_base_first, d_offsets, d_scalars, int(k), int(total), d_out_xyz), "fr_edwards_msm_segments_device")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.blsgpu_fr_edwards_bases_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _term_program(terms):
     """[(coefficient as a Python int in [0, r) or four Montgomery limbs, [table indices]), ...] -> (n_terms, term_ptr u32, term_tab u8, coef (n, 4) u64):
     the term program of include/bls12_381_hip.h (the library validates it)"""
@@ -1445,6 +1577,16 @@ class Context:
         h = ctypes.c_void_p()
         check(self.lib.blsgpu_fr_poseidon_create(self.h, t, r_full, r_partial, _ptr(rc), _ptr(mm), int(form), ctypes.byref(h)), "fr_poseidon")
         return FrPoseidon(self, h)
+
+    def fr_edwards(self, a, d):
+        """a twisted Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 over Fr (include/bls12_381_hip.h: blsgpu_fr_edwards_create): a and d as
+        Python ints in [0, r) or Montgomery limbs, the caller's (the library ships no parameter set).  a = 0, d = 0 and a = d are refused.
+        Returns an FrEdwards (.complete, .check, .normalize, .mul_batch, .bases -> FrEdwardsBases.msm_segments)."""
+        aa = _fr_limbs(a, (), "fr_edwards a")
+        dd = _fr_limbs(d, (), "fr_edwards d")
+        h = ctypes.c_void_p()
+        check(self.lib.blsgpu_fr_edwards_create(self.h, _ptr(aa), _ptr(dd), ctypes.byref(h)), "fr_edwards")
+        return FrEdwards(self, h)
 
     def fr_lookup(self, table):
         """a lookup table made resident (include/bls12_381_hip.h: blsgpu_fr_lookup_create): `table` is a (c, rows, 4) u64 array of

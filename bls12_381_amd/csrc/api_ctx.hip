@@ -249,6 +249,7 @@ static int take_status(blsgpu_ctx* c) {
     if (st & GSUM_STATUS_BAD) return bad("sum_segments_device: an index lies outside the point set (the term was skipped, that segment's value is unspecified)");
     if (st & FLG_STATUS_BAD) return bad("fr_lagrange_segments_device / lagrange_combine_device: a segment has decreasing offsets, more than BLSGPU_FR_LAGRANGE_LEN_MAX nodes or ends beyond total (nothing of it was written)");
     if (st & KZGV_STATUS_BAD) return bad("kzg_verify_cells_device: a row or cell number is out of range, or a batch's offsets are broken (that batch has verdict 0 and an identity pair)");
+    if (st & FRED_STATUS_BAD) return bad("fr_edwards_msm_segments_device: a segment has decreasing offsets, ends beyond total or names bases outside the table (its value is unspecified)");
     if (st & KZGR_STATUS_BAD) return bad("kzg_recover_device: a polynomial has a bad or duplicate cell number, fewer than c cells or broken offsets (its ok byte is 0 and its rows are zero)");
     if (st & 8u) return bad("msm_segments_device: a segment has decreasing offsets, more than SEG_LEN_MAX points or bases outside the resident set (its value is unspecified)");
     return bad("msm: a scalar is not canonical (>= r); Scalar::to_bytes never produces such bytes (scalar.rs:284-296)");

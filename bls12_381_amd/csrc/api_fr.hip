@@ -10,6 +10,7 @@
 #include "fr_spmv.hip.h"
 #include "fr_mle.hip.h"
 #include "fr_poseidon.hip.h"
+#include "fr_edwards.hip.h"
 #include "fr_expr.hip.h"
 #include "fr_lookup.hip.h"
 #include "fr_lagrange.hip.h"
@@ -964,6 +965,227 @@ extern "C" int blsgpu_fr_poseidon_merkle(blsgpu_ctx* c, const blsgpu_fr_poseidon
   void* dr = h.out(c->io_out, roots, k * 32);
   if (h.rc) return h.rc;
   return h.finish(frp_merkle_device(c, p, tag, dl, height, k, dn, dr));
+}
+
+// ---- twisted Edwards groups over Fr: checks, normalisation, products, fixed-base tables, segmented MSMs (fr_edwards.hip.h; fr_edwards_plan.h
+// holds the limits, every argument check, the recoding, the table layout and the plans) ---------------------------------------------------------
+static EdArgs fred_kargs(const uint32_t* a, const uint32_t* d) {
+  EdArgs k;
+  for (int i = 0; i < 8; i++) { k.a.w[i] = a[i]; k.d.w[i] = d[i]; }
+  return k;
+}
+extern "C" int blsgpu_fr_edwards_create(blsgpu_ctx* c, const uint64_t a[4], const uint64_t d[4], blsgpu_fr_edwards** out) { CTX_CLAIM(c);
+  if (out) *out = nullptr;
+  if (!c || !out) return bad("fr_edwards_create: NULL context / out");
+  FredCurve cv;
+  if (const char* what = fred_curve_check(a, d, &cv)) return bad(what);
+  blsgpu_fr_edwards* e = new blsgpu_fr_edwards();
+  e->device = c->device; e->complete = cv.complete;
+  for (int w = 0; w < 4; w++) { e->a[2 * w] = (u32)a[w]; e->a[2 * w + 1] = (u32)(a[w] >> 32); e->d[2 * w] = (u32)d[w]; e->d[2 * w + 1] = (u32)(d[w] >> 32); }
+  for (int w = 0; w < 4; w++) { e->a64[w] = a[w]; e->d64[w] = d[w]; }
+  *out = e;
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_edwards_complete(const blsgpu_fr_edwards* e) { return e ? e->complete : 0; }
+extern "C" void blsgpu_fr_edwards_free(blsgpu_fr_edwards* e) {
+  if (!e) return;
+  handle_quiesce(e->device);               // the rule of every handle's free; the constants themselves travel by value
+  delete e;
+}
+static int fred_handle_check(blsgpu_ctx* c, const blsgpu_fr_edwards* e) {
+  if (!c) return bad("fr_edwards: NULL context");
+  if (!e) return bad("fr_edwards: NULL curve");
+  if (e->device != c->device) return bad("fr_edwards: the curve was created for another device than the context");
+  return BLSGPU_OK;
+}
+// a host form's verdict: the sticky word of a synchronous call means a scalar with a bit at or above `bits`
+static int fred_finish(HostCall& h, int core_rc) {
+  const int rc = h.finish(core_rc);
+  if (rc == BLSGPU_ERR_ARG && h.status_host) g_err = "fr_edwards: a scalar has a bit set at or above `bits` (the value of that output is unspecified)";
+  return rc;
+}
+
+extern "C" int blsgpu_fr_edwards_check_device(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const void* d_xy, size_t n, void* d_ok) { CTX_CLAIM(c);
+  if (int rc = fred_handle_check(c, e)) return rc;
+  if (const char* what = fred_check_args(d_xy, n, d_ok, true)) return bad(what);
+  if (!n) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const FredLaunch l = fred_points_launch(n);
+  KLAUNCH(k_fred_check, dim3(l.grid), dim3(l.block), 0, c->stream, fred_kargs(e->a, e->d), (const u32*)d_xy, n, (uint8_t*)d_ok);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_edwards_check(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const uint64_t* xy, size_t n, uint8_t* ok) { CTX_CLAIM(c);
+  if (int rc = fred_handle_check(c, e)) return rc;
+  if (const char* what = fred_check_args(xy, n, ok, false)) return bad(what);
+  if (!n) return BLSGPU_OK;
+  HostCall h(c);
+  void* dx = h.in(c->io_a, xy, n * 64);
+  void* dk = h.out(c->flags_a, ok, n);
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_edwards_check_device(c, e, dx, n, dk));
+}
+
+extern "C" int blsgpu_fr_edwards_normalize_device(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const void* d_xyz, size_t n, void* d_xy, void* d_ok) { CTX_CLAIM(c);
+  if (int rc = fred_handle_check(c, e)) return rc;
+  if (const char* what = fred_normalize_args(d_xyz, n, d_xy, d_ok, true)) return bad(what);
+  if (!n) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const FredLaunch l = fred_points_launch(n);
+  KLAUNCH(k_fred_normalize<false>, dim3(l.grid), dim3(l.block), l.lds, c->stream, fred_kargs(e->a, e->d), (const u32*)d_xyz, n, (u32*)d_xy, (uint8_t*)d_ok);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_edwards_normalize(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const uint64_t* xyz, size_t n, uint64_t* xy, uint8_t* ok) { CTX_CLAIM(c);
+  if (int rc = fred_handle_check(c, e)) return rc;
+  if (const char* what = fred_normalize_args(xyz, n, xy, ok, false)) return bad(what);
+  if (!n) return BLSGPU_OK;
+  HostCall h(c);
+  void* di = h.in(c->io_a, xyz, n * 96);
+  void* dx = h.out(c->io_out, xy, n * 64);
+  void* dk = ok ? h.out(c->flags_a, ok, n) : nullptr;
+  if (h.rc) return h.rc;
+  return h.finish(blsgpu_fr_edwards_normalize_device(c, e, di, n, dx, dk));
+}
+
+extern "C" int blsgpu_fr_edwards_mul_batch_device(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const void* d_xy, const void* d_scalars, int bits, size_t n, void* d_out_xyz) { CTX_CLAIM(c);
+  if (int rc = fred_handle_check(c, e)) return rc;
+  if (const char* what = fred_mul_args(d_xy, d_scalars, bits, n, d_out_xyz, true)) return bad(what);
+  if (!n) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const FredMulPlan p = fred_mul_plan(n, bits);
+  if (!p.ok) return bad("fr_edwards_mul_batch: no plan for these sizes");
+  KLAUNCH(k_fred_mul, dim3(p.mul.grid), dim3(p.mul.block), p.mul.lds, c->stream, fred_kargs(e->a, e->d), (const u32*)d_xy, (const u32*)d_scalars, bits, n, (u32*)d_out_xyz,
+          c->status_word);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_edwards_mul_batch(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const uint64_t* xy, const uint8_t* scalars, int bits, size_t n, uint64_t* out_xyz) { CTX_CLAIM(c);
+  if (int rc = fred_handle_check(c, e)) return rc;
+  if (const char* what = fred_mul_args(xy, scalars, bits, n, out_xyz, false)) return bad(what);
+  if (!n) return BLSGPU_OK;
+  HostCall h(c);
+  h.report_status();
+  void* dx = h.in(c->io_a, xy, n * 64);
+  void* ds = h.in(c->io_b, scalars, n * 32);
+  void* dout = h.out(c->io_out, out_xyz, n * 96);
+  if (h.rc) return h.rc;
+  return fred_finish(h, blsgpu_fr_edwards_mul_batch_device(c, e, dx, ds, bits, n, dout));
+}
+
+// the table of n bases at d_xy (device memory), built and normalised on the device; synchronises (a setup call) and reads the flag back
+static int fred_bases_build(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const void* d_xy, const FredTablePlan& p, blsgpu_fr_edwards_bases** out) {
+  HIPCHK(hipSetDevice(c->device));
+  blsgpu_fr_edwards_bases* t = new blsgpu_fr_edwards_bases();
+  t->device = c->device; t->bits = p.bits; t->window = p.window; t->W = p.W; t->H = p.H; t->n = p.n;
+  for (int i = 0; i < 8; i++) { t->a[i] = e->a[i]; t->d[i] = e->d[i]; }
+  auto build = [&]() -> int {
+    HIPCHK(hipMalloc((void**)&t->table, p.bytes + 16));                   // the last 16 bytes: the flag of the build
+    u32* flag = t->table + p.entries * FRED_ENTRY_WORDS;
+    HIPCHK(hipMemsetAsync(flag, 0, 16, c->stream));
+    const EdArgs k = fred_kargs(e->a, e->d);
+    KLAUNCH(k_fred_table_build, dim3(p.build.grid), dim3(p.build.block), 0, c->stream, k, (const u32*)d_xy, p.n, p.window, p.W, p.H, t->table, flag);
+    KLAUNCH(k_fred_normalize<true>, dim3(p.norm.grid), dim3(p.norm.block), p.norm.lds, c->stream, k, (const u32*)t->table, p.entries, t->table, (uint8_t*)nullptr);
+    LAUNCHCHK();
+    u32 bad_base = 0;
+    HIPCHK(hipMemcpyAsync(&bad_base, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (bad_base) return bad("fr_edwards_bases: a base is not a point of the curve (or has limbs >= r)");
+    return BLSGPU_OK;
+  };
+  if (int rc = build()) { (void)hipStreamSynchronize(c->stream); if (t->table) hipFree(t->table); delete t; return rc; }
+  *out = t;
+  return BLSGPU_OK;
+}
+static int fred_bases_check(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const void* xy, size_t n, int bits, int window, bool device, blsgpu_fr_edwards_bases** out, FredTablePlan* p) {
+  if (out) *out = nullptr;
+  if (int rc = fred_handle_check(c, e)) return rc;
+  if (!out) return bad("fr_edwards_bases: NULL out");
+  if (!xy) return bad("fr_edwards_bases: NULL xy");
+  *p = fred_table_plan(n, bits, window);
+  if (!p->ok) return bad(p->why);
+  if (device && fred_misaligned(xy)) return bad("fr_edwards_bases_from_device: d_xy must be 16-byte aligned");
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_edwards_bases_from_device(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const void* d_xy, size_t n, int bits, int window, blsgpu_fr_edwards_bases** out) { CTX_CLAIM(c);
+  FredTablePlan p;
+  if (int rc = fred_bases_check(c, e, d_xy, n, bits, window, true, out, &p)) return rc;
+  return fred_bases_build(c, e, d_xy, p, out);
+}
+extern "C" int blsgpu_fr_edwards_bases_create(blsgpu_ctx* c, const blsgpu_fr_edwards* e, const uint64_t* xy, size_t n, int bits, int window, blsgpu_fr_edwards_bases** out) { CTX_CLAIM(c);
+  FredTablePlan p;
+  if (int rc = fred_bases_check(c, e, xy, n, bits, window, false, out, &p)) return rc;
+  FredCurve cv;
+  cv.a = fred_fe(e->a64); cv.d = fred_fe(e->d64);
+  for (size_t i = 0; i < n; i++)
+    if (!fred_on_curve(cv, xy + 8 * i)) {
+      char buf[128];
+      snprintf(buf, sizeof buf, "fr_edwards_bases_create: base %zu is not a point of the curve (or has limbs >= r)", i);
+      g_err = buf;
+      return BLSGPU_ERR_ARG;
+    }
+  HostCall h(c);
+  void* dx = h.in(c->io_a, xy, n * 64);
+  if (h.rc) return h.rc;
+  return fred_bases_build(c, e, dx, p, out);
+}
+extern "C" size_t blsgpu_fr_edwards_bases_len(const blsgpu_fr_edwards_bases* t) { return t ? t->n : 0; }
+extern "C" void blsgpu_fr_edwards_bases_free(blsgpu_fr_edwards_bases* t) {
+  if (!t) return;
+  handle_quiesce(t->device);               // an asynchronous MSM may still be reading the table
+  if (t->table) hipFree(t->table);
+  delete t;
+}
+
+static int fred_msm_check(blsgpu_ctx* c, const blsgpu_fr_edwards_bases* t, const void* base_first, const void* offsets, const void* scalars, size_t k, size_t total, const void* out,
+                          bool device) {
+  if (!c) return bad("fr_edwards_msm_segments: NULL context");
+  if (!t) return bad("fr_edwards_msm_segments: NULL table");
+  if (t->device != c->device) return bad("fr_edwards_msm_segments: the table lives on another device than the context");
+  FredMsmArgs a;
+  a.nbases = t->n; a.base_first = base_first; a.offsets = offsets; a.scalars = scalars; a.k = k; a.total = total; a.out = out; a.device = device;
+  if (const char* what = fred_msm_args(a)) return bad(what);
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_edwards_msm_segments_device(blsgpu_ctx* c, const blsgpu_fr_edwards_bases* t, const void* d_base_first, const void* d_offsets, const void* d_scalars, size_t k,
+                                                     size_t total, void* d_out_xyz) { CTX_CLAIM(c);
+  if (int rc = fred_msm_check(c, t, d_base_first, d_offsets, d_scalars, k, total, d_out_xyz, true)) return rc;
+  if (!k) return BLSGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const FredMsmPlan p = fred_msm_plan(k, total);
+  if (!p.ok) return bad("fr_edwards_msm_segments: no plan for these sizes");
+  if (c->fred_off.reserve(p.off_bytes) || c->fred_part.reserve(p.part_bytes + 16) || c->fred_meta.reserve(p.meta_bytes + 16)) {
+    g_err = "hipMalloc(fr edwards msm scratch) failed"; return BLSGPU_ERR_HIP;
+  }
+  hipStream_t st = c->stream;
+  unsigned long long* off = c->fred_off.as<unsigned long long>();
+  EdMsmArgs m;
+  m.c = fred_kargs(t->a, t->d); m.table = t->table; m.nbases = (u32)t->n; m.bits = t->bits; m.window = t->window; m.W = t->W; m.H = t->H;
+  KLAUNCH(k_fred_msm_prep, dim3(p.prep.grid), dim3(p.prep.block), 0, st, (const u32*)d_offsets, (const u32*)d_base_first, k, (u32)total, t->n, off, c->status_word);
+  if (p.chunks.grid)
+    KLAUNCH(k_fred_msm_chunks, dim3(p.chunks.grid), dim3(p.chunks.block), p.chunks.lds, st, m, (const u32*)d_base_first, (const u32*)d_scalars, (const unsigned long long*)off, (u32)k,
+            (u32)total, p.cut.terms, (u32*)d_out_xyz, c->fred_part.as<u32>(), c->fred_meta.as<u32>(), c->status_word);
+  KLAUNCH(k_fred_msm_combine, dim3(p.combine.grid), dim3(p.combine.block), p.combine.lds, st, m.c, (const unsigned long long*)off, (u32)k, (u32)total, p.cut.chunk, p.cut.nchunks,
+          (const u32*)c->fred_part.as<u32>(), (const u32*)c->fred_meta.as<u32>(), (u32*)d_out_xyz);
+  LAUNCHCHK();
+  return BLSGPU_OK;
+}
+extern "C" int blsgpu_fr_edwards_msm_segments(blsgpu_ctx* c, const blsgpu_fr_edwards_bases* t, const uint32_t* base_first, const uint32_t* offsets, const uint8_t* scalars, size_t k,
+                                              uint64_t* out_xyz) { CTX_CLAIM(c);
+  if (int rc = fred_msm_check(c, t, base_first, offsets, nullptr, k, 0, out_xyz, false)) return rc;
+  if (!k) return BLSGPU_OK;
+  size_t total = 0;
+  if (const char* what = fred_msm_args_host(offsets, base_first, k, t->n, &total)) return bad(what);
+  if (int rc = fred_msm_check(c, t, base_first, offsets, scalars, k, total, out_xyz, false)) return rc;
+  HostCall h(c);
+  h.report_status();
+  void* doff = h.in(c->io_a, offsets, (k + 1) * 4);
+  void* dbf = h.in(c->io_b, base_first, k * 4);
+  void* ds = total ? h.in(c->io_e, scalars, total * 32) : nullptr;
+  void* dout = h.out(c->io_out, out_xyz, k * 96);
+  if (h.rc) return h.rc;
+  if (!ds) { if (!h.reserve(c->io_e, 16)) return h.rc; ds = c->io_e.p; }      // no term: nothing is read, but the device form wants a pointer
+  return fred_finish(h, blsgpu_fr_edwards_msm_segments_device(c, t, dbf, doff, ds, k, total, dout));
 }
 
 // ---- expression programs: gate and quotient columns in one pass (fr_expr.hip.h; fr_expr_plan.h validates, builds the image and plans) ------

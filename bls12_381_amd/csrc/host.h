@@ -9,7 +9,8 @@
 //   api_pairing.hip  pairings, Miller loops, G2Prepared, final exponentiation, Gt, Fp6 / Fp12 hooks   (pairing / quad / prep / wide)
 //   api_aux.hip      hash-to-curve, expanders and hash-to-scalar, point codecs, bulk BLS verification   (h2c / expand_kernels / codec / generators)
 //   api_fr.hip       Fr vectors, transforms, scans, Lagrange, fraction scans, openings, SpMV, Poseidon,  (fr*.hip.h)
-//                    expression programs, lookup tables, multilinear folds and sumcheck, KZG cell recovery       (kzg_recover.hip.h)
+//                    expression programs, lookup tables, multilinear folds and sumcheck, KZG cell recovery,      (kzg_recover.hip.h)
+//                    twisted Edwards groups over Fr
 //   api_group.hip    device groups: one process driving several GPUs (host code only)
 //
 // Every kernel header is compiled into exactly ONE of them (a non-template __global__ function has one host-side stub per library).
@@ -44,6 +45,7 @@
 #include "kzg_plan.h"
 #include "kzg_verify_plan.h"
 #include "kzg_recover_plan.h"
+#include "fr_edwards_plan.h"
 
 using namespace bls;
 
@@ -257,6 +259,7 @@ struct blsgpu_ctx {
   DevBuf kzgr_roots; int kzgr_roots_log_c = -1, kzgr_roots_log_l = -1;      // ... and its root tables (w^l)^rho, g^l (w^l)^rho of the last (log_c, log_l) used
   hipEvent_t ev_kzgr_roots = nullptr;   // as ev_fr_cs: recorded where the tables were built, awaited by every user
   DevBuf frp_nodes;                     // blsgpu_fr_poseidon_merkle_device with nodes == NULL: the levels below the roots (fr_poseidon_plan.h)
+  DevBuf fred_off, fred_part, fred_meta;          // blsgpu_fr_edwards_msm_segments_device: the widened offsets, two partial records and two segment numbers per chunk (fr_edwards_plan.h)
 };
 
 static inline KTimer* ktimer_of(blsgpu_ctx* c) { return &c->ktimer; }
@@ -310,6 +313,22 @@ struct blsgpu_fr_poseidon {
   FrpArgs args = {};
   size_t products = 0;
   u32* image = nullptr;
+};
+
+// a twisted Edwards curve over Fr (api_fr.hip: blsgpu_fr_edwards_create; fr_edwards.hip.h): the two constants, which the kernels take by value,
+// and the verdict of the completeness test.  Nothing of it lives in device memory.
+struct blsgpu_fr_edwards {
+  int device = 0; int complete = 0;
+  uint32_t a[8] = {}, d[8] = {};
+  uint64_t a64[4] = {}, d64[4] = {};
+};
+// a fixed-base table on such a curve (api_fr.hip: blsgpu_fr_edwards_bases_create / _from_device): its own copy of the constants, the shape
+// and n * W * H entries (x, y, d x y), laid out by fr_edwards_plan.h
+struct blsgpu_fr_edwards_bases {
+  int device = 0; int bits = 0, window = 0, W = 0, H = 0;
+  size_t n = 0;
+  uint32_t a[8] = {}, d[8] = {};
+  u32* table = nullptr;
 };
 
 // an Fr expression program resident on the device (api_fr.hip: blsgpu_fr_expr_create; fr_expr.hip.h): what the accessors report and

@@ -822,6 +822,75 @@ int blsgpu_fr_poseidon_hash_many(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, c
 int blsgpu_fr_poseidon_hash_many_device(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const void* d_inputs, size_t n, void* d_out);
 int blsgpu_fr_poseidon_merkle(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const uint64_t* leaves, int height, size_t k, uint64_t* nodes, uint64_t* roots);
 int blsgpu_fr_poseidon_merkle_device(blsgpu_ctx* ctx, const blsgpu_fr_poseidon* p, const uint64_t tag[4], const void* d_leaves, int height, size_t k, void* d_nodes, void* d_roots);
+/* TWISTED EDWARDS GROUPS OVER Fr: the curves  a x^2 + y^2 = 1 + d x^2 y^2  whose coordinates are `Scalar`s -- Jubjub (Pedersen hashes, note
+ * commitments, RedJubjub keys) and Bandersnatch (256-wide Pedersen vector commitments) are two of them.  The group law is the unified addition
+ *   (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + d x1 x2 y1 y2), (y1 y2 - a x1 x2) / (1 - d x1 x2 y1 y2)),
+ * the identity is (0, 1) and -(x, y) = (-x, y), built on `Scalar`'s mul / add / sub (scalar.rs:452-503, :435-449, :420-432; the reference
+ * crate has no such group).  THE LIBRARY SHIPS NO PARAMETER SET: a and d are the caller's, as the constants of a Poseidon instance are.
+ * Formats.  An Fr element is four canonical Montgomery u64 limbs, as everywhere in the Fr entry points.  An AFFINE point is (x, y), 8 u64;
+ * there is no infinity byte.  A RESULT point is (X : Y : Z), 12 u64, x = X / Z, y = Y / Z: the representative is unspecified, compare after
+ * normalize (as for `*_mul_batch`).  A SCALAR is a plain 256-bit little-endian integer of 32 bytes -- NOT an Fr element (the order of such
+ * a group is not r): it is never compared with r and does not depend on blsgpu_set_scalar_form.  `bits` in [1, 256] says how many low bits of
+ * every scalar are read; a scalar with a bit set at or above `bits` is reported as a scalar >= r is elsewhere (BLSGPU_ERR_ARG from a host
+ * form; the sticky status word and the next blsgpu_synchronize for a device form) and the value of that ONE output is unspecified.
+ * Completeness.  blsgpu_fr_edwards_complete returns 1 exactly when a is a square and d is a non-square (two Euler-criterion powers on the
+ * host).  On such a curve every operation below is exact for EVERY pair of curve points: the points of order 2 and 4, P + P, P + (-P).  On a
+ * curve that is NOT complete (Bandersnatch: a = -5 is a non-square) results are exact when every input point has ODD order and are
+ * unspecified otherwise -- a promise of the caller's like blsgpu_set_assume_subgroup, not checked.  Points off the curve: unspecified values,
+ * never an access outside the arrays.
+ *   create        refuses a = 0, d = 0, a = d (a singular curve) and limbs >= r: BLSGPU_ERR_ARG, *out stays NULL, blsgpu_last_error names
+ *                 the argument.  The handle holds no device memory; blsgpu_fr_edwards_free follows blsgpu_fr_matrix_free.
+ *   check         ok[i] = 1 iff point i has limbs below r and satisfies the curve equation.
+ *   normalize     (X : Y : Z) -> (X / Z, Y / Z) with ONE inversion per 256 points; where Z = 0, (0, 1) is written and ok[i] = 0 (ok may be
+ *                 NULL).  There is no in-place form (the strides differ): any overlap of xy with xyz is refused.
+ *   mul_batch     out[i] = s_i * P_i for n independent pairs in one launch: signed 3-bit windows, 3 (ceil((bits + 1) / 3) - 1) doublings
+ *                 whatever the scalars hold, so bits = 64 does a quarter of the work of 256.
+ *   bases_create / bases_from_device   a fixed-base table for n bases: for every base B and each of W = ceil((bits + 1) / window) signed
+ *                 windows the 2^(window-1) multiples k 2^(window w) B, affine with d x y beside them (96 bytes an entry), built and
+ *                 normalised on the device.  window in [2, 8], n in [1, 2^24], and n * W * 2^(window-1) * 96 bytes at most 2 GiB.  A setup
+ *                 call: it synchronises.  A base that fails `check` is refused: the host form names it, the device form reads a flag back.
+ *                 blsgpu_fr_edwards_bases_free follows blsgpu_fr_matrix_free.  A table keeps its own copy of a and d.
+ *   msm_segments  out[j] = sum_{i < len_j} scalars[offsets[j] + i] * B[base_first[j] + i]: the contract of blsgpu_g1_msm_segments (k + 1
+ *                 non-decreasing u32 offsets with offsets[0] = 0 and offsets[k] = total, base_first == NULL means base_first[j] =
+ *                 offsets[j], overlapping slices -- a shared generator set -- allowed) with segments of ANY length: total <= 2^26, k <= 2^26.
+ *                 The scalars are read with the table's `bits`.  No doublings: a term is W table additions.  The term list is cut into
+ *                 chunks as blsgpu_g1_sum_segments cuts its own; an empty segment gives (0 : 1 : 1); k = 0 does nothing.  No atomics touch
+ *                 a result and no workgroup waits for another: results are limb-identical from run to run after normalize.
+ *                 Host form: offsets, base ranges and sizes are checked before anything is staged.  Device form: `total` = offsets[k] as
+ *                 the caller knows it; a segment that breaks the rules (offsets[0] != 0, decreasing offsets, offsets[j + 1] > total,
+ *                 offsets[k] != total, bases outside the table) is reported by the next blsgpu_synchronize (BLSGPU_ERR_ARG), its value and
+ *                 that of its neighbours in the same chunks are unspecified, and nothing outside the caller's arrays is read or written.
+ * Limits: n <= 2^26 points per check / normalize / mul_batch call.  Device pointers must be 16-byte aligned (d_offsets / d_base_first: 4).
+ * The device forms are asynchronous on the context's stream and never synchronise (the table builds excepted); the MSM's scratch is the
+ * context's own.  BLSGPU_ERR_ARG (nothing staged or launched): a NULL pointer with work to do, a handle of another device, bits or window
+ * out of range, a size above its limit, a misaligned device pointer, an output that overlaps an input.  What a device form CANNOT refuse:
+ * limbs >= r and points off the curve in check's sense (unspecified values), a scalar above `bits` and a broken segment (both reported by
+ * the next synchronise). */
+typedef struct blsgpu_fr_edwards blsgpu_fr_edwards;
+typedef struct blsgpu_fr_edwards_bases blsgpu_fr_edwards_bases;
+#define BLSGPU_FR_EDWARDS_MAX_POINTS ((size_t)1 << 26)      /* check / normalize / mul_batch: points of one call */
+#define BLSGPU_FR_EDWARDS_MAX_TOTAL  ((size_t)1 << 26)      /* msm_segments: terms, and segments, of one call */
+#define BLSGPU_FR_EDWARDS_MAX_BASES  ((size_t)1 << 24)      /* bases of one table */
+#define BLSGPU_FR_EDWARDS_TABLE_MAX_BYTES ((size_t)1 << 31) /* bytes of one table */
+#define BLSGPU_FR_EDWARDS_WINDOW_MIN 2
+#define BLSGPU_FR_EDWARDS_WINDOW_MAX 8
+int blsgpu_fr_edwards_create(blsgpu_ctx* ctx, const uint64_t a[4], const uint64_t d[4], blsgpu_fr_edwards** out);
+int blsgpu_fr_edwards_complete(const blsgpu_fr_edwards* e);
+void blsgpu_fr_edwards_free(blsgpu_fr_edwards* e);
+int blsgpu_fr_edwards_check(blsgpu_ctx* ctx, const blsgpu_fr_edwards* e, const uint64_t* xy, size_t n, uint8_t* ok);
+int blsgpu_fr_edwards_check_device(blsgpu_ctx* ctx, const blsgpu_fr_edwards* e, const void* d_xy, size_t n, void* d_ok);
+int blsgpu_fr_edwards_normalize(blsgpu_ctx* ctx, const blsgpu_fr_edwards* e, const uint64_t* xyz, size_t n, uint64_t* xy, uint8_t* ok);
+int blsgpu_fr_edwards_normalize_device(blsgpu_ctx* ctx, const blsgpu_fr_edwards* e, const void* d_xyz, size_t n, void* d_xy, void* d_ok);
+int blsgpu_fr_edwards_mul_batch(blsgpu_ctx* ctx, const blsgpu_fr_edwards* e, const uint64_t* xy, const uint8_t* scalars, int bits, size_t n, uint64_t* out_xyz);
+int blsgpu_fr_edwards_mul_batch_device(blsgpu_ctx* ctx, const blsgpu_fr_edwards* e, const void* d_xy, const void* d_scalars, int bits, size_t n, void* d_out_xyz);
+int blsgpu_fr_edwards_bases_create(blsgpu_ctx* ctx, const blsgpu_fr_edwards* e, const uint64_t* xy, size_t n, int bits, int window, blsgpu_fr_edwards_bases** out);
+int blsgpu_fr_edwards_bases_from_device(blsgpu_ctx* ctx, const blsgpu_fr_edwards* e, const void* d_xy, size_t n, int bits, int window, blsgpu_fr_edwards_bases** out);
+size_t blsgpu_fr_edwards_bases_len(const blsgpu_fr_edwards_bases* t);
+void blsgpu_fr_edwards_bases_free(blsgpu_fr_edwards_bases* t);
+int blsgpu_fr_edwards_msm_segments(blsgpu_ctx* ctx, const blsgpu_fr_edwards_bases* t, const uint32_t* base_first, const uint32_t* offsets, const uint8_t* scalars, size_t k,
+                                   uint64_t* out_xyz);
+int blsgpu_fr_edwards_msm_segments_device(blsgpu_ctx* ctx, const blsgpu_fr_edwards_bases* t, const void* d_base_first, const void* d_offsets, const void* d_scalars, size_t k,
+                                          size_t total, void* d_out_xyz);
 /* Fr EXPRESSION PROGRAMS: the row-wise evaluation of a constraint expression -- gates, a permutation term with its next-row operand,
  * boundary terms, all times 1 / Z_H -- over columns resident on the device, in ONE pass: the quotient numerator of a PLONK / halo2-style
  * prover on the extended coset domain between blsgpu_fr_ntt_many (onto the coset) and blsgpu_fr_ntt_many (back).  The expression is a

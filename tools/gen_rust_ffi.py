@@ -40,6 +40,8 @@ UNTYPED_FOR_RUST = {"blsgpu_fr_matrix*": "void*", "const blsgpu_fr_matrix*": "co
                     "blsgpu_fr_lookup*": "void*", "const blsgpu_fr_lookup*": "const void*", "blsgpu_fr_lookup**": "void*",
                     "blsgpu_kzg_multiproof*": "void*", "const blsgpu_kzg_multiproof*": "const void*", "blsgpu_kzg_multiproof**": "void*",
                     "blsgpu_kzg_cell_verifier*": "void*", "const blsgpu_kzg_cell_verifier*": "const void*", "blsgpu_kzg_cell_verifier**": "void*",
+                    "blsgpu_fr_edwards*": "void*", "const blsgpu_fr_edwards*": "const void*", "blsgpu_fr_edwards**": "void*",
+                    "blsgpu_fr_edwards_bases*": "void*", "const blsgpu_fr_edwards_bases*": "const void*", "blsgpu_fr_edwards_bases**": "void*",
                     # likewise an array of host pointers to scalars (an array of untyped pointers), and a 32-bit mask returned as `unsigned`
                     "const uint64_t*const*": "const void*const*", "uint32_t": "unsigned"}
 
